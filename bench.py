@@ -56,6 +56,9 @@ def parse():
     ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE configs[2] leg (one training step, scripts/train_bench.py as a child process)")
     ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE configs[4] leg (video_text_to_music, scripts/video_bench.py as a child process)")
     ap.add_argument("--cpu-steps", type=int, default=7, help="timed CPU-oracle decode steps (median; two warm-up steps before them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (codec logits of every CFG row, the codes "
+                         "generated so far) as DIR/<name>.npy in float32, at most 64 MB in all; same arguments = same inputs")
     return ap.parse_args()
 
 
@@ -94,8 +97,9 @@ def build_model(cfg, device):
     return model, time.time() - t0
 
 
-def decode_leg(model, cfg, args, device, rank, B, ep=None, profile=True, steps=None, warmup=None):
-    """prefill + W warm-up steps + K timed steps of one engine; the timed region is bracketed by barrier + synchronize."""
+def decode_leg(model, cfg, args, device, rank, B, ep=None, profile=True, steps=None, warmup=None, outputs=False):
+    """prefill + W warm-up steps + K timed steps of one engine; the timed region is bracketed by barrier + synchronize.
+    outputs: also return what the last timed step left for a caller (info["outputs"], host arrays), read before any further step."""
     from unimoe_audio_amd.codec_utils import prepare_audio_prompt
     from unimoe_audio_amd.model import DecodeEngine
     T = args.prompt
@@ -132,6 +136,10 @@ def decode_leg(model, cfg, args, device, rank, B, ep=None, profile=True, steps=N
     hit = (masks[:, :, : cfg.mlp_dynamic_expert_num].sum(1) > 0).sum(1).float()          # |U_l| per layer (last step)
     topk = eng.copy_buffer("all_topk", torch.int64, (cfg.num_hidden_layers, 2 * B)).cpu().float()
     tokens = eng.tokens[:, : K + W + 2].cpu().clone()
+    last = None
+    if outputs:          # (profile_steps below runs further eager steps: the last timed step's buffers are read before it)
+        logits = eng.copy_buffer("logits", torch.float32, (2 * B, cfg.codec_channels * cfg.codec_vocab_size)).cpu()
+        last = {"logits": logits.numpy(), "tokens": tokens.float().numpy()}
     prof = eng.profile_steps(4) if profile else None
     expert_launch = eng.info("expert_launch")
     err = eng.ep_error() if ep is not None else 0
@@ -141,9 +149,26 @@ def decode_leg(model, cfg, args, device, rank, B, ep=None, profile=True, steps=N
     if ep is not None:
         barrier()                     # peers may still be reading this rank's exchange region
     info = dict(dt=dt, t_prefill=t_prefill, mean_experts_hit=float(hit.mean()), mean_top_k=float(topk.mean()), prof=prof,
-                kv_len_first=T + W, kv_len_end=T + W + K, tokens=tokens, ep_error=err, steps=K, expert_launch=expert_launch)
+                kv_len_first=T + W, kv_len_end=T + W + K, tokens=tokens, ep_error=err, steps=K, expert_launch=expert_launch, outputs=last)
     eng.close()
     return info
+
+
+DUMP_MAX_BYTES = 60 << 20      # array data of one --dump-outputs directory (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """Writes every array as path/<name><suffix>.npy in float32.  When together they exceed DUMP_MAX_BYTES, each keeps a fixed
+    seeded sample of its elements in proportion to its size (flattened, ascending index order: the same elements in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, a.size * DUMP_MAX_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def barrier():
@@ -494,7 +519,7 @@ def main():
                 ok, why = 0, repr(e)
             ok_all = -max_over_ranks(-float(ok))
             if ok_all >= 1.0:
-                ep_info = decode_leg(model, cfg, args, device, rank, B, ep=link)
+                ep_info = decode_leg(model, cfg, args, device, rank, B, ep=link, outputs=bool(args.dump_outputs))
                 ep_info["backend"] = be
                 if max_over_ranks(float(ep_info["ep_error"])) == 0.0:
                     break
@@ -508,7 +533,7 @@ def main():
             notes["ep"] = "no expert-parallel backend worked on this node: `value` is the replica number"
     rep_info = None
     if mode != "ep" or not args.no_replica_check:
-        rep_info = decode_leg(model, cfg, args, device, rank, B)
+        rep_info = decode_leg(model, cfg, args, device, rank, B, outputs=bool(args.dump_outputs))
     if mode == "ep" and rep_info is not None:
         # both layouts were timed with the same K steps and give the same tokens (checked below): `auto` reports the faster one as `value`
         # and names the other in config; --parallel ep keeps the expert-parallel number whatever the replicas do
@@ -527,6 +552,8 @@ def main():
             notes["parallelism_choice"] = "auto: the expert-parallel layout was faster than N independent replicas on this node; both numbers above"
     info = ep_info if mode == "ep" else rep_info
     dt = max_over_ranks(info["dt"])                                     # the slowest rank defines the step time
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, info["outputs"], "" if world == 1 else f"_rank{rank}")
     out = None
     value = world * B * K / dt
     if rank == 0:

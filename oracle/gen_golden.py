@@ -20,13 +20,30 @@ Fixture families
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import types
 
-import numpy as np
-import torch
+# MKL's reproducible COMPATIBLE branch (tests/test_oracle_golden.py, PINNED_MKL): the fp32 gate logits of the dcmoe / dcmoebwd
+# fixtures are then the same bits on Intel and AMD hosts (together with one thread, see one_thread)
+os.environ["MKL_CBWR"] = "COMPATIBLE,STRICT"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 from . import _ref_shim
+
+
+@contextlib.contextmanager
+def one_thread():
+    """MKL's sgemm rounds by its thread split: the dcmoe / dcmoebwd fixtures are written on one thread, as
+    tests/test_oracle_golden.py runs their blocks."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
 
 
 def _np(t):
@@ -715,7 +732,8 @@ def main():
         if a.only and k not in a.only.split(","):
             continue
         print("==", k)
-        fn(ref, a.out)
+        with one_thread() if k in ("dcmoe", "dcmoebwd") else contextlib.nullcontext():
+            fn(ref, a.out)
 
 
 if __name__ == "__main__":

@@ -47,3 +47,27 @@ def test_roofline_entry_of_the_fused_launch_uses_all_three_projections():
     info["prof"]["down"] = (0.023, 36)
     r2 = bench.roofline(cfg, info, args, 1)
     assert r2["bytes_per_launch"] == (8 * 2 * 2752 * 2048 + 2 * 2 * 1376 * 2048) * 2
+
+
+def test_dump_outputs_float32_under_the_cap_and_the_same_sample_every_run(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    assert bench.DUMP_MAX_BYTES + 4096 <= 64 * 10 ** 6            # the .npy headers of a dump directory fit beside the data
+    small = {"logits": np.arange(12, dtype=np.float64).reshape(3, 4), "tokens": np.arange(6, dtype=np.int32).reshape(2, 3)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    # over the cap: every array keeps a seeded sample of its elements, in proportion to its size, the same one in every run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40_000)
+    rng = np.random.default_rng(3)
+    big = {"logits": rng.standard_normal((9, 5000), dtype=np.float32), "tokens": rng.integers(0, 1027, (5, 1000))}
+    bench.dump_outputs(str(tmp_path / "b"), big, "_rank1")
+    bench.dump_outputs(str(tmp_path / "c"), big, "_rank1")
+    total = 0
+    for k in big:
+        b, c = np.load(tmp_path / "b" / f"{k}_rank1.npy"), np.load(tmp_path / "c" / f"{k}_rank1.npy")
+        assert b.dtype == np.float32 and np.array_equal(b, c) and 0 < b.size < big[k].size
+        assert np.isin(b, big[k].astype(np.float32)).all()
+        total += b.nbytes
+    assert total <= 40_000
