@@ -8,12 +8,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 _MODEL = None
 
 
-def inference(task, input_text, model_path, ref_audio=None, ref_text=None, video=None, output="./output", device=0, reuse=True):
+def inference(task, input_text, model_path, ref_audio=None, ref_text=None, video=None, output="./output", device=0, reuse=True,
+              expert_weights="bf16"):
     global _MODEL
     from unimoe_audio_amd.api import UniMoEAudio
     try:
         if _MODEL is None or not reuse:
-            _MODEL = UniMoEAudio(model_path, device)
+            _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights)
         if task == "text_to_speech":
             return _MODEL.text_to_speech(input_text, ref_text, ref_audio, output_dir=output)
         if task == "text_to_music":
@@ -37,8 +38,10 @@ def main():
     ap.add_argument("--model", "-m", required=True)
     ap.add_argument("--device", "-d", type=int, default=0)
     ap.add_argument("--no-reuse", action="store_true")
+    ap.add_argument("--expert-weights", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step)")
     a = ap.parse_args()
-    out = inference(a.task, a.input, a.model, a.ref_audio, a.ref_text, a.video, a.output, a.device, not a.no_reuse)
+    out = inference(a.task, a.input, a.model, a.ref_audio, a.ref_text, a.video, a.output, a.device, not a.no_reuse, a.expert_weights)
     sys.exit(0 if out else 1)
 
 

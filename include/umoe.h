@@ -47,6 +47,13 @@ int umoe_pack_weight(const uint16_t* W, int N, int K, uint16_t* packed, umoe_str
 /* gate_proj / up_proj of one SwiGLU expert interleaved per 16-row block (block 2i = gate i,
  * block 2i+1 = up i) so one wave produces silu(g)*u without a round trip.  N_packed = 2*I. */
 int umoe_pack_gate_up(const uint16_t* Wg, const uint16_t* Wu, int I, int K, uint16_t* packed, umoe_stream_t stream);
+/* FP8 expert weights ("WP8", the decode engine's opt-in weight-only fp8: umoe_engine_set_layer_fp8).  Elements are OCP float8_e4m3fn
+ * q[N][K], one power-of-two scale 2^e per output row (int8 e), so that q * 2^e is exact in bf16.  One 16-byte lane load carries TWO
+ * k-steps of the WP16 order:
+ *   packed[((nb*KB2 + i)*64 + lane)*16 + j] = q[nb*16 + (lane&15)][(lane>>4)*(K/4) + 16*i + j]
+ * with KB2 = ceil(KB/2), KB = K/32; bytes past the end of a K quarter (K/4 % 16 == 8, e.g. K = 1376) and padded rows are zero.
+ * Exponents: 16 per block, exps[nb*16 + r] (0 for padded rows).  Gate/up blocks are interleaved as in umoe_pack_gate_up.  Packed on
+ * the host side (unimoe_audio_amd/quant.py). */
 
 /* ------------------------------------------------------------------ router
  * Replaces utils/UniMoE_Audio_core.py:246-291,331-339 (gate GEMM, Top-P count :157-167,
@@ -670,6 +677,16 @@ typedef struct umoe_engine umoe_engine;
 int umoe_engine_create(const umoe_engine_cfg* cfg, umoe_engine** out);
 void umoe_engine_destroy(umoe_engine* e);
 int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer_weights* w);
+/* fp8 expert weights of one layer (after umoe_engine_set_layer): host arrays [n_real + n_fix] (routed experts, then shared) of device
+ * pointers to WP8 gate/up pairs, their exponents, WP8 down blocks and theirs.  An engine with fp8 weights runs every dense decode layer's
+ * experts through the fp8 flat launch and nothing else: a decode step it cannot run that way (UMOE_FLAT_MOE=0, UMOE_RIDER_PUB=0, too few
+ * compute units for a schedule) is refused before anything is enqueued; expert parallel engines (ep_size > 1) are refused here.
+ * umoe_engine_info(e, "expert_fp8") = 1 when the last dense decode layer ran the fp8 launch.  Prefill keeps the bf16 weights. */
+int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* gu8, const int8_t* const* gu_e, const uint8_t* const* dn8,
+                              const int8_t* const* dn_e);
+/* test hook: the fp8 launch's conversion path over a row-major e4m3 matrix q [N][K] (K % 8 == 0) with one exponent per row:
+ * out[r][k] = bf16 bits of q[r][k] * 2^e[r] */
+int umoe_fp8_convert_probe(const uint8_t* q, const int8_t* e, int N, int K, uint16_t* out, umoe_stream_t stream);
 /* final norm [D], codec embeddings [C][V][D], WP16 codec head [C*V][D], rope tables [max_pos][hd/2] */
 int umoe_engine_set_globals(umoe_engine* e, const uint16_t* final_norm, const uint16_t* codec_emb,
                             const uint16_t* codec_head_w, const uint16_t* cos_tab, const uint16_t* sin_tab, int max_pos,

@@ -28,7 +28,11 @@ AUDIO_START = "<|AUDIO_START|>"
 
 class UniMoEAudio:
     def __init__(self, model_path: Optional[str], device_id: int = 0, config: Optional[UniMoEAudioConfig] = None,
-                 model: Optional[UniAudioRVQQwen2_5VLMoEForConditionalGeneration] = None):
+                 model: Optional[UniAudioRVQQwen2_5VLMoEForConditionalGeneration] = None, expert_weights: str = "bf16"):
+        """expert_weights "fp8": weight-only fp8 (e4m3, one power-of-two scale per row) of the routed and shared experts
+        (model.quantize_experts_): decode streams half the expert bytes; the whole model then computes with the dequantized weights."""
+        if expert_weights not in ("bf16", "fp8"):
+            raise ValueError(f"expert_weights must be 'bf16' or 'fp8' (got {expert_weights!r})")
         if not torch.cuda.is_available():
             raise RuntimeError("UniMoEAudio needs a ROCm device: the accelerated path has no CPU fallback")
         torch.cuda.set_device(device_id)
@@ -46,6 +50,8 @@ class UniMoEAudio:
             self.model = UniAudioRVQQwen2_5VLMoEForConditionalGeneration(cfg)
             self._load_weights(model_path)
             self.model = self.model.to(self.device, torch.bfloat16).eval()
+        if expert_weights == "fp8":
+            self.model.quantize_experts_("fp8")
         self._tokenizer = None
         self._dac = None
 

@@ -249,6 +249,11 @@ int umoe_moe_fused(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t*
 int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s,
                   const umoe_gemm_args* oproj = nullptr, uint32_t* o_flags = nullptr);
 bool umoe_moe_flat_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
+// The same launch on WP8 (fp8 e4m3) expert weights: the groups' `w` are WP8 blocks (include/umoe.h), e_gu / e_dn [num_groups] their
+// per-row exponents in the same group order.  Returns 1 (nothing launched) like umoe_moe_flat; the caller has no other fp8 path.
+int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const int8_t* const* e_gu, const int8_t* const* e_dn, uint32_t* flags,
+                      int flag_words, int n_wg, hipStream_t s, const umoe_gemm_args* oproj = nullptr, uint32_t* o_flags = nullptr);
+bool umoe_moe_flat_fp8_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
 
 // A small decode GEMM with row riders in front (umoe_gemm.hip wstream_gemm_rk, umoe_riders_dev.h; decode engine only).  kind 2: the
 // MoE combine of the previous layer rides in the QKV launch; kind 4: the same over the return slab of the expert-parallel exchange.

@@ -22,6 +22,10 @@ struct LayerDev {
     std::vector<const uint16_t*> rm_eg, rm_eu, rm_ed, rm_sg, rm_su, rm_sd;   // row-major copies (tiled prefill path)
     bool has_rm = false;
     bool set = false;
+    // fp8 expert weights (umoe_engine_set_layer_fp8): WP8 blocks + per-row exponents, [n_real routed, then n_fix shared]
+    std::vector<const uint16_t*> f8_gu, f8_dn;       // (WP8 addresses in the groups' `w` slots)
+    std::vector<const int8_t*> f8e_gu, f8e_dn;
+    bool has_f8 = false;
 };
 
 struct Carver {
@@ -90,6 +94,9 @@ struct umoe_engine {
                                  // fewer microseconds than the ragged path's four extra launches -- 2.91 vs 3.33 ms/step
     int expert_launch = 0;       // what the last dense decode layer enqueued for its experts: 0 launch per GEMM, 1 box-grid fused, 2 flat, 3 the
                                  // one-launch expert-parallel MoE half (umoe_engine_info)
+    bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
+                                 // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
+    int expert_fp8 = 0;          // the last dense decode layer ran the fp8 flat launch (umoe_engine_info "expert_fp8")
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
     bool fuse_o = false;         // UMOE_FUSE_O=1: with the flat expert launch, o_proj + residual is computed INSIDE it (half a 16-feature tile per
                                  // workgroup, handed over by flags; the first expert weight stage is requested inside the half tile): four
@@ -394,6 +401,27 @@ extern "C" int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer
     }
     L.set = true;
     e->groups_for_tok = -1;
+    return 0;
+}
+
+extern "C" int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* gu8, const int8_t* const* gu_e, const uint8_t* const* dn8,
+                                         const int8_t* const* dn_e) {
+    UMOE_REQUIRE(e && gu8 && gu_e && dn8 && dn_e && layer >= 0 && layer < e->c.layers, "umoe_engine_set_layer_fp8: bad argument (layer %d)", layer);
+    UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer_fp8: fp8 expert weights run on the flat expert launch only, not expert parallel (ep_size %d)",
+                 e->c.ep_size);
+    LayerDev& L = e->layers[layer];
+    UMOE_REQUIRE(L.set, "umoe_engine_set_layer_fp8: umoe_engine_set_layer(%d) first", layer);
+    const int G = e->c.n_real + e->c.n_fix;
+    for (int i = 0; i < G; ++i)
+        UMOE_REQUIRE(gu8[i] && gu_e[i] && dn8[i] && dn_e[i], "umoe_engine_set_layer_fp8: layer %d group %d: null pointer", layer, i);
+    L.f8_gu.assign(G, nullptr); L.f8_dn.assign(G, nullptr);
+    for (int i = 0; i < G; ++i) {
+        L.f8_gu[i] = reinterpret_cast<const uint16_t*>(gu8[i]);
+        L.f8_dn[i] = reinterpret_cast<const uint16_t*>(dn8[i]);
+    }
+    L.f8e_gu.assign(gu_e, gu_e + G); L.f8e_dn.assign(dn_e, dn_e + G);
+    L.has_f8 = true;
+    e->fp8 = true;
     return 0;
 }
 
@@ -983,8 +1011,29 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             const char* fv = getenv("UMOE_FLAT_MOE");      // (read per enqueue: the step graph captures the choice; A/B scripts toggle it)
             const bool flat = fv ? atoi(fv) != 0 : e->flat_moe;
             const int n_wg = e->n_cu < 256 ? e->n_cu : 256;
+            if (e->fp8) {
+                // fp8 expert weights: the same launch on the WP8 blocks -- and nothing else (no bf16 path streams these weights)
+                UMOE_REQUIRE(flat && n_wg > 0 && L.has_f8 && G <= UMOE_MAXE, "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
+                umoe_group_t g8u[UMOE_MAXE], g8d[UMOE_MAXE];
+                const int8_t* e8u[UMOE_MAXE];
+                const int8_t* e8d[UMOE_MAXE];
+                for (int i = 0; i < G; ++i) {
+                    const int x = i < c.n_fix ? c.n_real + i : i - c.n_fix;     // gu groups: the shared experts first (h_gu_pub)
+                    g8u[i] = gu.groups_host[i]; g8u[i].w = L.f8_gu[x]; e8u[i] = L.f8e_gu[x];
+                    g8d[i] = dn.groups_host[i]; g8d[i].w = L.f8_dn[i]; e8d[i] = L.f8e_dn[i];
+                }
+                umoe_gemm_args gu8 = gu, dn8 = dn;
+                gu8.groups_host = g8u; dn8.groups_host = g8d;
+                rc = umoe_moe_flat_fp8(&gu8, &dn8, e8u, e8d, e->ep_words + 64, 512 - 64, n_wg, s, o_in_flat ? &o : nullptr, e->ep_words + 2688);
+                UMOE_REQUIRE(rc != 1, "umoe_engine: the fp8 flat expert launch has no schedule for this shape on %d workgroups (layer %d)", n_wg, l);
+                if (rc) return rc;
+                e->expert_launch = 2;
+                e->expert_fp8 = 1;
+            } else {
             if (flat && n_wg > 0) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s, o_in_flat ? &o : nullptr, e->ep_words + 2688);
             e->expert_launch = rc == 0 ? 2 : 0;
+            e->expert_fp8 = 0;
+            }
             if (rc == 1 && o_in_flat) {      // the flat launch refused after all: o_proj as its own launch in front of whatever runs instead
                 if ((rc = umoe_grouped_gemm(&o, s))) return rc;
                 rc = 1;
@@ -1079,6 +1128,8 @@ static int prefill_state(umoe_engine* e, const uint8_t* valid_host, int T, const
     return 0;
 }
 
+static int fp8_step_check(umoe_engine* e);
+
 extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const uint8_t* valid_host, int T, const int32_t* pos3_host,
                                        const int32_t* next_pos_host, umoe_stream_t stream) {
     UMOE_REQUIRE(e && x && valid_host && T > 0, "umoe_engine_prefill: bad argument");
@@ -1093,6 +1144,8 @@ extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const 
     hipStream_t s = (hipStream_t)stream;
     const int n_tok = c.rows * T;
     int rc;
+    // a one-token prompt takes the dense decode layout, i.e. the fp8 flat launch on an fp8 engine: refused up front like a decode step
+    if (e->fp8 && dense_mode(e, n_tok) && (rc = fp8_step_check(e))) return rc;
     if ((rc = ensure_workspace(e, n_tok))) return rc;
     if ((rc = build_groups(e, n_tok, s))) return rc;
     if ((rc = prefill_state(e, valid_host, T, pos3_host, next_pos_host, s))) return rc;
@@ -1200,9 +1253,32 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     return rc;
 }
 
+// An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch: the box grid and the
+// launch-per-GEMM paths would stream bf16 expert weights it does not run on.  Checked on the host before anything is enqueued.
+static int fp8_step_check(umoe_engine* e) {
+    if (!e->fp8) return 0;
+    const umoe_engine_cfg& c = e->c;
+    const char* fv = getenv("UMOE_FLAT_MOE");
+    const bool flat = fv ? atoi(fv) != 0 : e->flat_moe;
+    UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: fp8 expert weights are not supported expert parallel (ep_size %d)", c.ep_size);
+    UMOE_REQUIRE(flat, "umoe_engine: fp8 expert weights need the flat expert launch (UMOE_FLAT_MOE=0 selects a bf16 path)");
+    UMOE_REQUIRE(e->rider_pub && e->fuse_router && e->fuse_moe,
+                 "umoe_engine: fp8 expert weights need the flat expert launch with published riders (UMOE_RIDER_PUB / UMOE_FUSE_ROUTER / UMOE_FUSE_MOE = 0 select a bf16 path)");
+    UMOE_REQUIRE(dense_mode(e, c.rows) && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096),
+                 "umoe_engine: fp8 expert weights need the dense decode layout of the flat expert launch (rows %d)", c.rows);
+    const int n_wg = e->n_cu < 256 ? e->n_cu : 256;
+    UMOE_REQUIRE(n_wg > 0 && umoe_moe_flat_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix) &&
+                     umoe_moe_flat_fp8_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix),
+                 "umoe_engine: fp8 expert weights: the flat expert launch has no schedule on %d compute units", e->n_cu);
+    for (int l = 0; l < c.layers; ++l)
+        UMOE_REQUIRE(e->layers[l].has_f8, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
+    return 0;
+}
+
 extern "C" int umoe_engine_decode_step(umoe_engine* e, const umoe_decode_io* io, umoe_stream_t stream) {
     UMOE_REQUIRE(e && io && io->tokens && io->state, "umoe_engine_decode_step: null argument");
     UMOE_REQUIRE(e->T_prompt > 0, "umoe_engine_decode_step: prefill first");
+    if (int rc = fp8_step_check(e)) return rc;
     return enqueue_step(e, io, (hipStream_t)stream);
 }
 
@@ -1212,6 +1288,7 @@ extern "C" int umoe_engine_profile_step(umoe_engine* e, const umoe_decode_io* io
                                         int* launches, int n) {
     UMOE_REQUIRE(e && io && ms && launches && n >= K_NUM, "umoe_engine_profile_step: need %d output slots", K_NUM);
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = fp8_step_check(e)) return rc;
     e->prof = true;
     e->ev_used = 0;
     const int rc = enqueue_step(e, io, s);
@@ -1233,6 +1310,7 @@ extern "C" int umoe_engine_capture(umoe_engine* e, const umoe_decode_io* io, umo
     UMOE_REQUIRE(e && io && io->tokens && io->state, "umoe_engine_capture: null argument");
     UMOE_REQUIRE(e->T_prompt > 0, "umoe_engine_capture: prefill first");
     UMOE_REQUIRE(!e->probe_on(), "umoe_engine_capture: the per-layer probe works on eager steps only (umoe_engine_set_probe)");
+    if (int rc = fp8_step_check(e)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (e->exec) { (void)hipGraphExecDestroy(e->exec); e->exec = nullptr; }
     if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
@@ -1256,6 +1334,7 @@ extern "C" int umoe_engine_replay(umoe_engine* e, umoe_stream_t stream) {
 extern "C" int umoe_engine_info(umoe_engine* e, const char* key) {
     if (!e || !key) return -1;
     if (!strcmp(key, "expert_launch")) return e->expert_launch;
+    if (!strcmp(key, "expert_fp8")) return e->expert_fp8;
     if (!strcmp(key, "n_cu")) return e->n_cu;
     return -1;
 }

@@ -5,6 +5,8 @@
 #include "umoe_common.h"
 #include "umoe_router_dev.h"
 
+#include <type_traits>
+
 #define FLAT_MAXG UMOE_GROUPS_INLINE
 #define FLAT_MAXWG 256
 #define FLAT_NP_MIN 4
@@ -75,6 +77,22 @@ struct flat_stamps {};
 
 typedef uint32_t flat_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t flat_u32x2 __attribute__((ext_vector_type(2)));
+
+// ---- FP8 expert weights (moe_flat_fp8_kernel): WP8 blocks (include/umoe.h) -- one 16-byte lane load carries TWO k-steps of OCP e4m3 --
+// and one power-of-two exponent per output row.  The conversion v_cvt_scalef32_pk_bf16_fp8 with the scale 2^e yields exactly the bf16 bits
+// of q * 2^e, so the MFMAs below see the operands of the bf16 kernel run on the dequantized weights: same tiles, K split, MFMA order.
+struct flat_f8 {                        // a kernel argument of its own (flat_args stays as it is)
+    const int8_t* e_gu[FLAT_MAXG];      // exponents of the gate/up blocks, 16 per block, blocks interleaved like the weights
+    const int8_t* e_dn[FLAT_MAXG];      // exponents of the down blocks
+};
+typedef __bf16 flat_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float flat_f8_scale(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }     // 2^e, |e| <= 126
+// 8 e4m3 values (one k-step of a lane) -> one MFMA operand
+__device__ __forceinline__ bf16x8_t flat_f8_frag(uint32_t lo, uint32_t hi, float sc) {
+    const flat_bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, true);
+    const flat_bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, true);
+    return bf16x8_t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
 
 // ---- gate/up SwiGLU slice: NP pairs of the flat list starting at fp0 (arithmetic of wstream_body<14, 1, PLAIN, SWIGLU, 8> per tile) ----
 // The workgroup normalises the 16 rows ITSELF while it stages them (post-attention RMSNorm, model.py:240): the raw rows exist when the
@@ -235,14 +253,17 @@ __device__ __forceinline__ void flat_oproj_wait(const flat_o O, const umoe_rider
 // half tile, the hand-off and the wait sit between this slice's first weight request and its row loads; 2: made inside the launch, half tile
 // and wait already done by the caller (the router riders).  ONE instantiation per NP serves all three: a second set of instantiations made
 // hipcc copy the whole 2.7 KB kernel-argument block into scratch (private_segment_fixed_size 36 -> 2736).
-template <int NP, bool PUBLISH = true>
+// F8: WP8 weights (w_gu holds WP8 addresses, F their exponents): one 16-byte chunk = two k-steps; every chunk index below counts chunks.
+template <int NP, bool PUBLISH = true, bool F8 = false>
 __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider_pub& pub, const int fp0, const unsigned b, char* smem, flat_stamps& st,
-                                            const int tid_in, const int oph = 0, const flat_o O = flat_o{}) {      // tid_in = threadIdx.x (a caller that loops over slices passes an opaque copy: see umoe_moe_ep.hip)
+                                            const int tid_in, const int oph = 0, const flat_o O = flat_o{}, const flat_f8* F = nullptr) {      // tid_in = threadIdx.x (a caller that loops over slices passes an opaque copy: see umoe_moe_ep.hip)
     constexpr int NT = 2 * NP, WV = 8, KB = 64;
     const int tid = tid_in, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: every guard around an MFMA is a scalar branch
     constexpr int QS = (KB * 16 + 255) & ~255, RS = QS * 4;
     const int i0 = __builtin_amdgcn_readfirstlane((KB * wave) / WV), i1 = __builtin_amdgcn_readfirstlane((KB * (wave + 1)) / WV);
+    constexpr int CS = F8 ? 2 : 1;                   // k-steps per 16-byte chunk (a wave's 8 steps are whole chunks either way)
+    const int c0 = i0 / CS, c1 = i1 / CS;
     // the slice straddles at most two groups (a group has far more than 7 pairs).  Every table read is a kernel-argument read with a
     // compile-time offset + a scalar select: ONE batch of scalar loads in front of the first request, no dependent second one
     int g0 = 0;
@@ -253,17 +274,32 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
     const int g1 = min(g0 + 1, A.G - 1);      // pairs >= cut belong to group g1
     f32x4_t acc[NT];
     const flat_u32x4* wp[NT];
+    [[maybe_unused]] const int8_t* ep[F8 ? NT : 1];
+    [[maybe_unused]] int ev[F8 ? NT : 1];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const int pp = fp0 + (t >> 1);
         const bool second = pp >= cut;
         const int lp = pp - (second ? cut : p0);
-        wp[t] = reinterpret_cast<const flat_u32x4*>(second ? wg1 : wg0) + ((size_t)(2 * lp + (t & 1)) * KB) * 64 + lane;
+        if constexpr (F8) {
+            const int blk = 2 * lp + (t & 1);
+            wp[t] = reinterpret_cast<const flat_u32x4*>(second ? wg1 : wg0) + ((size_t)blk * (KB / 2)) * 64 + lane;
+            ep[t] = (second ? F->e_gu[g0 + 1 < FLAT_MAXG ? g0 + 1 : g0] : F->e_gu[g0]) + blk * 16 + (lane & 15);
+        } else {
+            wp[t] = reinterpret_cast<const flat_u32x4*>(second ? wg1 : wg0) + ((size_t)(2 * lp + (t & 1)) * KB) * 64 + lane;
+        }
     }
+    // the row scales: requested behind the first weight chunk (never a round trip in front of it), needed at its first MFMA
+    auto load_scales = [&]() {
+        if constexpr (F8) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) ev[t] = *ep[t];
+        }
+    };
     flat_u32x4 w0[NT], w1[NT];
     auto load_chunk = [&](flat_u32x4 (&dst)[NT], int ii) {
-        const int ic = min(ii, i1 - 1);
+        const int ic = min(ii, c1 - 1);
 #pragma unroll
         for (int t = 0; t < NT; ++t) dst[t] = __builtin_nontemporal_load(wp[t] + (size_t)ic * 64);
     };
@@ -323,10 +359,10 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
             // oph 1: the first register stage is requested inside the half tile (flat_oproj_half); oph 2 (router riders: half tile and
             // wait done by the caller): here
             if (oph == 1) {
-                flat_oproj_half<NT, true>(O, pub, b, smem, tid, wp, w0, min(i0, i1 - 1));
+                flat_oproj_half<NT, true>(O, pub, b, smem, tid, wp, w0, min(c0, c1 - 1));
                 flat_oproj_wait(O, pub, b, tid);
             } else {
-                load_chunk(w0, i0);
+                load_chunk(w0, c0);
             }
             uint4 buf[8];
             const auto rrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A.a), 0, A.S * A.lda * 2, 0x00020000);
@@ -336,6 +372,7 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
                 buf[n] = make_uint4(t4[0], t4[1], t4[2], t4[3]);
             }
             const uint4 nw1 = ld16(A.norm_w + (tid & (4 * KB - 1)) * 8);
+            load_scales();
             FSTAMP(1);
             norm_stage(buf, nw1);
         } else {
@@ -349,7 +386,8 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
             //  second stage's 14 requests per wave only delayed the point where the rows are staged -- 8.6 -> 12.1 us -- and bought nothing:
             //  3.020 vs 3.015 ms/step.  The launch runs at the CU's request rate from its first request on.)
             __builtin_amdgcn_sched_barrier(0);
-            load_chunk(w0, i0);
+            load_chunk(w0, c0);
+            load_scales();
             __builtin_amdgcn_sched_barrier(0);
             FSTAMP(1);
             norm_stage(buf, nw1);
@@ -361,18 +399,30 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
     const int h = lane >> 4, mm = lane & 15;
     const char* bbase = smem + mm * RS;
     auto compute_chunk = [&](const flat_u32x4 (&src)[NT], int ii) {
-        if (ii < i1) {
-            const uint4 bv = *reinterpret_cast<const uint4*>(bbase + flat_lds_chunk_off(QS, h, ii, mm));
-            const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, bv);
+        if (ii < c1) {
+            if constexpr (F8) {
+                // k-steps 2 ii and 2 ii + 1: every tile's MFMA of the first step, then of the second (the bf16 kernel's order per tile)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, src[t]), bfrag, acc[t], 0, 0, 0);
+                for (int k = 0; k < 2; ++k) {
+                    const uint4 bv = *reinterpret_cast<const uint4*>(bbase + flat_lds_chunk_off(QS, h, 2 * ii + k, mm));
+                    const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, bv);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(flat_f8_frag(src[t][2 * k], src[t][2 * k + 1], flat_f8_scale(ev[t])), bfrag, acc[t], 0, 0, 0);
+                }
+            } else {
+                const uint4 bv = *reinterpret_cast<const uint4*>(bbase + flat_lds_chunk_off(QS, h, ii, mm));
+                const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, bv);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, src[t]), bfrag, acc[t], 0, 0, 0);
+            }
         }
     };
-    for (int i = i0; i < i1; i += 2) {
-        if (i + 1 < i1) load_chunk(w1, i + 1);
+    for (int i = c0; i < c1; i += 2) {
+        if (i + 1 < c1) load_chunk(w1, i + 1);
         compute_chunk(w0, i);
-        if (i + 2 < i1) load_chunk(w0, i + 2);
-        if (i + 1 < i1) compute_chunk(w1, i + 1);
+        if (i + 2 < c1) load_chunk(w0, i + 2);
+        if (i + 1 < c1) compute_chunk(w1, i + 1);
     }
     // ---- fixed-order cross-wave reduction through the (now free) staging area ----
     FSTAMP(4);
@@ -424,9 +474,12 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
 // ---- down-projection slice: blocks [nb0, nb0 + ND) of group grp (arithmetic of wstream_body<6, 2, PLAIN, BF16, 8> per tile) ----
 // U = 2 for an even number of k-steps (whole 2-step chunks per wave), U = 1 for an odd one: the K split of the 2-step launch does not
 // depend on U then, and a 1-step stream has no clamped duplicate step at the end of a wave's slice.
-template <int ND, int U>
+// F8: WP8 weights (w_dn holds WP8 addresses, F their exponents).  U = 2: one 16-byte load per lane carries the chunk's two k-steps;
+// U = 1 (an odd number of k-steps per K quarter: a wave's slice starts or ends on either half of a 16-byte chunk): one 8-byte load per
+// k-step.  Either way exactly the bf16 kernel's MFMAs -- no padded step is computed.
+template <int ND, int U, bool F8 = false>
 __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_pub& pub, const int grp, const int nb0, char* smem, flat_stamps& st,
-                                          const int sb, const int tid_in) {
+                                          const int sb, const int tid_in, const flat_f8* F = nullptr) {
     constexpr int NT = ND, WV = 8;
     const int tid = tid_in, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -444,22 +497,44 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
     i0 = __builtin_amdgcn_readfirstlane(i0);
     i1 = __builtin_amdgcn_readfirstlane(i1);
     f32x4_t acc[NT];
-    const flat_u32x4* wp[NT];
+    // (F8: a register stage holds U k-steps of e4m3 -- 8 bytes per step -- in ONE load: x4 for U = 2, x2 for U = 1)
+    using FW = std::conditional_t<U == 2, flat_u32x4, flat_u32x2>;
+    constexpr int UL = F8 ? 1 : U;                   // loads per register stage and tile
+    using WT = std::conditional_t<F8, FW, flat_u32x4>;
+    const WT* wp[NT];
+    [[maybe_unused]] int ev[F8 ? NT : 1];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        wp[t] = reinterpret_cast<const flat_u32x4*>(A.w_dn[grp]) + ((size_t)(nb0 + t) * KB) * 64 + lane;
+        if constexpr (F8) {
+            const int KB2 = (KB + 1) >> 1;           // 16-byte chunks per K quarter (the last one half used when KB is odd)
+            wp[t] = reinterpret_cast<const WT*>(reinterpret_cast<const flat_u32x4*>(A.w_dn[grp]) + ((size_t)(nb0 + t) * KB2) * 64 + lane);
+        } else {
+            wp[t] = reinterpret_cast<const flat_u32x4*>(A.w_dn[grp]) + ((size_t)(nb0 + t) * KB) * 64 + lane;
+        }
     }
-    flat_u32x4 w0[NT][U], w1[NT][U];
-    auto load_chunk = [&](flat_u32x4 (&dst)[NT][U], int ibase) {
+    WT w0[NT][UL], w1[NT][UL];
+    auto load_chunk = [&](WT (&dst)[NT][UL], int ibase) {
+        if constexpr (F8) {
+            const int ii = min(ibase, i1 - U);       // (U = 2: ibase and i1 even -- the stage is the whole chunk ii / 2)
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int ii = min(ibase + u, i1 - 1);
+            for (int t = 0; t < NT; ++t)
+                dst[t][0] = __builtin_nontemporal_load(U == 2 ? wp[t] + (size_t)(ii >> 1) * 64 : wp[t] + (size_t)(ii >> 1) * 128 + (ii & 1));
+        } else {
 #pragma unroll
-            for (int t = 0; t < NT; ++t) dst[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)ii * 64);
+            for (int u = 0; u < U; ++u) {
+                const int ii = min(ibase + u, i1 - 1);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) dst[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)ii * 64);
+            }
         }
     };
     if (i0 < i1) load_chunk(w0, i0);
+    if constexpr (F8) {      // the row scales behind the first weight stage
+        const int8_t* e = F->e_dn[grp] + nb0 * 16 + (lane & 15);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) ev[t] = e[t * 16];
+    }
     const int count = A.S;
     // wait for the workgroups of THIS launch that produced this group's rows: lane i of wave 0 polls producer i (bounded)
     if (tid < A.prod_n[grp]) flat_wait(A.flags + A.prod_base[grp] + tid, flat_epoch(pub), pub.err, 3u);
@@ -496,7 +571,7 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
     FSTAMP(sb + 1);
     const int h = lane >> 4, mm = lane & 15;
     const char* bbase = smem + mm * RS;
-    auto compute_chunk = [&](const flat_u32x4 (&src)[NT][U], int ibase) {
+    auto compute_chunk = [&](const WT (&src)[NT][UL], int ibase) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ii = ibase + u;
@@ -504,8 +579,12 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
                 const uint4 bv = *reinterpret_cast<const uint4*>(bbase + flat_lds_chunk_off(QS, h, ii, mm));
                 const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, bv);
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, src[t][u]), bfrag, acc[t], 0, 0, 0);
+                for (int t = 0; t < NT; ++t) {
+                    if constexpr (F8)
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(flat_f8_frag(src[t][0][2 * u], src[t][0][2 * u + 1], flat_f8_scale(ev[t])), bfrag, acc[t], 0, 0, 0);
+                    else
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, src[t][u]), bfrag, acc[t], 0, 0, 0);
+                }
             }
         }
     };

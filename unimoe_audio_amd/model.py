@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import ops
+from . import ops, quant
 from .codec_utils import DecoderOutput
 from .config import UniMoEAudioConfig
 from .dcmoe import UniMoEAudioSparseMoeBlock
@@ -353,17 +353,26 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
     def _pack_key(self):
         return tuple((p.data_ptr(), p._version) for n, p in self.named_parameters() if not n.startswith("visual."))
 
-    def engine(self, batch: int, max_prompt: int, max_tokens: int, attn_splits: int = 8, ep=None) -> "DecodeEngine":
+    def engine(self, batch: int, max_prompt: int, max_tokens: int, attn_splits: int = 8, ep=None,
+               expert_weights: Optional[str] = None) -> "DecodeEngine":
         """The decode engine for this shape, rebuilt when the shape, the weights (data pointer / version of any parameter) or the
-        expert-parallel link changed.  `ep`: an unimoe_audio_amd.ep.EpLink (every rank of the link calls this together)."""
+        expert-parallel link changed.  `ep`: an unimoe_audio_amd.ep.EpLink (every rank of the link calls this together).
+        `expert_weights` "bf16" / "fp8" (None: "fp8" when quantize_experts_('fp8') ran on this model, else "bf16")."""
         need_L = max_prompt + max_tokens + 8
         e = self._engine
         key = self._pack_key()
-        if e is None or e.batch != batch or e.Lmax < need_L or e.Tmax < max_tokens + 64 or e.pack_key != key or e.ep is not ep:
+        fmt = expert_weights or ("fp8" if quant.is_quantized(self) else "bf16")
+        if (e is None or e.batch != batch or e.Lmax < need_L or e.Tmax < max_tokens + 64 or e.pack_key != key or e.ep is not ep
+                or e.expert_weights != fmt):
             if e is not None:
                 e.close()
-            self._engine = DecodeEngine(self, batch, Lmax=need_L, Tmax=max_tokens + 64, attn_splits=attn_splits, ep=ep)
+            self._engine = DecodeEngine(self, batch, Lmax=need_L, Tmax=max_tokens + 64, attn_splits=attn_splits, ep=ep, expert_weights=fmt)
         return self._engine
+
+    def quantize_experts_(self, fmt: str = "fp8"):
+        """Weight-only fp8 of the routed and shared experts (unimoe_audio_amd/quant.py): the parameters become their dequantized
+        values W_deq in place; decode engines built afterwards stream the e4m3 copies (half the expert bytes)."""
+        return quant.quantize_experts_(self, fmt)
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, dec_output: DecoderOutput, max_tokens, min_tokens=None,
@@ -371,7 +380,8 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
                  image_grid_thw=None, video_grid_thw=None, second_per_grid_ts=None, cfg_scale: float = 3.0,
                  temperature: float = 1.2, top_p: float = 0.95, cfg_filter_top_k: int = 45,
                  eos_prob_mul_factor: float = 0.8, do_sample: bool = True, debug_guidance_step: int = 0, use_cache=True,
-                 seed: int = 0, use_graph: bool = True, poll_every: int = 16, vision_in_generate: bool = False):
+                 seed: int = 0, use_graph: bool = True, poll_every: int = 16, vision_in_generate: bool = False,
+                 expert_weights: Optional[str] = None):
         """reference generate(), utils/UniMoE_Audio_model.py:1070-1231 (same arguments, same return).
         vision_in_generate (not in the reference).  The reference's generate() accepts pixel_values(_videos) but never uses them: it builds
         inputs_embeds with calculate_input_embedding only (model.py:1116: the <|video_pad|> / <|image_pad|> tokens keep their TEXT
@@ -380,14 +390,15 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         yields the tokens the reference's inference path yields; True runs what the reference's forward() does for training
         (model.py:708-790): vision tower, embeddings scattered over the pad tokens, 3-D mRoPE positions from get_rope_index.
         use_cache=False: the reference recomputes the whole prefix every step without a cache (model.py:964-980) and allows it only
-        without a codec prompt (:1092-1093); the result is the same tokens, so the engine serves it from its KV cache."""
+        without a codec prompt (:1092-1093); the result is the same tokens, so the engine serves it from its KV cache.
+        expert_weights (not in the reference): "bf16" / "fp8" expert weights of the decode engine (None: fp8 after quantize_experts_)."""
         if not use_cache and codec_input_ids is not None:
             raise AssertionError("use_cache=False with a codec prompt: the reference asserts use_cache here (model.py:1092-1093)")
         dev = self.device
         input_ids, attention_mask = input_ids.to(dev), attention_mask.to(dev)
         B = input_ids.shape[0] // 2
         T = input_ids.shape[1]
-        eng = self.engine(B, T, int(max_tokens))
+        eng = self.engine(B, T, int(max_tokens), expert_weights=expert_weights)
         pos3 = deltas = None
         if vision_in_generate and (pixel_values is not None or pixel_values_videos is not None):
             x = self.multimodal_embedding(input_ids, None if codec_input_ids is None else codec_input_ids.to(dev), pixel_values, image_grid_thw,
@@ -432,8 +443,16 @@ class DecodeEngine:
     """Python face of umoe_engine_*: packs the weights once, owns the C engine and the decode state."""
 
     def __init__(self, model: UniAudioRVQQwen2_5VLMoEForConditionalGeneration, batch: int, Lmax: int, Tmax: int,
-                 attn_splits: int = 8, max_pos: Optional[int] = None, ep=None, ep_connect: bool = True):
+                 attn_splits: int = 8, max_pos: Optional[int] = None, ep=None, ep_connect: bool = True, expert_weights: Optional[str] = None):
         cfg = model.config
+        fmt = expert_weights or ("fp8" if quant.is_quantized(model) else "bf16")
+        if fmt not in ("bf16", "fp8"):
+            raise L.UmoeError(f"expert_weights must be 'bf16' or 'fp8' (got {fmt!r})")
+        if fmt == "fp8":
+            if ep is not None and ep.size > 1:
+                raise L.UmoeError("fp8 expert weights run on the flat expert launch only: not with expert parallel decode")
+            quant.check_quantized(model)      # refuses stale fp8 copies (a weight edited after quantize_experts_)
+        self.expert_weights = fmt
         dev = model.device
         if dev.type != "cuda":
             raise L.UmoeError("DecodeEngine needs the model on a ROCm device; there is no CPU path in the product")
@@ -511,6 +530,8 @@ class DecodeEngine:
                                rm_qkv=lp["qkv_rm"].data_ptr(), rm_o=layer.self_attn.o_proj.weight.data_ptr(),
                                rm_exp_gate=reg, rm_exp_up=reu, rm_exp_down=red, rm_sh_gate=rsg, rm_sh_up=rsu, rm_sh_down=rsd)
             L.check(lib.umoe_engine_set_layer(self.h, li, C.byref(w)), "umoe_engine_set_layer")
+            if self.expert_weights == "fp8":
+                self._set_layer_fp8(li, ex, sh)
         emb, head = mpk["emb"], mpk["head"]
         # (slack: the temporal stream of a video advances by seconds-per-grid * tokens_per_second per frame pair, model.py:597-603)
         max_pos = self.Lmax + 4104 if max_pos_override is None else int(max_pos_override)
@@ -521,6 +542,19 @@ class DecodeEngine:
         L.check(lib.umoe_engine_set_globals(self.h, m.language_model.norm.weight.data_ptr(), emb.data_ptr(), head.data_ptr(),
                                             cos.data_ptr(), sin.data_ptr(), max_pos, delay), "umoe_engine_set_globals")
         torch.cuda.synchronize()
+
+    def _set_layer_fp8(self, li, ex, sh):
+        """WP8 blocks + exponents of one layer's experts (routed, then shared) from the (q, e) quantize_experts_ kept."""
+        gu8, gue, dn8, dne = [], [], [], []
+        for m_ in list(ex) + list(sh):
+            st = m_._fp8          # (packed once by quantize_experts_; moved only if the model moved after it)
+            for k in ("gu", "dn"):
+                if st[k][0].device != self.dev:
+                    st[k] = (st[k][0].to(self.dev), st[k][1].to(self.dev))
+            gu8.append(self._k(st["gu"][0])), gue.append(self._k(st["gu"][1]))
+            dn8.append(self._k(st["dn"][0])), dne.append(self._k(st["dn"][1]))
+        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        L.check(L.lib().umoe_engine_set_layer_fp8(self.h, li, arr(gu8), arr(gue), arr(dn8), arr(dne)), "umoe_engine_set_layer_fp8")
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -706,7 +740,8 @@ class DecodeEngine:
         return out
 
     def info(self, key: str) -> int:
-        """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 1 box-grid fused, 2 flat), "n_cu"."""
+        """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 1 box-grid fused, 2 flat), "n_cu",
+        "expert_fp8" (1: the last dense decode layer ran the fp8 flat launch)."""
         return int(L.lib().umoe_engine_info(self.h, key.encode()))
 
     def write_buffer(self, name: str, src: torch.Tensor, offset_bytes: int = 0) -> None:
