@@ -1,7 +1,7 @@
 """Headline benchmark: audio-tokens/s of the TTS decode loop (BASELINE.json configs[1]).
 
-  python bench.py --gpus 1 --steps K --warmup W
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full]
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" = one decode step of the whole batch: 36 x (RMSNorm, QKV, mRoPE, KV-cached GQA attention, o_proj, RMSNorm,
 Top-P router, ragged dispatch, grouped SwiGLU experts + shared experts, combine) + codec head + CFG + top-k/top-p
@@ -9,8 +9,11 @@ sampling + EOS/delay bookkeeping, for batch 8 = 16 CFG rows, on synthetic N(0, 0
 utils/config.json architecture.  One audio token = one generated frame of one sequence (12 codebook ids).
 Inputs (weights, prompt KV cache) are resident in HBM when the timed region starts; prefill is reported separately.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: grouped gate/up SwiGLU GEMM, HBM-bound) and
-`cpu_baseline` (the CPU oracle timed on the host cores, a bounded sample of the same workload).
+Prints ONE JSON line (rank 0).  A plain run only sets up, warms up, times the K steps, writes --dump-outputs and prints the headline
+line.  `--full` adds everything else, each measured by a run of its own after the timed steps: `roofline` (dominant kernel: grouped
+gate/up SwiGLU GEMM, HBM-bound) and `kernel_ms_per_step` (an eager profiling pass), `config1` / `config3` / `config5` (the other
+BASELINE configs), `cpu_baseline` (the CPU oracle timed on the host cores, a bounded sample of the same workload) and, with
+`--parallel ep`, the replica leg beside the expert-parallel one.
 """
 from __future__ import annotations
 
@@ -49,12 +52,16 @@ def parse():
                     help="single GPU only: time ONE rank of an N-rank expert-parallel job in loopback (no peers; a kernel-time proxy, "
                          "reported as a secondary field, never as `value`)")
     ap.add_argument("--ep-trial", default="", help=argparse.SUPPRESS)      # internal: the sandboxed rehearsal of an exchange backend (see main)
-    ap.add_argument("--no-replica-check", action="store_true", help="N > 1, ep: skip the replica leg (secondary number + bit check)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline and per-kernel times (an eager pass after the "
+                         "timed steps), the configs[0] / [2] / [4] legs, the CPU baseline, and with --parallel ep the replica leg")
+    ap.add_argument("--no-replica-check", action="store_true", help="N > 1: skip the replica leg (secondary number + bit check; "
+                                                                    "--parallel ep runs it with --full only)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-config1", action="store_true", help="skip the BASELINE configs[0] (single prompt) legs")
-    ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE configs[2] leg (one training step, scripts/train_bench.py as a child process)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE configs[4] leg (video_text_to_music, scripts/video_bench.py as a child process)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-config1", action="store_true", help="--full: skip the BASELINE configs[0] (single prompt) legs")
+    ap.add_argument("--no-config3", action="store_true", help="--full: skip the BASELINE configs[2] leg (one training step, scripts/train_bench.py as a child process)")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the BASELINE configs[4] leg (video_text_to_music, scripts/video_bench.py as a child process)")
     ap.add_argument("--cpu-steps", type=int, default=7, help="timed CPU-oracle decode steps (median; two warm-up steps before them)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (codec logits of every CFG row, the codes "
@@ -519,7 +526,7 @@ def main():
                 ok, why = 0, repr(e)
             ok_all = -max_over_ranks(-float(ok))
             if ok_all >= 1.0:
-                ep_info = decode_leg(model, cfg, args, device, rank, B, ep=link, outputs=bool(args.dump_outputs))
+                ep_info = decode_leg(model, cfg, args, device, rank, B, ep=link, profile=args.full, outputs=bool(args.dump_outputs))
                 ep_info["backend"] = be
                 if max_over_ranks(float(ep_info["ep_error"])) == 0.0:
                     break
@@ -532,8 +539,9 @@ def main():
             mode = "replica"
             notes["ep"] = "no expert-parallel backend worked on this node: `value` is the replica number"
     rep_info = None
-    if mode != "ep" or not args.no_replica_check:
-        rep_info = decode_leg(model, cfg, args, device, rank, B, outputs=bool(args.dump_outputs))
+    if mode != "ep" or (not args.no_replica_check and (args.parallel == "auto" or args.full)):
+        # (auto: the replica number may become `value`; --parallel ep: it is a secondary number + bit check)
+        rep_info = decode_leg(model, cfg, args, device, rank, B, profile=args.full, outputs=bool(args.dump_outputs))
     if mode == "ep" and rep_info is not None:
         # both layouts were timed with the same K steps and give the same tokens (checked below): `auto` reports the faster one as `value`
         # and names the other in config; --parallel ep keeps the expert-parallel number whatever the replicas do
@@ -573,9 +581,10 @@ def main():
                        "parallelism": {"single": "single", "ep": f"ep{world}", "replica": f"replica{world}"}[mode],
                        "graph": not args.no_graph, "codes_per_s": round(value * cfg.codec_channels, 1),
                        "prefill_s": round(info["t_prefill"], 3), "mean_top_k": round(info["mean_top_k"], 2)},
-            "roofline": roofline(cfg, info_dt, args, ep),
-            "kernel_ms_per_step": {k: round(v[0] * v[1], 4) for k, v in info["prof"].items()},
         }
+        if args.full:
+            out["roofline"] = roofline(cfg, info_dt, args, ep)
+            out["kernel_ms_per_step"] = {k: round(v[0] * v[1], 4) for k, v in info["prof"].items()}
         if world > 1:
             out["config"]["rccl_ranks"] = rccl_ranks
             out["config"]["ranks_share_gpus"] = shared_gpu
@@ -594,7 +603,7 @@ def main():
                                             if k in ("kernel", "achieved", "frac", "bytes_per_launch", "avg_launch_us", "step_bytes", "step_achieved", "step_frac")},
                                "note": "ONE rank of an expert-parallel job in loopback on one GPU (its own rows stand in for the "
                                        "peers'): kernel time of the sharded step without xGMI latency; not the model's outputs"}
-    if world == 1 and not args.no_config1:
+    if world == 1 and args.full and not args.no_config1:
         # BASELINE configs[0]: the reference's own CPU-runnable case, one prompt (2 CFG rows: ragged dispatch path), GPU side
         try:
             c1 = decode_leg(model, cfg, args, device, 0, 1, profile=False, steps=min(K, 200), warmup=W)
@@ -605,14 +614,14 @@ def main():
             out["config1"] = {"error": repr(e)}
     del model
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.layers and not args.codec_channels:
+    if rank == 0 and world == 1 and args.full and not args.layers and not args.codec_channels:
         # BASELINE configs[2] and configs[4] at their own shapes on this GPU (secondary keys; `value` stays configs[1])
         if not args.no_config3:
             out["config3"] = child_leg("train_bench.py", [], {"TB_STEPS": "4", "TB_NOCACHE_STEPS": "2"})
         if not args.no_config5:
             out["config5"] = child_leg("video_bench.py", ["--steps", "100", "--warmup", "5"])
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args)
                 out["config"]["gpu_vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)

@@ -71,3 +71,12 @@ def test_dump_outputs_float32_under_the_cap_and_the_same_sample_every_run(tmp_pa
         assert np.isin(b, big[k].astype(np.float32)).all()
         total += b.nbytes
     assert total <= 40_000
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup) == (20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.parse().full is True
