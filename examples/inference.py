@@ -9,12 +9,14 @@ _MODEL = None
 
 
 def inference(task, input_text, model_path, ref_audio=None, ref_text=None, video=None, output="./output", device=0, reuse=True,
-              expert_weights="bf16"):
+              expert_weights="bf16", stream=False):
     global _MODEL
     from unimoe_audio_amd.api import UniMoEAudio
     try:
         if _MODEL is None or not reuse:
             _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights)
+        if stream:
+            return _stream(_MODEL, task, input_text, ref_audio, ref_text, video, output)
         if task == "text_to_speech":
             return _MODEL.text_to_speech(input_text, ref_text, ref_audio, output_dir=output)
         if task == "text_to_music":
@@ -25,6 +27,27 @@ def inference(task, input_text, model_path, ref_audio=None, ref_text=None, video
     except Exception as e:   # the reference swallows every exception and returns None (examples/inference.py:116-118)
         print(f"inference failed: {e}")
         return None
+
+
+def _stream(m, task, input_text, ref_audio, ref_text, video, output):
+    """the *_stream twins: print when each chunk arrives, then the same wav files as the non-streaming methods"""
+    import time
+    t0 = time.perf_counter()
+    if task == "text_to_speech":
+        chunks = m.text_to_speech_stream(input_text, ref_text, ref_audio, output_dir=output)
+    elif task == "text_to_music":
+        chunks = m.text_to_music_stream(input_text, output_dir=output)
+    elif task == "video_text_to_music":
+        chunks = m.video_text_to_music_stream(video, input_text, output_dir=output)
+    else:
+        raise ValueError(f"unknown task {task}")
+    rows = set()
+    for ch in chunks:
+        rows.add(ch.row)
+        print(f"{time.perf_counter() - t0:8.3f} s  row {ch.row}  samples {ch.start_sample}..{ch.start_sample + ch.pcm.numel()}"
+              f"{'  (last)' if ch.final else ''}", flush=True)
+    stem = {"text_to_speech": "speech", "text_to_music": "music", "video_text_to_music": "video_music"}[task]
+    return [os.path.join(output, f"generated_{stem}_{i}.wav") for i in sorted(rows)]
 
 
 def main():
@@ -40,8 +63,10 @@ def main():
     ap.add_argument("--no-reuse", action="store_true")
     ap.add_argument("--expert-weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step)")
+    ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
     a = ap.parse_args()
-    out = inference(a.task, a.input, a.model, a.ref_audio, a.ref_text, a.video, a.output, a.device, not a.no_reuse, a.expert_weights)
+    out = inference(a.task, a.input, a.model, a.ref_audio, a.ref_text, a.video, a.output, a.device, not a.no_reuse, a.expert_weights,
+                    a.stream)
     sys.exit(0 if out else 1)
 
 

@@ -597,6 +597,13 @@ int umoe_codec_ce_bwd(const float* probs, const int64_t* labels, const int32_t* 
  * in_proj, L2-normalised nearest neighbour, subtract.  All DAC dims are load-time parameters. */
 int umoe_rvq_from_codes(const int32_t* codes, const float* codebooks, const float* out_w, const float* out_b, int NQ,
                         int CB, int cd, int Dl, int T, float* z, umoe_stream_t stream);
+/* from_delayed: the same sums for frames [f0, f0 + n) of Bz rows, the codes read from the decode engine's delayed token buffer
+ * tokens [B][Tmax][NQ]: z row r is token row rows[r] (rows == NULL: r), frame t's code of level q is
+ * tokens[row][prefill_step[row] + t + delay[q]][q]; positions at or past t_valid read as `pad`.  prefill_step [B], delay [NQ] and rows
+ * [Bz] are device arrays.  z [Bz][Dl][Lz], frame t written to column t - f0 + z_off. */
+int umoe_rvq_from_delayed(const int32_t* tokens, int B, int Tmax, int NQ, const int32_t* prefill_step, const int32_t* delay, int t_valid,
+                          int pad, const int32_t* rows, int Bz, int f0, int n, const float* codebooks, const float* out_w, const float* out_b,
+                          int CB, int cd, int Dl, float* z, int z_off, int Lz, umoe_stream_t stream);
 int umoe_rvq_nearest(const float* z, const float* codebooks, const float* in_w, const float* in_b, const float* out_w,
                      const float* out_b, int NQ, int CB, int cd, int Dl, int T, int32_t* codes, float* resid_ws,
                      umoe_stream_t stream);
@@ -612,6 +619,17 @@ int umoe_dac_conv1d(const float* x, const float* w, const float* bias, const flo
                     int L, int Cout, int K, int stride, int dilation, int pad, int act, float* y, int* Lout_out, umoe_stream_t stream);
 int umoe_dac_conv_transpose1d(const float* x, const float* w, const float* bias, const float* snake_alpha, int B, int Cin, int L,
                               int Cout, int K, int stride, int pad, int out_pad, float* y, int* Lout_out, umoe_stream_t stream);
+/* Windowed twins for streaming decode: outputs [t_begin, t_begin + n) (absolute positions) of the convolution of a sequence of true
+ * length L, with the full convolution's zero padding outside [0, L).  x holds input positions [x_off, x_off + Lx) ([B][Cin][Lx]),
+ * resid positions [r_off, r_off + Lr), y positions [y_off, y_off + Ly).  Every input position inside [0, L) that the requested outputs
+ * read must lie in the x buffer (checked).  Each output is bit-identical to the same position of umoe_dac_conv1d /
+ * umoe_dac_conv_transpose1d on the whole sequence. */
+int umoe_dac_conv1d_win(const float* x, int x_off, int Lx, const float* w, const float* bias, const float* snake_alpha, const float* resid,
+                        int r_off, int Lr, int B, int Cin, int L, int Cout, int K, int stride, int dilation, int pad, int act, int t_begin,
+                        int n, float* y, int y_off, int Ly, umoe_stream_t stream);
+int umoe_dac_conv_transpose1d_win(const float* x, int x_off, int Lx, const float* w, const float* bias, const float* snake_alpha, int B,
+                                  int Cin, int L, int Cout, int K, int stride, int pad, int out_pad, int t_begin, int n, float* y, int y_off,
+                                  int Ly, umoe_stream_t stream);
 /* windowed-sinc resampling to the codec's rate (torchaudio.transforms.Resample as used at utils.py:101-110, restated): with o / n =
  * orig / new frequency over their gcd, kern [n][2 width + o] the filter bank (built by the host from the published formula),
  * y[b][frame * n + phase] = sum_t kern[phase][t] * x[b][frame * o - width + t] (zero outside [0, L)). */

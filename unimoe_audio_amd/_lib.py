@@ -146,6 +146,7 @@ EXPORTS = [
     "umoe_ep_unique_id", "umoe_ep_comm_create", "umoe_ep_comm_destroy", "umoe_ep_all_to_all",
     "umoe_ep_ipc_export", "umoe_ep_ipc_open", "umoe_ep_ipc_close", "umoe_engine_ep_region", "umoe_engine_ep_connect",
     "umoe_engine_ep_error", "umoe_token_drop", "umoe_router_bwd_drop", "umoe_router_bwd_ex", "umoe_dac_conv1d", "umoe_dac_conv_transpose1d", "umoe_dac_resample", "umoe_vision_rope", "umoe_vision_attn", "umoe_swiglu_pair", "umoe_gelu", "umoe_engine_prefill_pos", "umoe_engine_set_probe", "umoe_engine_info", "umoe_engine_prefill_external", "umoe_engine_set_layer_fp8", "umoe_fp8_convert_probe",
+    "umoe_dac_conv1d_win", "umoe_dac_conv_transpose1d_win", "umoe_rvq_from_delayed",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -197,6 +198,9 @@ def lib():
         L.umoe_dac_conv1d.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(i32), vp]
         L.umoe_dac_conv_transpose1d.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.POINTER(i32), vp]
         L.umoe_dac_resample.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+        L.umoe_dac_conv1d_win.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32] + [i32] * 9 + [i32, i32, vp, i32, i32, vp]
+        L.umoe_dac_conv_transpose1d_win.argtypes = [vp, i32, i32, vp, vp, vp] + [i32] * 8 + [i32, i32, vp, i32, i32, vp]
+        L.umoe_rvq_from_delayed.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]
         L.umoe_vision_rope.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_attn.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]
         L.umoe_swiglu_pair.argtypes = [vp, i32, i32, i32, vp, vp]

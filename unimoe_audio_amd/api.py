@@ -13,13 +13,33 @@ tests/test_gpu_api.py drives text_to_speech / text_to_music end to end with a st
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Union
+from typing import List, NamedTuple, Optional, Union
 
 import torch
 
 from .codec_utils import DecoderOutput, generate_output, prepare_audio_prompt, preprocess_codec
 from .config import UniMoEAudioConfig
 from .model import UniAudioRVQQwen2_5VLMoEForConditionalGeneration
+
+class AudioChunk(NamedTuple):
+    """One piece of a streamed request: samples [start_sample, start_sample + len(pcm)) of row `row` (float32, CPU, the codec's
+    sample rate); `final` on the row's last chunk, which carries the min_duration zero pad of the non-streaming methods."""
+    row: int
+    start_sample: int
+    pcm: torch.Tensor
+    final: bool
+
+
+def _frame_codes(eng, row: int, f0: int, f1: int, t_valid: int) -> torch.Tensor:
+    """codes [f1 - f0, C] (int64, CPU) of frames [f0, f1) of `row`, read from the engine's delayed token buffer as generate_output
+    reverts them: tokens[row][prefill_step + t + delay_c][c], the pad code at positions >= t_valid (DecodeEngine.finish())"""
+    cfg = eng.cfg
+    tok = eng.tokens[row]
+    d = torch.tensor(list(cfg.codec_delay_pattern), device=tok.device)
+    idx = eng.prefill_steps[row] + torch.arange(f0, f1, device=tok.device)[:, None] + d[None]
+    g = tok.gather(0, idx.clamp(max=tok.shape[0] - 1)).long()
+    return torch.where(idx < t_valid, g, torch.full_like(g, cfg.codec_pad_value)).cpu()
+
 
 SYSTEM_MESSAGE = "<|im_start|>system\nYou are a helpful assistant.<|im_end|>\n"
 INPUT_FORMAT = "<|im_start|>user\n{}<|im_end|>\n<|im_start|>assistant\n"
@@ -107,6 +127,69 @@ class UniMoEAudio:
             return []
         return generate_output(cfg, codes, lengths)
 
+    def _stream_updates(self, input_ids, attention_mask, codec_input_ids, max_audio_seconds, min_audio_seconds, chunk_frames, **gen):
+        B = input_ids.shape[0] // 2
+        prefill, steps = prepare_audio_prompt(self.model.config, [None] * B)
+        dec = DecoderOutput(prefill, steps, self.device)
+        return self.model.generate_stream(input_ids, attention_mask, dec, max_tokens=max_audio_seconds * 50, min_tokens=min_audio_seconds * 50,
+                                          codec_input_ids=codec_input_ids, chunk_frames=chunk_frames, **gen)
+
+    @torch.no_grad()
+    def generate_codes_stream(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, codec_input_ids: Optional[torch.Tensor] = None,
+                              max_audio_seconds: int = 10, min_audio_seconds: int = 2, cfg_scale: float = 3.0, temperature: float = 1.2,
+                              top_p: float = 0.95, cfg_filter_top_k: int = 45, eos_prob_mul_factor: float = 0.8, do_sample: bool = True,
+                              seed: int = 0, chunk_frames: int = 25):
+        """generate_codes() as a stream: yields (row, codes [n, 12]) as the decode loop makes frames final, every `chunk_frames`
+        steps.  Concatenated per row, the chunks are generate_codes()'s codes at the same seed."""
+        upds = self._stream_updates(input_ids, attention_mask, codec_input_ids, max_audio_seconds, min_audio_seconds, chunk_frames,
+                                    cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                                    eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
+        for upd in upds:
+            for row, f0, f1, _ in upd.rows:
+                if f1 > f0:
+                    yield row, _frame_codes(self.model._engine, row, f0, f1, upd.dec_step + 1)
+
+    @torch.no_grad()
+    def _stream_audio(self, input_ids, attention_mask, codec_input_ids, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir, stem,
+                      **gen):
+        """The streamed twin of generate_codes + _finish: every state read, the frames that became final go through
+        umoe_rvq_from_delayed and the streaming DAC decoder, queued on the decode stream between two replays (never on a side
+        stream: see DecodeEngine.run_stream).  A row's last chunk carries _finish's min_duration=1 zero pad."""
+        from .dac import DacStreamDecoder, DelayedTokenSource, write_wav_pcm16
+        B = input_ids.shape[0] // 2
+        dm = self.dac.model
+        decoder = source = None
+        start, kept = [0] * B, [[] for _ in range(B)]
+        for upd in self._stream_updates(input_ids, attention_mask, codec_input_ids, max_audio_seconds, min_audio_seconds, chunk_frames, **gen):
+            if decoder is None:
+                source = DelayedTokenSource(self.model._engine, dm)
+                decoder = DacStreamDecoder(dm, B, source)
+            source.t_valid = upd.dec_step + 1
+            n_new = [0] * B
+            for row, f0, f1, _ in upd.rows:
+                n_new[row] = f1 - f0
+            out = decoder.push(n_new)
+            ends = [row for row, _, _, complete in upd.rows if complete]
+            tail = decoder.flush(ends, min_duration=1) if ends else {}
+            # one copy to the host per state read
+            parts = [(row, complete, [t for t in (out.get(row), tail.get(row)) if t is not None]) for row, _, _, complete in upd.rows]
+            flat = [t for _, _, ts in parts for t in ts]
+            host = torch.cat(flat).float().cpu() if flat else torch.zeros(0)
+            o = 0
+            for row, complete, ts in parts:
+                n = sum(t.numel() for t in ts)
+                pcm, o = host[o:o + n], o + n
+                if n == 0 and not complete:
+                    continue
+                yield AudioChunk(row, start[row], pcm, complete)
+                start[row] += pcm.numel()
+                if output_dir is not None:
+                    kept[row].append(pcm)
+        if output_dir is not None:
+            os.makedirs(output_dir, exist_ok=True)
+            for i in range(B):
+                write_wav_pcm16(os.path.join(output_dir, f"generated_{stem}_{i}.wav"), torch.cat(kept[i])[None], dm.sample_rate)
+
     # ---- reference task methods (both spellings) -----------------------------------------------------------------------
     def _texts(self, obj: Union[str, List[str]]) -> List[str]:
         if isinstance(obj, str):
@@ -129,21 +212,40 @@ class UniMoEAudio:
                       min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                       save_name: str = "music", cfg_scale: float = 10.0, eos_prob_mul_factor: float = 0.6, do_sample: bool = True,
                       **_) -> List[str]:
+        enc = self._music_prompt(caption)
+        audios = self.generate_codes(enc.input_ids, enc.attention_mask, None, max_audio_seconds, min_audio_seconds, cfg_scale,
+                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample)
+        return self._finish(audios, output_dir, save_name)
+
+    def _music_prompt(self, caption):
         caption = self._texts(caption)
         neg = SYSTEM_MESSAGE + INPUT_FORMAT.format("<|MUSIC_START|>Low quality.<|MUSIC_END|>") + AUDIO_START
         texts = []
         for c in caption:
             texts += [neg, SYSTEM_MESSAGE + INPUT_FORMAT.format("<|MUSIC_START|>" + c + "<|MUSIC_END|>") + AUDIO_START]
-        enc = self.tokenizer(texts, add_special_tokens=False, return_tensors="pt", padding=True)
-        audios = self.generate_codes(enc.input_ids, enc.attention_mask, None, max_audio_seconds, min_audio_seconds, cfg_scale,
-                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample)
-        return self._finish(audios, output_dir, save_name)
+        return self.tokenizer(texts, add_special_tokens=False, return_tensors="pt", padding=True)
+
+    def text_to_music_stream(self, caption: Union[str, List[str]], output_dir: Optional[str] = None, max_audio_seconds: int = 20,
+                             min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
+                             save_name: str = "music", cfg_scale: float = 10.0, eos_prob_mul_factor: float = 0.6, do_sample: bool = True,
+                             chunk_frames: int = 25, **_):
+        """text_to_music() as a stream of AudioChunks (see _stream_audio); output_dir: also write text_to_music()'s wav files at the end"""
+        enc = self._music_prompt(caption)
+        return self._stream_audio(enc.input_ids, enc.attention_mask, None, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir,
+                                  save_name, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample)
 
     def text_to_speech(self, transcription: Union[str, List[str], None] = None, prompt_transcription: Optional[str] = None,
                        prompt_wav: Optional[str] = None, output_dir: str = "./", max_audio_seconds: int = 10,
                        min_audio_seconds: int = 2, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                        caption=None, prompt_text=None, prompt_codec=None, save_name: str = "speech", cfg_scale: float = 1.0,
                        eos_prob_mul_factor: float = 1.0, do_sample: bool = True, **_) -> List[str]:
+        enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec)
+        audios = self.generate_codes(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, cfg_scale,
+                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample)
+        return self._finish(audios, output_dir, save_name)
+
+    def _speech_prompt(self, transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec):
         texts_in = self._texts(transcription if transcription is not None else caption)
         ptxt = prompt_transcription if prompt_transcription is not None else prompt_text
         if prompt_codec is None:
@@ -161,9 +263,18 @@ class UniMoEAudio:
                       SYSTEM_MESSAGE + INPUT_FORMAT.format(wrap(t)) + AUDIO_START]
         enc = self.tokenizer(texts, add_special_tokens=False, return_tensors="pt", padding=True)
         codec = pc.unsqueeze(0).expand(len(texts), -1, -1).reshape(-1, pc.shape[1])
-        audios = self.generate_codes(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, cfg_scale,
-                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample)
-        return self._finish(audios, output_dir, save_name)
+        return enc, codec
+
+    def text_to_speech_stream(self, transcription: Union[str, List[str], None] = None, prompt_transcription: Optional[str] = None,
+                              prompt_wav: Optional[str] = None, output_dir: Optional[str] = None, max_audio_seconds: int = 10,
+                              min_audio_seconds: int = 2, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
+                              caption=None, prompt_text=None, prompt_codec=None, save_name: str = "speech", cfg_scale: float = 1.0,
+                              eos_prob_mul_factor: float = 1.0, do_sample: bool = True, chunk_frames: int = 25, **_):
+        """text_to_speech() as a stream of AudioChunks (see _stream_audio); output_dir: also write text_to_speech()'s wav files at the end"""
+        enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec)
+        return self._stream_audio(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir,
+                                  save_name, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample)
 
     def video_text_to_music(self, video, caption: Union[str, List[str]], output_dir: str = "./", max_audio_seconds: int = 20,
                             min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
@@ -176,6 +287,20 @@ class UniMoEAudio:
         vision_in_generate: False (default) = the reference's inference path, whose generate() never feeds the pixels to the model (the
         pad tokens keep their text embeddings, positions stay 1-D; see model.generate); True = vision tower + 3-D positions.
         A file path is decoded when a decoder is importable here (torchvision.io / decord / moviepy, in that order)."""
+        enc, vis = self._video_prompt(video, caption, sampling_fps, max_frames)
+        R = enc.input_ids.shape[0]
+        cfg = self.model.config
+        prefill, steps = prepare_audio_prompt(cfg, [None] * (R // 2))
+        dec = DecoderOutput(prefill, steps, self.device)
+        codes, lengths = self.model.generate(enc.input_ids, enc.attention_mask, dec, max_tokens=max_audio_seconds * 50,
+                                             min_tokens=min_audio_seconds * 50, **vis,
+                                             cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                                             eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, vision_in_generate=vision_in_generate)
+        audios = [] if codes is None else generate_output(cfg, codes, lengths)
+        return self._finish(audios, output_dir, save_name)
+
+    def _video_prompt(self, video, caption, sampling_fps, max_frames):
+        """(tokenized prompts, the pixel arguments of generate()) of video_text_to_music"""
         from .vision import frames_to_patches
         caption = self._texts(caption)
         if isinstance(video, (str, bytes, os.PathLike)):
@@ -192,16 +317,19 @@ class UniMoEAudio:
             texts += [neg, SYSTEM_MESSAGE + INPUT_FORMAT.format(vid + "<|MUSIC_START|>" + c + "<|MUSIC_END|>") + AUDIO_START]
         enc = self.tokenizer(texts, add_special_tokens=False, return_tensors="pt", padding=True)
         R = len(texts)
-        cfg = self.model.config
-        prefill, steps = prepare_audio_prompt(cfg, [None] * (R // 2))
-        dec = DecoderOutput(prefill, steps, self.device)
-        codes, lengths = self.model.generate(enc.input_ids, enc.attention_mask, dec, max_tokens=max_audio_seconds * 50,
-                                             min_tokens=min_audio_seconds * 50, pixel_values_videos=patches.repeat(R, 1),
-                                             video_grid_thw=grid[None].repeat(R, 1), second_per_grid_ts=torch.full((R,), 2.0 / max(sampling_fps, 1e-6)),
-                                             cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
-                                             eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, vision_in_generate=vision_in_generate)
-        audios = [] if codes is None else generate_output(cfg, codes, lengths)
-        return self._finish(audios, output_dir, save_name)
+        return enc, dict(pixel_values_videos=patches.repeat(R, 1), video_grid_thw=grid[None].repeat(R, 1),
+                         second_per_grid_ts=torch.full((R,), 2.0 / max(sampling_fps, 1e-6)))
+
+    def video_text_to_music_stream(self, video, caption: Union[str, List[str]], output_dir: Optional[str] = None, max_audio_seconds: int = 20,
+                                   min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
+                                   save_name: str = "video_music", cfg_scale: float = 10.0, eos_prob_mul_factor: float = 0.6,
+                                   do_sample: bool = True, fps: float = 1.0, sampling_fps: float = 1.0, max_frames: int = 8,
+                                   vision_in_generate: bool = False, chunk_frames: int = 25, **_):
+        """video_text_to_music() as a stream of AudioChunks (see _stream_audio); output_dir: also write its wav files at the end"""
+        enc, vis = self._video_prompt(video, caption, sampling_fps, max_frames)
+        return self._stream_audio(enc.input_ids, enc.attention_mask, None, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir,
+                                  save_name, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, vision_in_generate=vision_in_generate, **vis)
 
 
 def _decode_video_file(path: str, sampling_fps: float, max_frames: int) -> torch.Tensor:

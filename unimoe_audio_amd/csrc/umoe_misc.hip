@@ -857,23 +857,50 @@ extern "C" int umoe_delay_step(int64_t* pred, int32_t* tokens, int32_t* state, c
 // from_codes: z[d][t] = sum_q ( out_w[q][d][:] . codebook[q][codes[q][t]][:] + out_b[q][d] )
 // third-party descript-audio-codec 1.0.0 ResidualVectorQuantize.from_codes (reference call site
 // utils/UniMoE_Audio_utils.py:123).  codes [NQ][T], codebooks [NQ][CB][cd], out_w [NQ][Dl][cd], z [Dl][T].
+template <class CodeAt>
+__device__ __forceinline__ float rvq_sum(const float* __restrict__ cb, const float* __restrict__ ow, const float* __restrict__ ob, int NQ,
+                                         int CB, int cd, int Dl, int d, CodeAt code_at) {
+    float acc = 0.f;
+    for (int q = 0; q < NQ; ++q) {
+        int code = code_at(q);
+        code = min(max(code, 0), CB - 1);
+        const float* e = cb + ((size_t)q * CB + code) * cd;
+        const float* w = ow + ((size_t)q * Dl + d) * cd;
+        float s = ob ? ob[(size_t)q * Dl + d] : 0.f;
+        for (int j = 0; j < cd; ++j) s += w[j] * e[j];
+        acc += s;
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void rvq_from_codes_kernel(const int32_t* __restrict__ codes, const float* __restrict__ cb,
                                                              const float* __restrict__ ow, const float* __restrict__ ob,
                                                              int NQ, int CB, int cd, int Dl, int T, float* __restrict__ z) {
     const int t = blockIdx.x;
-    for (int d = threadIdx.x; d < Dl; d += blockDim.x) {
-        float acc = 0.f;
-        for (int q = 0; q < NQ; ++q) {
-            int code = codes[(size_t)q * T + t];
-            code = min(max(code, 0), CB - 1);
-            const float* e = cb + ((size_t)q * CB + code) * cd;
-            const float* w = ow + ((size_t)q * Dl + d) * cd;
-            float s = ob ? ob[(size_t)q * Dl + d] : 0.f;
-            for (int j = 0; j < cd; ++j) s += w[j] * e[j];
-            acc += s;
-        }
-        z[(size_t)d * T + t] = acc;
-    }
+    for (int d = threadIdx.x; d < Dl; d += blockDim.x)
+        z[(size_t)d * T + t] = rvq_sum(cb, ow, ob, NQ, CB, cd, Dl, d, [&](int q) { return codes[(size_t)q * T + t]; });
+}
+
+// from_delayed: the same sums, the codes read straight from the decode engine's delayed token buffer tokens [B][Tmax][NQ]: frame t of
+// row rows[r] has code tokens[row][prefill_step[row] + t + delay[q]][q] (codec_utils.generate_output's revert), positions at or past
+// t_valid read as `pad` (what DecodeEngine.finish() fills there).  z [Bz][Dl][Lz], frame t in column t - f0 + z_off.
+__global__ __launch_bounds__(256) void rvq_from_delayed_kernel(const int32_t* __restrict__ tokens, int B, int Tmax, int NQ,
+                                                               const int32_t* __restrict__ prefill_step, const int32_t* __restrict__ delay,
+                                                               int t_valid, int pad, const int32_t* __restrict__ rows, int f0,
+                                                               const float* __restrict__ cb, const float* __restrict__ ow,
+                                                               const float* __restrict__ ob, int CB, int cd, int Dl,
+                                                               float* __restrict__ z, int z_off, int Lz) {
+    const int t = f0 + blockIdx.x, r = blockIdx.y;
+    const int row = rows ? rows[r] : r;
+    if (row < 0 || row >= B) return;
+    const int32_t* tb = tokens + (size_t)row * Tmax * NQ;
+    const int p0 = prefill_step[row] + t;
+    float* zr = z + (size_t)r * Dl * Lz + (t - f0 + z_off);
+    for (int d = threadIdx.x; d < Dl; d += blockDim.x)
+        zr[(size_t)d * Lz] = rvq_sum(cb, ow, ob, NQ, CB, cd, Dl, d, [&](int q) {
+            const int p = p0 + delay[q];
+            return (p >= 0 && p < t_valid) ? tb[(size_t)p * NQ + q] : pad;
+        });
 }
 
 extern "C" int umoe_rvq_from_codes(const int32_t* codes, const float* codebooks, const float* out_w, const float* out_b,
@@ -881,6 +908,22 @@ extern "C" int umoe_rvq_from_codes(const int32_t* codes, const float* codebooks,
     UMOE_REQUIRE(codes && codebooks && out_w && z && NQ > 0 && CB > 0 && cd > 0 && Dl > 0, "umoe_rvq_from_codes: bad argument");
     if (T == 0) return 0;
     rvq_from_codes_kernel<<<dim3((unsigned)T), 256, 0, (hipStream_t)stream>>>(codes, codebooks, out_w, out_b, NQ, CB, cd, Dl, T, z);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int umoe_rvq_from_delayed(const int32_t* tokens, int B, int Tmax, int NQ, const int32_t* prefill_step, const int32_t* delay,
+                                     int t_valid, int pad, const int32_t* rows, int Bz, int f0, int n, const float* codebooks,
+                                     const float* out_w, const float* out_b, int CB, int cd, int Dl, float* z, int z_off, int Lz,
+                                     umoe_stream_t stream) {
+    UMOE_REQUIRE(tokens && prefill_step && delay && codebooks && out_w && z && B > 0 && Tmax > 0 && NQ > 0 && CB > 0 && cd > 0 && Dl > 0 &&
+                 Bz > 0 && f0 >= 0 && n >= 0 && t_valid >= 0 && t_valid <= Tmax, "umoe_rvq_from_delayed: bad argument");
+    UMOE_REQUIRE(rows || Bz <= B, "umoe_rvq_from_delayed: %d z rows without a row map over %d token rows", Bz, B);
+    UMOE_REQUIRE(z_off >= 0 && (long long)z_off + n <= Lz, "umoe_rvq_from_delayed: %d frames at column %d of a %d-column buffer", n, z_off, Lz);
+    if (n == 0) return 0;
+    rvq_from_delayed_kernel<<<dim3((unsigned)n, (unsigned)Bz), 256, 0, (hipStream_t)stream>>>(tokens, B, Tmax, NQ, prefill_step, delay, t_valid,
+                                                                                              pad, rows, f0, codebooks, out_w, out_b, CB, cd,
+                                                                                              Dl, z, z_off, Lz);
     UMOE_LAUNCH_CHECK();
     return 0;
 }

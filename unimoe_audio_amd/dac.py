@@ -407,3 +407,309 @@ class Dac:
             pad = torch.zeros((audio_out.size(0), int((min_duration - duration) * sr)), dtype=audio_out.dtype)
             audio_out = torch.cat((audio_out, pad), dim=1)
         write_wav_pcm16(save_path, audio_out, sr)
+
+
+# ----------------------------------------------------------------------------------------------- streaming decode
+# The decoder is a chain of convolutions with bounded receptive fields, so a prefix of the waveform is fixed by a prefix of the
+# latent frames.  stream_plan() walks the graph DacModel._run walks and derives, per conv, which input positions an output reads;
+# DacStreamDecoder keeps one buffer per layer input, trimmed to the left context the next window needs, and computes every output
+# that the frames pushed so far fully determine.  Each output runs through the windowed kernels (umoe_dac_conv1d_win /
+# umoe_dac_conv_transpose1d_win), whose arithmetic per output is that of the full-sequence kernels, so the streamed waveform is
+# bit-identical to DacModel.decode for any schedule of pushes.
+
+_OPEN = 1 << 26          # true length of a sequence that is still growing: no window reads past what was pushed, so any bound works
+
+
+class StreamLayer:
+    """One conv of the decoder: reads buffer `src` (= its own index), writes buffer src + 1; `res` is the buffer added as the residual.
+    `left` / `look`: input positions before / after the one aligned with an output (t * stride for a conv, t // stride for a
+    transposed conv) that the output reads."""
+
+    def __init__(self, kind, mod, snake, cin, cout, K, stride, dil, pad, out_pad, tanh, res):
+        self.kind, self.mod, self.snake = kind, mod, snake
+        self.cin, self.cout, self.K, self.stride, self.dil, self.pad, self.out_pad = cin, cout, K, stride, dil, pad, out_pad
+        self.tanh, self.res = tanh, res
+        s = stride
+        if kind == "conv":
+            self.left, self.look = pad, (K - 1) * dil - pad
+        else:
+            self.left = max(t // s - self.reads(t, t + 1)[0] for t in range(s))
+            self.look = max(self.reads(t, t + 1)[1] - t // s for t in range(s))
+
+    def out_len(self, L: int) -> int:
+        if self.kind == "conv":
+            return (L + 2 * self.pad - self.dil * (self.K - 1) - 1) // self.stride + 1
+        return (L - 1) * self.stride - 2 * self.pad + self.K + self.out_pad
+
+    def reads(self, t0: int, t1: int):
+        """[lo, hi] of the input positions (unclamped) that outputs [t0, t1) read"""
+        s, p, K = self.stride, self.pad, self.K
+        if self.kind == "conv":
+            return t0 * s - p, (t1 - 1) * s - p + (K - 1) * self.dil
+        return -((K - 1 - t0 - p) // s), (t1 - 1 + p) // s
+
+    def ready(self, A: int) -> int:
+        """how many outputs the input positions [0, A) determine when more input may follow"""
+        s, p, K = self.stride, self.pad, self.K
+        n = (A - 1 + p - (K - 1) * self.dil) // s + 1 if self.kind == "conv" else s * A - p
+        return max(0, min(n, self.out_len(A)))
+
+
+class StreamPlan:
+    def __init__(self, layers: List[StreamLayer], hop: int, latent_dim: int):
+        self.layers, self.hop, self.latent_dim = layers, hop, latent_dim
+
+    def out_len(self, frames: int) -> int:
+        L = frames
+        for ly in self.layers:
+            L = ly.out_len(L)
+        return L
+
+    def ready(self, frames: int) -> int:
+        """waveform samples that `frames` latent frames determine while more may follow"""
+        n = frames
+        for ly in self.layers:
+            n = ly.ready(n)
+        return n
+
+    @property
+    def lookahead_frames(self) -> int:
+        """frames past a sample's own frame that must arrive before the sample is determined (steady state)"""
+        A = 64 * self.hop
+        return -((self.ready(A) - A * self.hop) // self.hop)
+
+
+def stream_plan(model: DacModel) -> StreamPlan:
+    """The decoder graph of DacModel._run / decode as a list of StreamLayers (first conv; per DecoderBlock the transposed conv and
+    3 x [conv K=7 dilated, conv K=1 + residual]; last conv + tanh).  Pure index arithmetic: runs wherever the model lives."""
+    layers: List[StreamLayer] = []
+
+    def add(kind, m, snake, res=None, tanh=False):
+        g = m.geom
+        shape = m.weight_v.shape
+        cin, cout = (shape[0], shape[1]) if g["transposed"] else (shape[1], shape[0])
+        layers.append(StreamLayer(kind, m, snake, int(cin), int(cout), int(shape[2]), g["stride"], g.get("dilation", 1), g["padding"],
+                                  g.get("output_padding", 0), tanh, res))
+
+    def walk(mods):
+        snake = None
+        for m in mods:
+            if isinstance(m, Snake1d):
+                snake = m
+            elif isinstance(m, _WN):
+                add("convt" if m.geom["transposed"] else "conv", m, snake)
+                snake = None
+            elif isinstance(m, _Seq) and len(m.items()) == 4 and isinstance(m.items()[0], Snake1d):      # ResidualUnit: x + block(x)
+                a0, c0, a1, c1 = m.items()
+                unit_in = len(layers)
+                add("conv", c0, a0)
+                add("conv", c1, a1, res=unit_in)
+            elif isinstance(m, _Seq):
+                walk(m.items())
+            elif isinstance(m, nn.Tanh):
+                layers[-1].tanh = True
+
+    walk(model.decoder.items())
+    hop = math.prod(ly.stride for ly in layers if ly.kind == "convt")
+    return StreamPlan(layers, hop, model.latent_dim)
+
+
+class _Group:
+    """Rows that share one timeline: buffer i holds positions [base[i], have[i]) of layer i's input ([rows, C, have - base])."""
+
+    def __init__(self, rows, n_buf):
+        self.rows = list(rows)
+        self.have = [0] * (n_buf + 1)
+        self.keep = [0] * n_buf
+        self.base = [0] * n_buf
+        self.bufs = [None] * n_buf
+        self.L = None                                  # true lengths per buffer, once flushed
+
+    def split(self, rows):
+        g = _Group(rows, len(self.bufs))
+        idx = torch.tensor([self.rows.index(r) for r in rows], dtype=torch.long)
+        g.have, g.keep, g.base = list(self.have), list(self.keep), list(self.base)
+        g.bufs = [None if b is None else b.index_select(0, idx.to(b.device)) for b in self.bufs]
+        return g
+
+
+class DacStreamDecoder:
+    """Streaming DacModel.decode for `batch` rows.  push(n_new) takes how many more latent frames each row has and returns the new
+    waveform samples every row's frames now determine; flush(rows) applies the true right edge (and Dac.decode's min_duration pad).
+    For any schedule of pushes the concatenated samples of a row are bit-identical to DacModel.decode(z)[row, 0].
+    `source(rows, f0, n, out, col)` writes latent frames [f0, f0 + n) of `rows` into out[:, :, col:col + n] (out [len(rows), Dl, W]).
+    Rows that receive the same frames are decoded in one launch per layer; they part when their schedules do.
+    All work is queued on the current stream: the decode engine's (see model.DecodeEngine.run_stream)."""
+
+    def __init__(self, model: DacModel, batch: int, source, dtype=torch.float32, device=None):
+        self.model, self.batch, self.source = model, int(batch), source
+        self.plan = stream_plan(model)
+        self.dtype = dtype
+        self.device = device if device is not None else next(model.parameters()).device
+        self._groups = [_Group(range(self.batch), len(self.plan.layers))]
+        self.samples = [0] * self.batch
+        self.closed = [False] * self.batch
+
+    # ---- executor of one window (the test suite swaps in a float64 restatement) ---------------------------------------------
+    def _conv(self, ly: StreamLayer, x, x_off, L_true, t0, n, resid, r_off, y, y_off):
+        """outputs [t0, t0 + n) of layer ly into y (positions [y_off, ...)); x / resid hold positions from x_off / r_off"""
+        f = self.model._folded()
+        w, b = f[ly.mod]
+        a = f[ly.snake] if ly.snake is not None else None
+        assert x.shape[1] == ly.cin and y.shape[1] == ly.cout and y.shape[0] == x.shape[0]
+        assert resid is None or (resid.shape[:2] == y.shape[:2])
+        if ly.kind == "conv":
+            _lib_call("umoe_dac_conv1d_win", _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), _dev_f32(resid), r_off,
+                      0 if resid is None else resid.shape[2], x.shape[0], ly.cin, L_true, ly.cout, ly.K, ly.stride, ly.dil, ly.pad,
+                      int(ly.tanh), t0, n, _dev_f32(y), y_off, y.shape[2], _stream())
+        else:
+            _lib_call("umoe_dac_conv_transpose1d_win", _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), x.shape[0],
+                      ly.cin, L_true, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, t0, n, _dev_f32(y), y_off, y.shape[2], _stream())
+
+    def _empty(self, *shape):
+        return torch.empty(shape, dtype=self.dtype, device=self.device)
+
+    def _append(self, g: _Group, i: int, C: int, n: int):
+        """room for n more positions in buffer i (keeping [keep, have)); returns (tensor, column of position have)"""
+        old, keep = g.bufs[i], g.keep[i]
+        kept = g.have[i] - keep
+        buf = self._empty(len(g.rows), C, kept + n)
+        if kept:
+            buf[:, :, :kept] = old[:, :, keep - g.base[i]: keep - g.base[i] + kept]
+        g.bufs[i], g.base[i] = buf, keep
+        return buf, kept
+
+    def _advance(self, g: _Group, n_new: int, final: bool) -> torch.Tensor:
+        P = self.plan
+        lys = P.layers
+        if n_new:
+            buf, col = self._append(g, 0, P.latent_dim, n_new)
+            self.source(g.rows, g.have[0], n_new, buf, col)
+            g.have[0] += n_new
+        if final:
+            g.L = [g.have[0]]
+            for ly in lys:
+                g.L.append(ly.out_len(g.L[-1]))
+        wave = None
+        t_wave = g.have[-1]
+        for i, ly in enumerate(lys):
+            target = g.L[i + 1] if final else ly.ready(g.have[i])
+            if ly.res is not None:
+                target = min(target, g.have[ly.res])
+            n = target - g.have[i + 1]
+            if n <= 0:
+                continue
+            t0 = g.have[i + 1]
+            if i + 1 == len(lys):
+                y, y_off = self._empty(len(g.rows), ly.cout, n), t0
+            else:
+                y, col = self._append(g, i + 1, ly.cout, n)
+                y_off = t0 - col
+            resid = g.bufs[ly.res] if ly.res is not None else None
+            r_off = g.base[ly.res] if ly.res is not None else 0
+            self._conv(ly, g.bufs[i], g.base[i], g.L[i] if final else _OPEN, t0, n, resid, r_off, y, y_off)
+            g.have[i + 1] = target
+            if i + 1 == len(lys):
+                wave = y[:, 0]
+        # left context: what the next window of each reader of buffer i starts at
+        for i, ly in enumerate(lys):
+            need = max(0, ly.reads(g.have[i + 1], g.have[i + 1] + 1)[0])
+            for j, lj in enumerate(lys):
+                if lj.res == i:
+                    need = min(need, g.have[j + 1])
+            g.keep[i] = max(g.keep[i], min(need, g.have[i]))
+        if wave is None:
+            wave = self._empty(len(g.rows), 0)
+        assert wave.shape[1] == g.have[-1] - t_wave
+        return wave
+
+    def _regroup(self, key):
+        """split every group so that all rows of a group have the same key(row)"""
+        out = []
+        for g in self._groups:
+            ks = {}
+            for r in g.rows:
+                ks.setdefault(key(r), []).append(r)
+            out.extend([g] if len(ks) == 1 else [g.split(rs) for rs in ks.values()])
+        self._groups = out
+
+    def push(self, n_new) -> dict:
+        """n_new: more latent frames per row (a list of `batch` ints, or one int for all) -> {row: new samples (1-D tensor)}"""
+        n_new = [int(n_new)] * self.batch if isinstance(n_new, int) else [int(v) for v in n_new]
+        assert len(n_new) == self.batch and min(n_new) >= 0
+        for r in range(self.batch):
+            if n_new[r] and self.closed[r]:
+                raise ValueError(f"row {r} was flushed already")
+        self._regroup(lambda r: n_new[r])
+        out = {}
+        for g in self._groups:
+            n = n_new[g.rows[0]]
+            if n:
+                w = self._advance(g, n, False)
+                for k, r in enumerate(g.rows):
+                    out[r] = w[k]
+                    self.samples[r] += w.shape[1]
+        return out
+
+    def flush(self, rows, min_duration=None) -> dict:
+        """The rest of each row's waveform: the true right edge (a decode of T frames has plan.out_len(T) samples), then the zero pad
+        Dac.decode appends when the audio is shorter than min_duration seconds -> {row: samples (1-D tensor)}"""
+        rows = [rows] if isinstance(rows, int) else list(rows)
+        todo = set(rows)
+        for r in rows:
+            if self.closed[r]:
+                raise ValueError(f"row {r} was flushed already")
+        self._regroup(lambda r: r in todo)
+        out = {}
+        keep = []
+        for g in self._groups:
+            if g.rows[0] not in todo:
+                keep.append(g)
+                continue
+            w = self._advance(g, 0, True)
+            for k, r in enumerate(g.rows):
+                a = w[k]
+                total = self.samples[r] + a.shape[0]
+                sr = self.model.sample_rate
+                duration = total / sr
+                if min_duration is not None and duration < min_duration:                  # Dac.decode
+                    a = torch.cat((a, torch.zeros(int((min_duration - duration) * sr), dtype=a.dtype, device=a.device)))
+                out[r] = a
+                self.samples[r] += a.shape[0]
+                self.closed[r] = True
+        self._groups = keep
+        return out
+
+
+def _lib_call(name, *args):
+    L.check(getattr(L.lib(), name)(*args), name)
+
+
+class DelayedTokenSource:
+    """Latent frames straight from a decode engine's delayed token buffer (umoe_rvq_from_delayed): frame t of row b reverts the delay
+    pattern, tokens[b][prefill_step_b + t + delay_c][c], and sums the codebook rows like DacModel.from_codes, bit for bit.
+    `t_valid` (dec_step + 1 of the last state read): token positions at or past it read as the pad code, as DecodeEngine.finish() has it."""
+
+    def __init__(self, engine, model: DacModel):
+        cfg = engine.cfg
+        self.engine, self.model = engine, model
+        self.pad = int(cfg.codec_pad_value)
+        dev = engine.tokens.device
+        self.prefill = torch.tensor(engine.prefill_steps, dtype=torch.int32, device=dev)
+        self.delay = torch.tensor(list(cfg.codec_delay_pattern), dtype=torch.int32, device=dev)
+        self.t_valid = 0
+        self._rows = {}
+
+    def __call__(self, rows, f0, n, out, col):
+        eng, f = self.engine, self.model._folded()
+        B, Tmax, NQ = eng.tokens.shape
+        if NQ > self.model.n_codebooks:
+            raise L.UmoeError(f"{NQ} codec channels, the DAC has {self.model.n_codebooks} codebooks")
+        key = tuple(rows)
+        if key not in self._rows:
+            self._rows[key] = torch.tensor(rows, dtype=torch.int32, device=eng.tokens.device)
+        cb = f["cb"][:NQ].contiguous()
+        ow, ob = f["out_w"][:NQ].contiguous(), f["out_b"][:NQ].contiguous()
+        _lib_call("umoe_rvq_from_delayed", C.c_void_p(eng.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(self.prefill.data_ptr()),
+                  C.c_void_p(self.delay.data_ptr()), int(self.t_valid), self.pad, C.c_void_p(self._rows[key].data_ptr()), len(rows), f0, n,
+                  _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2], ow.shape[1], _dev_f32(out), col, out.shape[2], _stream())

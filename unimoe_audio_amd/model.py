@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -422,6 +422,50 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         return codes, lengths
 
 
+    @torch.no_grad()
+    def generate_stream(self, input_ids, attention_mask, dec_output: DecoderOutput, max_tokens, min_tokens=None,
+                        codec_input_ids: Optional[torch.Tensor] = None, pixel_values=None, pixel_values_videos=None,
+                        image_grid_thw=None, video_grid_thw=None, second_per_grid_ts=None, cfg_scale: float = 3.0,
+                        temperature: float = 1.2, top_p: float = 0.95, cfg_filter_top_k: int = 45,
+                        eos_prob_mul_factor: float = 0.8, do_sample: bool = True, debug_guidance_step: int = 0, use_cache=True,
+                        seed: int = 0, use_graph: bool = True, poll_every: int = 16, vision_in_generate: bool = False,
+                        expert_weights: Optional[str] = None, chunk_frames: int = 25):
+        """generate() with the same arguments (poll_every is unused: the state is read every `chunk_frames` steps), as a generator of
+        DecodeEngine.run_stream's StreamUpdates; the engine (self._engine) holds the token buffer the updates index.  The tokens are
+        generate()'s.  At the end dec_output.generated_tokens is set as generate() sets it.  Teacher labels and expert-parallel
+        engines are not streamed: use generate()."""
+        if getattr(dec_output, "labels_prefill", None) is not None:
+            raise L.UmoeError("generate_stream: teacher labels (DecoderOutput.labels_prefill) run the diagnostic path of generate() only")
+        if not use_cache and codec_input_ids is not None:
+            raise AssertionError("use_cache=False with a codec prompt: the reference asserts use_cache here (model.py:1092-1093)")
+        dev = self.device
+        input_ids, attention_mask = input_ids.to(dev), attention_mask.to(dev)
+        B = input_ids.shape[0] // 2
+        T = input_ids.shape[1]
+        eng = self.engine(B, T, int(max_tokens), expert_weights=expert_weights)
+        if (eng.ep is not None and eng.ep.size > 1) or getattr(eng, "sharded", False):
+            raise L.UmoeError("generate_stream: expert-parallel decode is not streamed; use generate()")
+        pos3 = deltas = None
+        if vision_in_generate and (pixel_values is not None or pixel_values_videos is not None):
+            x = self.multimodal_embedding(input_ids, None if codec_input_ids is None else codec_input_ids.to(dev), pixel_values, image_grid_thw,
+                                          pixel_values_videos, video_grid_thw)
+            pos3, deltas = self.get_rope_index(input_ids, image_grid_thw, video_grid_thw, second_per_grid_ts, attention_mask)
+        else:
+            x = self.calculate_input_embedding(input_ids, None if codec_input_ids is None else codec_input_ids.to(dev))
+        eng.prefill(x.reshape(-1, x.shape[-1]).contiguous(), attention_mask, position_ids=pos3, rope_deltas=deltas)
+        eng.start_decode(dec_output.generated_tokens, dec_output.prefill_steps, int(max_tokens), min_tokens,
+                         cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, top_k=cfg_filter_top_k,
+                         eos_mul=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
+        ends = {}
+        for upd in eng.run_stream(int(chunk_frames), use_graph=use_graph):
+            ends.update({r: f1 for r, _, f1, done in upd.rows if done})
+            yield upd
+        _, lengths, tokens = eng.finish()
+        dec_output.generated_tokens = tokens
+        if lengths is not None and [ends.get(b) for b in range(B)] != [int(v) for v in lengths.cpu()]:
+            raise AssertionError(f"run_stream ended rows at {ends}, finish() has lengths {lengths.tolist()}")
+
+
 def golden_loss(guided_BxCxV: torch.Tensor, labels_BxC: torch.Tensor, eos: int) -> Optional[torch.Tensor]:
     """The teacher's loss of one decode step (reference _decoder_step, model.py:1019-1048): labels above EOS are ignored on channel 0,
     labels >= EOS on the delayed channels; CrossEntropy per channel on the GUIDED logits (after CFG, masks and the EOS factor),
@@ -437,6 +481,12 @@ def golden_loss(guided_BxCxV: torch.Tensor, labels_BxC: torch.Tensor, eos: int) 
         l = torch.nn.functional.cross_entropy(guided_BxCxV[:, c].float(), lab[:, c], ignore_index=-100) * (3 if c == 0 else 1)
         total = l if total is None else total + l
     return total
+
+
+class StreamUpdate(NamedTuple):
+    """One state read of DecodeEngine.run_stream: dec_step, and (row, f0, f1, complete) per row with news."""
+    dec_step: int
+    rows: List[Tuple[int, int, int, bool]]
 
 
 class DecodeEngine:
@@ -702,6 +752,49 @@ class DecodeEngine:
             if self.all_done():
                 break
         return done
+
+    def run_stream(self, chunk_frames: int, use_graph: bool = True):
+        """run() in chunks: the same steps in the same order (graph replays, seeds), with the state read once every `chunk_frames`
+        steps instead of every `poll_every` (steps past the end are no-ops on the token state, so the tokens are those of run()).
+        Yields a StreamUpdate per read: dec_step and, per row, the newly final frames [f0, f1) -- a frame is final once all its
+        delayed channels are written (dec_step >= prefill_step + t + max_delay) and it lies before the row's length -- and whether
+        the row is complete.  On the last update every row is complete and the lengths are finish()'s.
+        Whatever the caller does between updates (the streaming DAC decode) must be queued on the current stream, between the
+        replays: the flat expert launch's in-launch hand-offs assume all of its workgroups are resident, so nothing may run on a
+        side stream that could hold CUs while it runs."""
+        if chunk_frames < 1:
+            raise ValueError("chunk_frames must be >= 1")
+        B, md = self.batch, max(self.cfg.codec_delay_pattern)
+        ps = self.prefill_steps
+        budget = self.max_tokens - int(self.state[4 * B].item())
+        emitted, complete = [0] * B, [False] * B
+        done, over = 0, budget <= 0
+        while not all(complete):
+            if not over:
+                n = min(chunk_frames, budget - done)
+                for _ in range(n):
+                    self.step(use_graph)
+                done += n
+                over = self.all_done() or done >= budget
+            st = self.state.cpu()
+            dec_step = int(st[4 * B])
+            rows = []
+            for b in range(B):
+                if complete[b]:
+                    continue
+                fin = int(st[2 * B + b])
+                if over:                          # finish()'s lengths
+                    final_len = max((dec_step + 1 - md if fin == -1 else fin) - ps[b], 0)
+                else:
+                    final_len = None if fin == -1 else max(fin - ps[b], 0)
+                f1 = max(dec_step + 1 - md - ps[b], 0)
+                if final_len is not None:
+                    f1 = final_len if over else min(f1, final_len)
+                complete[b] = final_len is not None and f1 == final_len
+                if f1 > emitted[b] or complete[b]:
+                    rows.append((b, emitted[b], f1, complete[b]))
+                    emitted[b] = f1
+            yield StreamUpdate(dec_step, rows)
 
     def finish(self):
         """reference model.py:1205-1231: lengths, packing of generated_codes."""
