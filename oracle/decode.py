@@ -16,13 +16,16 @@ Restates (reference = /root/reference/utils, read as text):
   generate (EOS countdown, delay padding, packing) UniMoE_Audio_model.py:1070-1231
   delay pattern helpers / DecoderOutput           UniMoE_Audio_utils.py:137-325
   _preprocess_codec                               UniMoE_Audio_mod.py:140-156
+and the product's own sampler (cfg_sample_kernel: counter hash, tie rule, inverse-CDF draw; mix64 .. draw below).
 The KV cache grows by concatenation per step like the reference's DynamicCache
 (UniMoE_Audio_model.py:353-354,1109) so that the timed CPU baseline pays what the reference pays.
 """
 from __future__ import annotations
 
+import types
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -204,6 +207,104 @@ def cfg_and_mask(cfg, logits_2B: torch.Tensor, cfg_scale: float, enable_eos: boo
         out[:, :, eos:] = NEG_INF
     out[:, 0, eos] *= eos_mul
     return out
+
+
+# ----------------------------------------------------------------------------- the device sampler (umoe_misc.hip cfg_sample_kernel)
+# The reference draws with torch.multinomial; the product draws u from a counter hash and inverts the CDF. These restate the
+# product's sampler: the hash bit for bit, the filters in float64 with its documented tie rule, the draw in the kernel's fp32 order.
+_M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def mix64(z):
+    """splitmix64 finaliser with 64-bit wrap-around; int or uint64 array in, same kind out."""
+    a = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        a = a + np.uint64(0x9E3779B97F4A7C15)
+        a = (a ^ (a >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        a = (a ^ (a >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        a = a ^ (a >> np.uint64(31))
+    return int(a) if a.ndim == 0 else a
+
+
+def sampler_u(seed: int, step: int, row):
+    """u of the row `row` (= b * C + c, the workgroup) at decode step `step`: float32((h >> 40) + 0.5) * 2^-24, rounded to float32
+    as the kernel does, so u == 1.0 is reachable."""
+    r = np.asarray(row, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    inner = (np.uint64(int(step) & 0xFFFFFFFF) << np.uint64(32)) | r
+    h = mix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.asarray(mix64(inner), dtype=np.uint64))
+    top = np.asarray(h, dtype=np.uint64) >> np.uint64(40)
+    u = (top.astype(np.float64) + 0.5).astype(np.float32) * np.float32(2.0 ** -24)
+    return u if u.ndim else np.float32(u)
+
+
+def _rank_desc(x: torch.Tensor) -> torch.Tensor:
+    """rank of every entry of each row in descending order, equal values by lower index first (+0.0 equals -0.0)"""
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices
+    return torch.empty_like(order).scatter_(-1, order, torch.arange(x.shape[-1]).expand_as(order).contiguous())
+
+
+def filter_probs(logits_2B: torch.Tensor, cfg_scale: float, temperature: float, top_p: float, top_k: Optional[int], eos: int,
+                 eos_mul: float, enable_eos: bool = True, details: bool = False):
+    """logits_2B [2B, C, V] -> the float64 probabilities [B*C, V] cfg_sample_kernel samples from: CFG mix and EOS masks
+    (cfg_and_mask), temperature, EOS killed unless it is the arg-max, top-k, top-p, softmax. Ties rank by lower index first, for
+    top-k and for the top-p order. top_k None or <= 0: no top-k.
+    details: also the top-k survivors [B*C, V] (the fast path's candidates, in index order) and, per row, the distance of the
+    nearest top-p prefix sum of a survivor from top_p (inf without top-p): the kernel's fp32 sums may decide those the other way."""
+    x = cfg_and_mask(types.SimpleNamespace(codec_eos_value=eos), logits_2B.to(torch.float64).clone(), cfg_scale, enable_eos, eos_mul)
+    V = x.shape[-1]
+    x = x.reshape(-1, V) / temperature
+    rows = torch.arange(x.shape[0])
+    top = torch.argmax(x, dim=-1)                                   # first maximum
+    x[rows[top != eos], eos] = NEG_INF
+    cand = torch.ones_like(x, dtype=torch.bool)
+    if top_k is not None and top_k > 0:
+        cand = _rank_desc(x) < top_k
+        x = x.masked_fill(~cand, NEG_INF)
+    gap = torch.full((x.shape[0],), float("inf"), dtype=torch.float64)
+    if top_p < 1.0:
+        pr = torch.softmax(x, dim=-1)
+        order = torch.sort(pr, dim=-1, descending=True, stable=True).indices
+        sp = pr.gather(-1, order)
+        before = torch.empty_like(pr).scatter_(-1, order, torch.cumsum(sp, -1) - sp)   # mass ranked strictly ahead
+        x = x.masked_fill(before > top_p, NEG_INF)
+        gap = (before - top_p).abs().masked_fill(~cand, float("inf")).amin(-1)
+    probs = torch.softmax(x, dim=-1)
+    return (probs, cand, gap) if details else probs
+
+
+def scan64(p) -> np.ndarray:
+    """The fast path's fp32 Hillis-Steele inclusive scan over its 64 candidate lanes (lanes past len(p) hold 0)."""
+    c = np.zeros(64, np.float32)
+    c[: len(p)] = np.asarray(p, np.float32)
+    o = 1
+    while o < 64:
+        c = np.concatenate([c[:o], c[o:] + c[:-o]])
+        o *= 2
+    return c[: len(p)]
+
+
+def draw(probs, u, path: str, lanes=None, margin: bool = False):
+    """Inverse-CDF draw of one row: the first index, in index order, with p > 0 and cumulative sum > u; else the last positive index.
+    path "slow": a sequential fp32 sum over all V entries; "fast": scan64 over the candidates `lanes` (indices in increasing order;
+    default: the positive entries). margin: also the distance of u from the nearest cumulative sum at a positive entry."""
+    p = np.asarray(probs, np.float32)
+    if path == "slow":
+        idx = np.arange(p.shape[0])
+        q = p
+        cum = np.add.accumulate(p, dtype=np.float32)               # sequential, like thread 0's loop
+    elif path == "fast":
+        idx = np.flatnonzero(p > 0) if lanes is None else np.asarray(lanes)
+        assert idx.size <= 64, idx.size
+        q = p[idx]
+        cum = scan64(q)
+    else:
+        raise ValueError(path)
+    pos = np.flatnonzero(q > 0)
+    hit = pos[cum[pos] > u]
+    pick = int(idx[hit[0]]) if hit.size else (int(idx[pos[-1]]) if pos.size else int(idx[0]) if idx.size else 0)
+    if margin:
+        return pick, float(np.abs(cum[pos].astype(np.float64) - float(u)).min()) if pos.size else float("inf")
+    return pick
 
 
 # ----------------------------------------------------------------------------- delay pattern

@@ -854,7 +854,7 @@ def test_cfg_sampler_vs_reference_goldens(dev):
     pred = ops.cfg_sample(two.to(dev), B, C, V, cfg_scale=0.0, temperature=0.0, top_p=1.0, top_k=45, eos=1024, eos_mul=1.0,
                           enable_eos=True, do_sample=False).cpu().reshape(-1)
     assert torch.equal(pred, torch.argmax(guided, -1))
-    for n in "abd":
+    for n in "abcd":
         T, tp, tk = g[f"params_{n}"].tolist()
         ref = OD.sample_next_token(guided.clone(), T, tp, None if tk < 0 else int(tk), 1024, return_probs=True)
         pred, probs = ops.cfg_sample(two.to(dev), B, C, V, cfg_scale=0.0, temperature=T, top_p=tp, top_k=None if tk < 0 else int(tk),

@@ -567,6 +567,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         __shared__ int n_cand;
         auto key_of = [](float f) -> unsigned {  // monotonic: larger float -> larger key
             unsigned u = __float_as_uint(f);
+            if (u == 0x80000000u) u = 0u;  // -0.0 keys as +0.0: equal values, ranked by index like the slow path
             return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
         };
         constexpr int PER = 8;  // contiguous indices per thread (V <= 2048)

@@ -371,12 +371,18 @@ def codec_embed_sum_bwd(tok: torch.Tensor, d_out: torch.Tensor, V: int) -> torch
 
 
 def cfg_sample(logits: torch.Tensor, B: int, Cc: int, V: int, *, cfg_scale, temperature, top_p, top_k, eos, eos_mul,
-               enable_eos=True, do_sample=True, seed=0, want_probs=False):
+               enable_eos=True, do_sample=True, seed=0, want_probs=False, step: Optional[torch.Tensor] = None,
+               min_tokens: Optional[int] = None):
+    """step: a device int32 scalar, the decode engine's step counter. Given, it replaces 0 in the hash, and EOS is enabled iff
+    min_tokens is None or *step >= min_tokens (enable_eos is then ignored), as in an engine step."""
     pred = torch.empty((B, Cc), dtype=torch.int64, device=logits.device)
     probs = torch.empty((B * Cc, V), dtype=torch.float32, device=logits.device) if want_probs else None
+    if step is not None:
+        assert step.dtype == torch.int32 and step.numel() == 1 and step.device == logits.device, "step: one device int32"
     a = L.SampleArgs(logits=_p(logits), B=B, C=Cc, V=V, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p,
-                     eos_mul=eos_mul, top_k=-1 if top_k is None else top_k, eos=eos, enable_eos=int(enable_eos), min_tokens=-1,
-                     step=None, do_sample=int(do_sample), seed=seed, pred=_p(pred), probs_out=_p(probs))
+                     eos_mul=eos_mul, top_k=-1 if top_k is None else top_k, eos=eos, enable_eos=int(enable_eos),
+                     min_tokens=-1 if min_tokens is None else int(min_tokens), step=None if step is None else _p(step),
+                     do_sample=int(do_sample), seed=seed, pred=_p(pred), probs_out=_p(probs))
     L.check(L.lib().umoe_codec_head_cfg_sample(C.byref(a), _stream()), "umoe_codec_head_cfg_sample")
     return (pred, probs) if want_probs else pred
 
