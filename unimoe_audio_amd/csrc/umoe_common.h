@@ -244,15 +244,12 @@ int umoe_moe_fused(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t*
 // The same two GEMMs as ONE workgroup per CU with a static, byte-balanced schedule (umoe_moe_flat.hip): `n_wg` workgroups (<= the
 // device's CU count: every workgroup must be resident), the riders are the first S of them.  `gu` / `dn` as for umoe_moe_fused (any
 // nt); `flags`: >= n_wg device words.  Returns 1 (nothing launched) when the shapes or n_wg do not allow a schedule.
-// `oproj` (optional): the o_proj + residual GEMM whose output rows ARE gu's raw rows (fused_router->x): it is computed inside the launch, half
-// a 16-feature tile per workgroup, handed over through `o_flags` (8 x 256 device words, monotonic epochs); K = D = 2048 only.
-int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s,
-                  const umoe_gemm_args* oproj = nullptr, uint32_t* o_flags = nullptr);
+int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s);
 bool umoe_moe_flat_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
 // The same launch on WP8 (fp8 e4m3) expert weights: the groups' `w` are WP8 blocks (include/umoe.h), e_gu / e_dn [num_groups] their
 // per-row exponents in the same group order.  Returns 1 (nothing launched) like umoe_moe_flat; the caller has no other fp8 path.
 int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const int8_t* const* e_gu, const int8_t* const* e_dn, uint32_t* flags,
-                      int flag_words, int n_wg, hipStream_t s, const umoe_gemm_args* oproj = nullptr, uint32_t* o_flags = nullptr);
+                      int flag_words, int n_wg, hipStream_t s);
 bool umoe_moe_flat_fp8_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
 
 // A small decode GEMM with row riders in front (umoe_gemm.hip wstream_gemm_rk, umoe_riders_dev.h; decode engine only).  kind 2: the

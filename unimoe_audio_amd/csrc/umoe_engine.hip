@@ -98,11 +98,6 @@ struct umoe_engine {
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
     int expert_fp8 = 0;          // the last dense decode layer ran the fp8 flat launch (umoe_engine_info "expert_fp8")
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
-    bool fuse_o = false;         // UMOE_FUSE_O=1: with the flat expert launch, o_proj + residual is computed INSIDE it (half a 16-feature tile per
-                                 // workgroup, handed over by flags; the first expert weight stage is requested inside the half tile): four
-                                 // launches per layer, bit-identical -- and 0.05 ms/step SLOWER in all three forms measured (3.170 / 3.064 /
-                                 // 3.069 vs 3.02 / 3.01 / 3.01 ms): the hand-off (publish, 2048-flag wait, row staging) costs the
-                                 // launch more than the o_proj launch it removes.  Off by default; kept selectable and parity-tested
     bool flat_moe = true;        // UMOE_FLAT_MOE: both expert GEMMs as ONE workgroup per CU with a byte-balanced static schedule
                                  // (umoe_moe_flat.hip); 0 / shapes that do not fit: the box-grid launch below
     bool fuse_moe = true;        // UMOE_FUSE_MOE: gate/up and down projections of a dense decode layer in ONE launch (umoe_moe_fused)
@@ -322,7 +317,9 @@ extern "C" int umoe_engine_create(const umoe_engine_cfg* cfg, umoe_engine** out)
         umoe_engine_destroy(e);
         return -2;
     }
-    // [0] decode steps taken, [1] sticky hand-off error, [16..32) row flags of the rider hand-off (umoe_gemm_args.rider_pub)
+    // [0] decode steps taken, [1] sticky hand-off error, [2] expert-parallel round, [64, 512) flags of the fused / flat expert launch,
+    // [1024, 1280) row flags of the rider hand-offs (umoe_gemm_args.rider_pub), [2048, 2688) flags of the expert-parallel flat launch;
+    // words from 2688 up are unused
     if (hipMalloc(&e->ep_words, 32768) != hipSuccess || hipMemset(e->ep_words, 0, 32768) != hipSuccess) {
         umoe_set_error("umoe_engine_create: hipMalloc failed (state words)");
         umoe_engine_destroy(e);
@@ -351,7 +348,6 @@ extern "C" int umoe_engine_create(const umoe_engine_cfg* cfg, umoe_engine** out)
     }
     if (const char* v = getenv("UMOE_FLAT_MOE")) e->flat_moe = atoi(v) != 0;
     if (const char* v = getenv("UMOE_EP_FLAT")) e->ep_flat = atoi(v) != 0;
-    if (const char* v = getenv("UMOE_FUSE_O")) e->fuse_o = atoi(v) != 0;
     if (const char* v = getenv("UMOE_DENSE_EXPERTS")) e->dense_experts = atoi(v) != 0;
     if (const char* v = getenv("UMOE_TILED_PREFILL")) e->tiled_prefill = atoi(v) != 0;
     if (const char* v = getenv("UMOE_FUSE_ROUTER")) e->fuse_router = atoi(v) != 0;
@@ -867,19 +863,6 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     o.groups = g + 1; o.groups_host = gh + 1; o.num_groups = 1; o.max_rows = n_tok; o.max_n_blocks = D / 16; o.max_k = HD;
     o.a = e->attn_out; o.lda = HD; o.resid = e->x; o.out = e->x1; o.ldo = D; o.n_valid = D;
     o.prologue = UMOE_PRO_PLAIN; o.epilogue = UMOE_EPI_BF16_RESID;
-    // decode with the flat expert launch: o_proj is computed INSIDE that launch (umoe_moe_flat with the o_proj arguments); the conditions are
-    // those under which the flat launch is taken below (the same flags and shapes; should it refuse after all, o_proj is launched there)
-    bool o_in_flat = false;
-    {
-        const char* fv = getenv("UMOE_FLAT_MOE");
-        const bool flat = fv ? atoi(fv) != 0 : e->flat_moe;
-        const bool densef = dense_mode(e, n_tok) && !e->ep_decode(n_tok);
-        const char* ov = getenv("UMOE_FUSE_O");      // (read per enqueue like UMOE_FLAT_MOE: A/B scripts toggle it between captures)
-        const bool fuse_o = ov ? atoi(ov) != 0 : e->fuse_o;
-        o_in_flat = fuse_o && flat && densef && T == 1 && !tiled && e->fuse_router && e->rider_pub && e->fuse_moe && e->n_cu > 0 && c.n_dyn == 9 && c.n_fix == 2 &&
-                    D == 2048 && HD == 2048 && n_tok <= 16 &&
-                    umoe_moe_flat_feasible(e->n_cu < 256 ? e->n_cu : 256, n_tok, D, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix);
-    }
     if (tiled) {
         umoe_tgroup_t tg{};
         tg.w = L.w.rm_o; tg.static_count = n_tok; tg.n = D; tg.k = HD; tg.ldw = HD;
@@ -887,14 +870,12 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
         ta.groups = &tg; ta.num_groups = 1; ta.max_rows = n_tok; ta.a = e->attn_out; ta.lda = HD; ta.resid = e->x; ta.out = e->x1;
         ta.ldo = D; ta.epilogue = UMOE_EPI_BF16_RESID;
         rc = umoe_tiled_gemm(&ta, s);
-    } else if (!o_in_flat) {
-        rc = umoe_grouped_gemm(&o, s);
     } else {
-        rc = 0;
+        rc = umoe_grouped_gemm(&o, s);
     }
     if (rc) return rc;
-    if (!o_in_flat) PROF(K_OPROJ);
-    if (e->probe_x1 && n_tok == c.rows && !o_in_flat)
+    PROF(K_OPROJ);
+    if (e->probe_x1 && n_tok == c.rows)
         UMOE_HIP(hipMemcpyAsync(e->probe_x1 + (size_t)l * c.rows * D, e->x1, (size_t)c.rows * D * 2, hipMemcpyDeviceToDevice, s));
     if (e->ep_decode(n_tok)) return run_moe_ep(e, l, n_tok, s);
     // 5. RMSNorm + router                                         model.py:240, core.py:246-291
@@ -922,10 +903,6 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     const bool flat_ok = dense && e->flat_moe && e->fuse_moe && e->n_cu > 0 && c.n_dyn == 9 && c.n_fix == 2 &&
                          umoe_moe_flat_feasible(e->n_cu < 256 ? e->n_cu : 256, n_tok, D, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix);
     const bool pub_riders = fuse_router && e->rider_pub && (box_fits || flat_ok);
-    if (o_in_flat && !(pub_riders && e->fuse_moe && flat_ok)) {      // (cannot happen with the conditions above; never run a layer without its o_proj)
-        if ((rc = umoe_grouped_gemm(&o, s))) return rc;
-        o_in_flat = false;
-    }
     if (pub_riders) {
         rc = 0;                  // no launch here: the riders write h2 inside the gate/up launch and hand it over (ra.h_out stays h2)
     } else if (fuse_router) {
@@ -1024,20 +1001,15 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
                 }
                 umoe_gemm_args gu8 = gu, dn8 = dn;
                 gu8.groups_host = g8u; dn8.groups_host = g8d;
-                rc = umoe_moe_flat_fp8(&gu8, &dn8, e8u, e8d, e->ep_words + 64, 512 - 64, n_wg, s, o_in_flat ? &o : nullptr, e->ep_words + 2688);
+                rc = umoe_moe_flat_fp8(&gu8, &dn8, e8u, e8d, e->ep_words + 64, 512 - 64, n_wg, s);
                 UMOE_REQUIRE(rc != 1, "umoe_engine: the fp8 flat expert launch has no schedule for this shape on %d workgroups (layer %d)", n_wg, l);
                 if (rc) return rc;
                 e->expert_launch = 2;
                 e->expert_fp8 = 1;
             } else {
-            if (flat && n_wg > 0) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s, o_in_flat ? &o : nullptr, e->ep_words + 2688);
-            e->expert_launch = rc == 0 ? 2 : 0;
-            e->expert_fp8 = 0;
-            }
-            if (rc == 1 && o_in_flat) {      // the flat launch refused after all: o_proj as its own launch in front of whatever runs instead
-                if ((rc = umoe_grouped_gemm(&o, s))) return rc;
-                rc = 1;
-                o_in_flat = false;
+                if (flat && n_wg > 0) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);
+                e->expert_launch = rc == 0 ? 2 : 0;
+                e->expert_fp8 = 0;
             }
         }
         if (rc == 1 && box_fits) {
@@ -1050,8 +1022,6 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             rc = umoe_grouped_gemm(&dn, s);
         }
         if (rc) return rc;
-        if (o_in_flat && e->probe_x1 && n_tok == c.rows)      // (x1 was made inside the launch)
-            UMOE_HIP(hipMemcpyAsync(e->probe_x1 + (size_t)l * c.rows * D, e->x1, (size_t)c.rows * D * 2, hipMemcpyDeviceToDevice, s));
         PROF(K_GATEUP);          // (the fused launch is booked as gate/up: zero down launches tell the reader which form ran)
     } else {
         rc = umoe_grouped_gemm(&dn, s);

@@ -29,7 +29,9 @@
 
 #define FLAT_RIDER_LDS 512      // bytes of LDS behind the GEMM area for the riders' partial sums (router4_body: 4 + 4 * 16 floats)
 
-__global__ __launch_bounds__(512, 1) void moe_flat_kernel(const flat_args A, const umoe_router_args ra, const umoe_rider_pub pub, const int lds_gemm, const flat_o O) {
+// The body of both kernels below.  F8: WP8 blocks + per-row exponents *F (flat_gateup / flat_down with F8); F = nullptr for bf16 weights.
+template <bool F8>
+__device__ __forceinline__ void moe_flat_body(const flat_args& A, const umoe_router_args& ra, const umoe_rider_pub& pub, const int lds_gemm, const flat_f8* F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned b = blockIdx.x;
     const unsigned eg = A.gu[b], ed = A.dn[b];
@@ -42,15 +44,7 @@ __global__ __launch_bounds__(512, 1) void moe_flat_kernel(const flat_args A, con
     }
 #endif
     const int token = (int)(eg >> 16) - 1;
-    const bool oph = O.half > 0;            // o_proj inside this launch (kernel argument: a scalar branch)
     if (token >= 0) {
-        // (the router reads the raw rows: with o_proj inside the launch the rider takes its half tile and the wait first, no prefetch behind it)
-        if (oph) {
-            const flat_u32x4* const nowp[1] = {nullptr};
-            flat_u32x4 now0[1];
-            flat_oproj_half<1, false>(O, pub, b, smem, (int)threadIdx.x, nowp, now0, 0);
-            flat_oproj_wait(O, pub, b, (int)threadIdx.x);
-        }
         // rider: the Top-P router of row `token` (its own RMSNorm + gate GEMV on waves 0..3, then wave 0 alone walks the serial chain while
         // the other waves go on to the GEMM).  Nobody in this launch waits for it: its tables feed the combine of a LATER launch.
         // Waves 4..7 only keep the two barriers of router4_body company.
@@ -67,13 +61,11 @@ __global__ __launch_bounds__(512, 1) void moe_flat_kernel(const flat_args A, con
         }
     }
     const int fp0 = (int)(eg & 2047u), np = (int)((eg >> 11) & 7u);
-    if (oph && token >= 0) __syncthreads();      // (the half tile's reduction slab is the staging area of the rows)
-    const int ophm = oph ? (token >= 0 ? 2 : 1) : 0;
     switch (np) {
-        case 4: flat_gateup<4>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O); break;
-        case 5: flat_gateup<5>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O); break;
-        case 6: flat_gateup<6>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O); break;
-        case 7: flat_gateup<7>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O); break;
+        case 4: flat_gateup<4, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
+        case 5: flat_gateup<5, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
+        case 6: flat_gateup<6, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
+        case 7: flat_gateup<7, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
         default: break;
     }
     for (int sl = 0; sl < FLAT_SLICES; ++sl) {
@@ -83,25 +75,25 @@ __global__ __launch_bounds__(512, 1) void moe_flat_kernel(const flat_args A, con
         __syncthreads();     // (the reduction slab of the previous GEMM is the staging area of this one)
         if (A.dn_kb[grp] & 1) {
             switch (nd) {
-                case 1: flat_down<1, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 2: flat_down<2, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 3: flat_down<3, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 4: flat_down<4, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 5: flat_down<5, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 6: flat_down<6, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 7: flat_down<7, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 8: flat_down<8, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 9: flat_down<9, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                default: flat_down<10, 1>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
+                case 1: flat_down<1, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 2: flat_down<2, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 3: flat_down<3, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 4: flat_down<4, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 5: flat_down<5, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 6: flat_down<6, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 7: flat_down<7, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 8: flat_down<8, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 9: flat_down<9, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                default: flat_down<10, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
             }
         } else {
             switch (nd) {
-                case 1: flat_down<1, 2>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 2: flat_down<2, 2>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 3: flat_down<3, 2>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 4: flat_down<4, 2>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                case 5: flat_down<5, 2>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
-                default: flat_down<6, 2>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x); break;
+                case 1: flat_down<1, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 2: flat_down<2, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 3: flat_down<3, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 4: flat_down<4, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 5: flat_down<5, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                default: flat_down<6, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
             }
         }
     }
@@ -114,93 +106,14 @@ __global__ __launch_bounds__(512, 1) void moe_flat_kernel(const flat_args A, con
 #endif
 }
 
-// The same launch on FP8 (OCP e4m3) expert weights: WP8 blocks + per-row exponents F (flat_gateup / flat_down with F8).  A kernel of
-// its own name, so that traces tell the two apart, and a copy of the body above rather than a shared template: moe_flat_kernel must
-// compile to the same code as before (a body shared through one more inline level changed its scalar register allocation).
+__global__ __launch_bounds__(512, 1) void moe_flat_kernel(const flat_args A, const umoe_router_args ra, const umoe_rider_pub pub, const int lds_gemm) {
+    moe_flat_body<false>(A, ra, pub, lds_gemm, nullptr);
+}
+
+// The same launch on FP8 (OCP e4m3) expert weights: a kernel of its own name, so that traces tell the two apart.
 __global__ __launch_bounds__(512, 1) void moe_flat_fp8_kernel(const flat_args A, const umoe_router_args ra, const umoe_rider_pub pub, const int lds_gemm,
-                                                              const flat_o O, const flat_f8 F) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned b = blockIdx.x;
-    const unsigned eg = A.gu[b], ed = A.dn[b];
-    flat_stamps st;
-#ifdef UMOE_TIMELINE
-    if (A.dbg) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) st.t[k] = 0;
-        st.t[0] = wall_clock64();
-    }
-#endif
-    const int token = (int)(eg >> 16) - 1;
-    const bool oph = O.half > 0;            // o_proj inside this launch (kernel argument: a scalar branch)
-    if (token >= 0) {
-        // (the router reads the raw rows: with o_proj inside the launch the rider takes its half tile and the wait first, no prefetch behind it)
-        if (oph) {
-            const flat_u32x4* const nowp[1] = {nullptr};
-            flat_u32x4 now0[1];
-            flat_oproj_half<1, false>(O, pub, b, smem, (int)threadIdx.x, nowp, now0, 0);
-            flat_oproj_wait(O, pub, b, (int)threadIdx.x);
-        }
-        // rider: the Top-P router of row `token` (its own RMSNorm + gate GEMV on waves 0..3, then wave 0 alone walks the serial chain while
-        // the other waves go on to the GEMM).  Nobody in this launch waits for it: its tables feed the combine of a LATER launch.
-        // Waves 4..7 only keep the two barriers of router4_body company.
-        float* rl = reinterpret_cast<float*>(smem + lds_gemm);
-        if (threadIdx.x < 256) {
-#ifdef UMOE_TIMELINE
-            TL_ENTER(5);
-#endif
-            if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, token, threadIdx.x, rl TL_PASS, nullptr, 0u, nullptr);
-            else router4_body<9, 2, 0, false>(ra, token, threadIdx.x, rl TL_PASS, nullptr, 0u, nullptr);
-        } else {
-            __syncthreads();
-            __syncthreads();
-        }
-    }
-    const int fp0 = (int)(eg & 2047u), np = (int)((eg >> 11) & 7u);
-    if (oph && token >= 0) __syncthreads();      // (the half tile's reduction slab is the staging area of the rows)
-    const int ophm = oph ? (token >= 0 ? 2 : 1) : 0;
-    switch (np) {
-        case 4: flat_gateup<4, true, true>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O, &F); break;
-        case 5: flat_gateup<5, true, true>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O, &F); break;
-        case 6: flat_gateup<6, true, true>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O, &F); break;
-        case 7: flat_gateup<7, true, true>(A, pub, fp0, b, smem, st, (int)threadIdx.x, ophm, O, &F); break;
-        default: break;
-    }
-    for (int sl = 0; sl < FLAT_SLICES; ++sl) {
-        const unsigned e16 = (ed >> (16 * sl)) & 0xffffu;
-        const int nd = (int)(e16 >> 12), grp = (int)(e16 & 15u), nb0 = (int)((e16 >> 4) & 255u);
-        if (nd == 0) break;
-        __syncthreads();     // (the reduction slab of the previous GEMM is the staging area of this one)
-        if (A.dn_kb[grp] & 1) {
-            switch (nd) {
-                case 1: flat_down<1, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 2: flat_down<2, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 3: flat_down<3, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 4: flat_down<4, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 5: flat_down<5, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 6: flat_down<6, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 7: flat_down<7, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 8: flat_down<8, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 9: flat_down<9, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                default: flat_down<10, 1, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-            }
-        } else {
-            switch (nd) {
-                case 1: flat_down<1, 2, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 2: flat_down<2, 2, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 3: flat_down<3, 2, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 4: flat_down<4, 2, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                case 5: flat_down<5, 2, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-                default: flat_down<6, 2, true>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, &F); break;
-            }
-        }
-    }
-#ifdef UMOE_TIMELINE
-    if (A.dbg && threadIdx.x == 0) {
-        st.t[15] = wall_clock64();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) A.dbg[(size_t)b * 16 + k] = st.t[k];
-    }
-#endif
+                                                              const flat_f8 F) {
+    moe_flat_body<true>(A, ra, pub, lds_gemm, &F);
 }
 
 // ------------------------------------------------------------------------------------ host: the static schedule
@@ -387,7 +300,7 @@ static void flat_knobs(FlatShape& sh) {
 // Returns 0 (launched), 1 (shapes / CU count do not allow it: nothing launched), < 0 error.  `f8` (umoe_moe_flat_fp8): the groups' weight
 // pointers are WP8 blocks, f8 holds their exponents in the same group order.
 static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s,
-                           const umoe_gemm_args* oproj, uint32_t* o_flags, const flat_f8* f8) {
+                           const flat_f8* f8) {
     UMOE_REQUIRE(gu && dn && flags, "umoe_moe_flat: null argument");
     const int G = gu->num_groups;
     if (!(gu->fused_router && gu->rider_pub && gu->groups_host && dn->groups_host && G == dn->num_groups && G <= FLAT_MAXG && gu->prologue == UMOE_PRO_PLAIN &&
@@ -456,21 +369,6 @@ static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, u
         kb_dn_max = std::max(kb_dn_max, sh.dn_kb[i]);
     }
     for (int i = G; i <= FLAT_MAXG; ++i) A.pair0[i] = P;
-    flat_o O;
-    memset(&O, 0, sizeof(O));
-    if (oproj) {
-        // o_proj + residual inside the launch: its output rows are this launch's raw rows
-        if (!(o_flags && oproj->groups_host && oproj->num_groups == 1 && oproj->epilogue == UMOE_EPI_BF16_RESID && oproj->prologue == UMOE_PRO_PLAIN &&
-              oproj->ksplit <= 1 && oproj->resid && oproj->a && oproj->out == (void*)r->x && oproj->ldo == r->D && oproj->max_rows == r->S && r->D == 2048 &&
-              (oproj->lda & 7) == 0))
-            return 1;
-        const umoe_group_t& og = oproj->groups_host[0];
-        if (og.rows || og.count || og.row_off || og.a_row_base || og.a_col_off || og.out_row_base || og.bias || og.static_count != r->S || og.k != 2048 ||
-            og.n_blocks * 16 != r->D || 2 * og.n_blocks > 256)
-            return 1;
-        O.rows = oproj->a; O.lda_rows = oproj->lda; O.w = og.w; O.resid = oproj->resid; O.flags = o_flags;
-        O.x1 = reinterpret_cast<uint16_t*>(oproj->out); O.lda = r->D; O.S = r->S; O.half = 2 * og.n_blocks; O.n_wg = n_wg;
-    }
     memcpy(A.gu, pl.gu, sizeof(uint32_t) * n_wg);
     memcpy(A.dn, pl.dn, sizeof(uint32_t) * n_wg);
     const umoe_rider_pub pub = *reinterpret_cast<const umoe_rider_pub*>(gu->rider_pub);
@@ -488,19 +386,18 @@ static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, u
     }
     umoe_router_args rr = *r;
     rr.h_out = nullptr;          // nobody reads normalised rows from memory: every workgroup makes its own copy in LDS
-    if (f8) moe_flat_fp8_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds, O, *f8);
-    else moe_flat_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds, O);
+    if (f8) moe_flat_fp8_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds, *f8);
+    else moe_flat_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds);
     UMOE_LAUNCH_CHECK();
     return 0;
 }
 
-int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s,
-                  const umoe_gemm_args* oproj, uint32_t* o_flags) {
-    return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, oproj, o_flags, nullptr);
+int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s) {
+    return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, nullptr);
 }
 
 int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const int8_t* const* e_gu, const int8_t* const* e_dn, uint32_t* flags,
-                      int flag_words, int n_wg, hipStream_t s, const umoe_gemm_args* oproj, uint32_t* o_flags) {
+                      int flag_words, int n_wg, hipStream_t s) {
     UMOE_REQUIRE(e_gu && e_dn && gu && dn && gu->num_groups <= FLAT_MAXG, "umoe_moe_flat_fp8: bad argument");
     flat_f8 F;
     memset(&F, 0, sizeof(F));
@@ -508,7 +405,7 @@ int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const 
         UMOE_REQUIRE(e_gu[i] && e_dn[i], "umoe_moe_flat_fp8: group %d has no exponents", i);
         F.e_gu[i] = e_gu[i]; F.e_dn[i] = e_dn[i];
     }
-    return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, oproj, o_flags, &F);
+    return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, &F);
 }
 
 // Does a schedule exist for this decode shape on n_wg workgroups?  (the engine asks before it drops the RMSNorm launch)
