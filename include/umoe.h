@@ -489,7 +489,13 @@ int umoe_attn_softmax_bwd(const uint16_t* p, const uint16_t* dp, int ld, int hea
                           umoe_stream_t stream);
 /* backward of umoe_attn_prefill_fwd over full sequences (nq == T queries per row, one per key position; keys
  * [kv_start[row], t] visible to query t): dq [rows*T][H*hd], dk / dv in cache layout (positions [0, T) written).
- * "Unfused" first version: scores are materialised per (row, kv head) group in the workspace. */
+ * "Unfused" first version: scores are materialised per (row, kv head) group in the workspace (up to 16 heads per kv head).
+ * Pinned by tests/test_gpu_attn_train.py: every dq row and dk / dv positions [0, T) are written, slots [T, Lmax) are not
+ * touched; the dq rows of queries that see no key (t < kv_start) and the dk / dv rows below kv_start are exactly zero; the
+ * visible outputs do not depend on what the masked slots (K / V below kv_start, q / d_out rows of padded queries) hold,
+ * PROVIDED those values are finite: the kernels stage the 64-key step that holds kv_start whole and give its masked keys a
+ * zero probability, and 0 x NaN in the matrix core is NaN (umoe_qkv_mrope_kvappend writes every slot of [0, T), so both
+ * callers keep this).  Two calls on the same inputs give the same bits. */
 typedef struct {
     const uint16_t* q;             /* [rows*T][H*hd] rotated queries (umoe_qkv_mrope_kvappend q_out) */
     const uint16_t* k_cache;       /* [rows][KVH][Lmax][hd] */
@@ -538,7 +544,9 @@ typedef struct {
     const int32_t* pos3;      /* [3][rows] */
     int sec0, sec1, sec2;
     float* lse_out;           /* optional (umoe_attn_prefill_fwd, MFMA path): log-sum-exp per (query, head) [rows*nq][H], +inf for
-                               * queries that see no key; kept for umoe_attn_prefill_bwd */
+                               * queries that see no key (their out row is exactly zero); kept for umoe_attn_prefill_bwd.
+                               * MFMA path: slots below kv_start inside the 64-slot step that holds it are loaded and must be
+                               * finite; slots behind q_pos0 + nq - 1 are never read */
 } umoe_attn_args;
 int umoe_attn_decode(const umoe_attn_args* a, umoe_stream_t stream);
 /* causal prefill (nq = T queries per row) over keys already appended by umoe_qkv_mrope_kvappend */

@@ -1170,7 +1170,7 @@ extern "C" int umoe_attn_prefill_bwd(const umoe_attn_bwd_args* a, umoe_stream_t 
         const int rcf = umoe_attn_bwd_fused(a, stream);   // flash-style path when the forward's output and log-sum-exp are given
         if (rcf <= 0) return rcf;
     }
-    UMOE_REQUIRE(a->KVH > 0 && a->H % a->KVH == 0 && a->H / a->KVH <= 12 && a->hd % 8 == 0 && a->T > 0 && a->T <= a->Lmax && a->rows > 0,
+    UMOE_REQUIRE(a->KVH > 0 && a->H % a->KVH == 0 && a->H / a->KVH <= 16 && a->hd % 8 == 0 && a->T > 0 && a->T <= a->Lmax && a->rows > 0,
                  "umoe_attn_prefill_bwd: bad sizes (H=%d KVH=%d hd=%d T=%d Lmax=%d)", a->H, a->KVH, a->hd, a->T, a->Lmax);
     float* sc;
     uint16_t *P, *dP, *dS, *qsT, *dosT, *kT, *dST, *PT;
@@ -1183,7 +1183,17 @@ extern "C" int umoe_attn_prefill_bwd(const umoe_attn_bwd_args* a, umoe_stream_t 
     UMOE_HIP(hipMemsetAsync(dP, 0, (size_t)G * Tp * Tp * 2, s));
     UMOE_HIP(hipMemsetAsync(dS, 0, (size_t)G * Tp * Tp * 2, s));
     int rc;
-    umoe_tgroup_t tg[12];
+    umoe_tgroup_t tg[16];
+    // one group per query head; umoe_tiled_gemm takes 12 groups per launch, so 13 .. 16 heads per kv head go in two launches
+    auto per_head_gemm = [&](umoe_tgemm_args& ta) {
+        for (int j0 = 0; j0 < G; j0 += 12) {
+            ta.groups = tg + j0;
+            ta.num_groups = G - j0 < 12 ? G - j0 : 12;
+            const int r = umoe_tiled_gemm(&ta, stream);
+            if (r) return r;
+        }
+        return 0;
+    };
     for (int b = 0; b < a->rows; ++b)
         for (int g = 0; g < a->KVH; ++g) {
             const uint16_t* K_ = a->k_cache + (((size_t)b * a->KVH + g) * a->Lmax) * hd;
@@ -1198,12 +1208,12 @@ extern "C" int umoe_attn_prefill_bwd(const umoe_attn_bwd_args* a, umoe_stream_t 
             }
             umoe_tgemm_args ta{};
             ta.groups = tg; ta.num_groups = G; ta.max_rows = T; ta.a = a->q; ta.lda = HD; ta.out = sc; ta.ldo = Tp; ta.epilogue = UMOE_EPI_F32_RAW;
-            if ((rc = umoe_tiled_gemm(&ta, stream))) return rc;
+            if ((rc = per_head_gemm(ta))) return rc;
             if ((rc = umoe_attn_softmax_fwd(sc, Tp, G, T, Tp, a->kv_start_host[b], a->scale, P, Tp, stream))) return rc;
             // dP_h = dO_h V^T
             for (int j = 0; j < G; ++j) tg[j].w = V_;
             ta.a = a->d_out; ta.out = dP; ta.epilogue = UMOE_EPI_BF16;
-            if ((rc = umoe_tiled_gemm(&ta, stream))) return rc;
+            if ((rc = per_head_gemm(ta))) return rc;
             if ((rc = umoe_attn_softmax_bwd(P, dP, Tp, G, T, Tp, a->scale, dS, stream))) return rc;
             // dQ_h = dS_h K
             if ((rc = umoe_transpose_slots(K_, hd, hd, nullptr, nullptr, nullptr, 1, T, kT, Tp, stream))) return rc;
@@ -1214,7 +1224,7 @@ extern "C" int umoe_attn_prefill_bwd(const umoe_attn_bwd_args* a, umoe_stream_t 
             }
             ta = umoe_tgemm_args{};
             ta.groups = tg; ta.num_groups = G; ta.max_rows = T; ta.a = dS; ta.lda = Tp; ta.out = a->dq; ta.ldo = HD; ta.epilogue = UMOE_EPI_BF16;
-            if ((rc = umoe_tiled_gemm(&ta, stream))) return rc;
+            if ((rc = per_head_gemm(ta))) return rc;
             // stacked contractions over (head, query): dK = [dS_h]^T [Q_h], dV = [P_h]^T [dO_h]
             for (int j = 0; j < G; ++j) {
                 const size_t off = (size_t)b * T * HD + (size_t)(g * G + j) * hd;
