@@ -1,6 +1,8 @@
 """CLI mirror of the reference's examples/inference.py (flags --task/-t --input/-i --ref-audio/-ra --ref-text/-rt
---video/-v --output/-o --model/-m --device/-d --no-reuse; exit code 0/1, reference examples/inference.py:152-235)."""
+--video/-v --output/-o --model/-m --device/-d --no-reuse; exit code 0/1, reference examples/inference.py:152-235).
+--requests FILE.json (not in the reference): speech and music requests with their own settings in ONE decode batch."""
 import argparse
+import json
 import os
 import sys
 
@@ -29,6 +31,42 @@ def inference(task, input_text, model_path, ref_audio=None, ref_text=None, video
         return None
 
 
+def load_requests(path):
+    """FILE.json: a list of objects, {"task": "text_to_speech", "transcription": ..., "prompt_transcription": ..., "prompt_wav": ...}
+    or {"task": "text_to_music", "caption": ...}, each with any further field of SpeechRequest / MusicRequest (max_audio_seconds,
+    temperature, cfg_scale, seed, ...)"""
+    from unimoe_audio_amd.api import MusicRequest, SpeechRequest
+    kinds = {"text_to_speech": SpeechRequest, "text_to_music": MusicRequest}
+    reqs = []
+    for i, item in enumerate(json.load(open(path))):
+        item = dict(item)
+        task = item.pop("task", None)
+        if task not in kinds:
+            raise ValueError(f"{path}: request {i}: task must be one of {sorted(kinds)}")
+        reqs.append(kinds[task](**item))
+    return reqs
+
+
+def batch_inference(requests_file, model_path, output="./output", device=0, reuse=True, expert_weights="bf16", stream=False):
+    global _MODEL
+    from unimoe_audio_amd.api import UniMoEAudio
+    try:
+        reqs = load_requests(requests_file)
+        if _MODEL is None or not reuse:
+            _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights)
+        if not stream:
+            return _MODEL.generate_batch(reqs, output_dir=output)
+        import time
+        t0 = time.perf_counter()
+        for ch in _MODEL.generate_batch(reqs, output_dir=output, stream=True):
+            print(f"{time.perf_counter() - t0:8.3f} s  request {ch.row}  samples {ch.start_sample}..{ch.start_sample + ch.pcm.numel()}"
+                  f"{'  (last)' if ch.final else ''}", flush=True)
+        return [os.path.join(output, f"generated_{r.save_name}_{i}.wav") for i, r in enumerate(reqs)]
+    except Exception as e:
+        print(f"inference failed: {e}")
+        return None
+
+
 def _stream(m, task, input_text, ref_audio, ref_text, video, output):
     """the *_stream twins: print when each chunk arrives, then the same wav files as the non-streaming methods"""
     import time
@@ -52,8 +90,10 @@ def _stream(m, task, input_text, ref_audio, ref_text, video, output):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--task", "-t", required=True, choices=["text_to_speech", "text_to_music", "video_text_to_music"])
-    ap.add_argument("--input", "-i", required=True)
+    ap.add_argument("--task", "-t", choices=["text_to_speech", "text_to_music", "video_text_to_music"])
+    ap.add_argument("--input", "-i")
+    ap.add_argument("--requests", help="a JSON list of text_to_speech / text_to_music requests, each with its own settings, decoded as "
+                                       "one batch (UniMoEAudio.generate_batch); replaces --task / --input")
     ap.add_argument("--ref-audio", "-ra")
     ap.add_argument("--ref-text", "-rt")
     ap.add_argument("--video", "-v")
@@ -65,6 +105,11 @@ def main():
                     help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step)")
     ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
     a = ap.parse_args()
+    if a.requests:
+        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream)
+        sys.exit(0 if out else 1)
+    if not a.task or a.input is None:
+        ap.error("--task and --input are required (or --requests FILE.json)")
     out = inference(a.task, a.input, a.model, a.ref_audio, a.ref_text, a.video, a.output, a.device, not a.no_reuse, a.expert_weights,
                     a.stream)
     sys.exit(0 if out else 1)

@@ -567,6 +567,19 @@ int umoe_codec_embed_sum_bwd(const int32_t* tok, const uint16_t* d_out, int rows
  * logits [2B][C*V] fp32 (row 2b = uncond, 2b+1 = cond).  temperature 0 or do_sample 0 => arg-max.
  * probs_out optional [B*C][V] (post-filter probabilities, for parity).  rng: Philox-free counter
  * hash seeded by (seed, step, row). */
+/* Per-request settings of one batch entry b (a CFG pair): a table of B of them in DEVICE memory replaces the scalar members of the
+ * same names in umoe_sample_args / umoe_decode_io (and the one max_tokens of umoe_delay_step) when `row_params` is set there.  The
+ * kernels read the table at every launch, so a captured step graph records the POINTER: the values may be rewritten between
+ * requests.  8-byte aligned. */
+typedef struct {
+    float cfg_scale, temperature, top_p, eos_mul;
+    int32_t top_k;        /* <= 0: none */
+    int32_t do_sample;
+    int32_t min_tokens;   /* -1 = None */
+    int32_t max_tokens;   /* this row's max_tokens (delay step only) */
+    uint64_t seed;
+} umoe_row_params;
+
 typedef struct {
     const float* logits;
     int B, C, V;
@@ -580,6 +593,9 @@ typedef struct {
     uint64_t seed;
     int64_t* pred;            /* [B][C] */
     float* probs_out;
+    const umoe_row_params* row_params; /* device [B] or NULL.  Set: workgroup (b, c) takes cfg_scale, temperature, top_p, eos_mul, top_k,
+                                        * do_sample, min_tokens and seed from row_params[b]; the draw of row (b, c) stays
+                                        * u(seed, step, b * C + c), what it is in a launch whose one seed is row_params[b].seed */
 } umoe_sample_args;
 int umoe_codec_head_cfg_sample(const umoe_sample_args* a, umoe_stream_t stream);
 
@@ -590,6 +606,11 @@ int umoe_codec_head_cfg_sample(const umoe_sample_args* a, umoe_stream_t stream);
  * step0 (dec_step of the first decode call), 3 reserved}. */
 int umoe_delay_step(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C, int Tmax,
                     int eos, int pad, int max_delay, umoe_stream_t stream);
+/* the same with per-row lengths: row b is forced to end at cur >= row_params[b].max_tokens - max_delay (device table [B]; NULL = the
+ * one max_tokens of the state, i.e. umoe_delay_step).  The loop bound state[4B + 1] stays one number: the host sets it to the
+ * largest row value. */
+int umoe_delay_step_rows(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C, int Tmax,
+                         int eos, int pad, int max_delay, const umoe_row_params* row_params, umoe_stream_t stream);
 
 /* Per-channel codec cross-entropy of the training loss (model.py:830-847) on already shifted logits [N][C][V] fp32 and
  * labels [N][C] int64 (-100 = ignore): ch_loss[c] = mean nll over valid labels, total = ch_loss[0] + sum of channels with
@@ -739,6 +760,8 @@ typedef struct {
     float cfg_scale, temperature, top_p, eos_mul;
     int top_k, do_sample, min_tokens;
     uint64_t seed;
+    const umoe_row_params* row_params; /* device [rows / 2] or NULL (= the scalar members above): per-request sampling settings and
+                                        * max_tokens, handed to the sampler and the delay step of every step */
 } umoe_decode_io;
 int umoe_engine_decode_step(umoe_engine* e, const umoe_decode_io* io, umoe_stream_t stream);
 /* graph capture of one decode step; replays read all step-dependent scalars from device memory */

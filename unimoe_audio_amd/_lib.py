@@ -104,10 +104,18 @@ class AttnArgs(C.Structure):
                 ("sec0", i32), ("sec1", i32), ("sec2", i32), ("lse_out", vp)]
 
 
+class RowParams(C.Structure):
+    """umoe_row_params: the settings of one batch entry; tables of them are packed by unimoe_audio_amd/row_params.py (numpy dtype of the
+    same layout) and live in device memory"""
+    _fields_ = [("cfg_scale", f32), ("temperature", f32), ("top_p", f32), ("eos_mul", f32), ("top_k", C.c_int32), ("do_sample", C.c_int32),
+                ("min_tokens", C.c_int32), ("max_tokens", C.c_int32), ("seed", u64)]
+
+
 class SampleArgs(C.Structure):
     _fields_ = [("logits", vp), ("B", i32), ("C", i32), ("V", i32), ("cfg_scale", f32), ("temperature", f32),
                 ("top_p", f32), ("eos_mul", f32), ("top_k", i32), ("eos", i32), ("enable_eos", i32),
-                ("min_tokens", i32), ("step", vp), ("do_sample", i32), ("seed", u64), ("pred", vp), ("probs_out", vp)]
+                ("min_tokens", i32), ("step", vp), ("do_sample", i32), ("seed", u64), ("pred", vp), ("probs_out", vp),
+                ("row_params", vp)]
 
 
 class EngineCfg(C.Structure):
@@ -129,7 +137,7 @@ class LayerWeights(C.Structure):
 
 class DecodeIO(C.Structure):
     _fields_ = [("tokens", vp), ("state", vp), ("cfg_scale", f32), ("temperature", f32), ("top_p", f32),
-                ("eos_mul", f32), ("top_k", i32), ("do_sample", i32), ("min_tokens", i32), ("seed", u64)]
+                ("eos_mul", f32), ("top_k", i32), ("do_sample", i32), ("min_tokens", i32), ("seed", u64), ("row_params", vp)]
 
 
 EXPORTS = [
@@ -146,7 +154,7 @@ EXPORTS = [
     "umoe_ep_unique_id", "umoe_ep_comm_create", "umoe_ep_comm_destroy", "umoe_ep_all_to_all",
     "umoe_ep_ipc_export", "umoe_ep_ipc_open", "umoe_ep_ipc_close", "umoe_engine_ep_region", "umoe_engine_ep_connect",
     "umoe_engine_ep_error", "umoe_token_drop", "umoe_router_bwd_drop", "umoe_router_bwd_ex", "umoe_dac_conv1d", "umoe_dac_conv_transpose1d", "umoe_dac_resample", "umoe_vision_rope", "umoe_vision_attn", "umoe_swiglu_pair", "umoe_gelu", "umoe_engine_prefill_pos", "umoe_engine_set_probe", "umoe_engine_info", "umoe_engine_prefill_external", "umoe_engine_set_layer_fp8", "umoe_fp8_convert_probe",
-    "umoe_dac_conv1d_win", "umoe_dac_conv_transpose1d_win", "umoe_rvq_from_delayed",
+    "umoe_dac_conv1d_win", "umoe_dac_conv_transpose1d_win", "umoe_rvq_from_delayed", "umoe_delay_step_rows",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -161,6 +169,7 @@ def _mirrors():
 
 
 STRUCT_MIRRORS = _mirrors()          # C struct name -> ctypes mirror (tests/test_abi_cpu.py compares offsets field by field)
+TABLE_MIRRORS = {"umoe_row_params": RowParams}     # device-table records (tests/test_row_params_cpu.py); size-checked at load like the above
 
 
 def lib():
@@ -250,6 +259,9 @@ def lib():
         L.umoe_mul_noise.argtypes = [vp, vp, C.c_long, vp, vp]
         L.umoe_codec_head_cfg_sample.argtypes = [C.POINTER(SampleArgs), vp]
         L.umoe_delay_step.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+        if not hasattr(L, "umoe_delay_step_rows"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_delay_step_rows): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_delay_step_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_from_codes.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_nearest.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.umoe_codec_ce_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -268,7 +280,7 @@ def lib():
             raise UmoeError(f"{_SO} predates this package (no umoe_struct_size): rebuild it (`make -C unimoe_audio_amd/csrc`)")
         L.umoe_struct_size.restype = C.c_size_t
         L.umoe_struct_size.argtypes = [C.c_char_p]
-        for cname, cls in STRUCT_MIRRORS.items():
+        for cname, cls in list(STRUCT_MIRRORS.items()) + list(TABLE_MIRRORS.items()):
             built = int(L.umoe_struct_size(cname.encode()))
             if built != C.sizeof(cls):
                 raise UmoeError(f"{_SO}: sizeof({cname}) is {built} in the library and {C.sizeof(cls)} in unimoe_audio_amd/_lib.py: "

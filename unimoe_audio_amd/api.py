@@ -13,13 +13,16 @@ tests/test_gpu_api.py drives text_to_speech / text_to_music end to end with a st
 from __future__ import annotations
 
 import os
-from typing import List, NamedTuple, Optional, Union
+from dataclasses import dataclass
+from typing import Any, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
 from .codec_utils import DecoderOutput, generate_output, prepare_audio_prompt, preprocess_codec
 from .config import UniMoEAudioConfig
 from .model import UniAudioRVQQwen2_5VLMoEForConditionalGeneration
+from .row_params import scaled as _scaled
+
 
 class AudioChunk(NamedTuple):
     """One piece of a streamed request: samples [start_sample, start_sample + len(pcm)) of row `row` (float32, CPU, the codec's
@@ -39,6 +42,41 @@ def _frame_codes(eng, row: int, f0: int, f1: int, t_valid: int) -> torch.Tensor:
     idx = eng.prefill_steps[row] + torch.arange(f0, f1, device=tok.device)[:, None] + d[None]
     g = tok.gather(0, idx.clamp(max=tok.shape[0] - 1)).long()
     return torch.where(idx < t_valid, g, torch.full_like(g, cfg.codec_pad_value)).cpu()
+
+
+@dataclass
+class SpeechRequest:
+    """One text_to_speech request of UniMoEAudio.generate_batch: text_to_speech's arguments and defaults, for ONE sentence, plus seed"""
+    transcription: str
+    prompt_transcription: str
+    prompt_wav: Optional[str] = None
+    prompt_codec: Any = None
+    max_audio_seconds: int = 10
+    min_audio_seconds: int = 2
+    temperature: float = 1.0
+    top_p: float = 1.0
+    cfg_filter_top_k: Optional[int] = 45
+    save_name: str = "speech"
+    cfg_scale: float = 1.0
+    eos_prob_mul_factor: float = 1.0
+    do_sample: bool = True
+    seed: int = 0
+
+
+@dataclass
+class MusicRequest:
+    """One text_to_music request of UniMoEAudio.generate_batch: text_to_music's arguments and defaults, for ONE caption, plus seed"""
+    caption: str
+    max_audio_seconds: int = 20
+    min_audio_seconds: int = 8
+    temperature: float = 1.0
+    top_p: float = 1.0
+    cfg_filter_top_k: Optional[int] = 45
+    save_name: str = "music"
+    cfg_scale: float = 10.0
+    eos_prob_mul_factor: float = 0.6
+    do_sample: bool = True
+    seed: int = 0
 
 
 SYSTEM_MESSAGE = "<|im_start|>system\nYou are a helpful assistant.<|im_end|>\n"
@@ -113,13 +151,15 @@ class UniMoEAudio:
                        top_p: float = 0.95, cfg_filter_top_k: int = 45, eos_prob_mul_factor: float = 0.8, do_sample: bool = True,
                        seed: int = 0):
         """input_ids [2B, T] (negative prompt, positive prompt per sample), returns the list of [len_i, 12] code tensors
-        exactly as the reference's `generate_output` does (delay pattern reverted)."""
+        exactly as the reference's `generate_output` does (delay pattern reverted).
+        max_audio_seconds, min_audio_seconds, the sampling settings and seed may each be a sequence of B values, one per sample
+        (model.generate): the samples then decode in one batch, each with its own settings and length."""
         cfg = self.model.config
         B = input_ids.shape[0] // 2
         prefill, steps = prepare_audio_prompt(cfg, [None] * B)
         dec = DecoderOutput(prefill, steps, self.device)
-        codes, lengths = self.model.generate(input_ids, attention_mask, dec, max_tokens=max_audio_seconds * 50,
-                                             min_tokens=min_audio_seconds * 50, codec_input_ids=codec_input_ids,
+        codes, lengths = self.model.generate(input_ids, attention_mask, dec, max_tokens=_scaled(max_audio_seconds, 50),
+                                             min_tokens=_scaled(min_audio_seconds, 50), codec_input_ids=codec_input_ids,
                                              cfg_scale=cfg_scale, temperature=temperature, top_p=top_p,
                                              cfg_filter_top_k=cfg_filter_top_k, eos_prob_mul_factor=eos_prob_mul_factor,
                                              do_sample=do_sample, seed=seed)
@@ -131,7 +171,8 @@ class UniMoEAudio:
         B = input_ids.shape[0] // 2
         prefill, steps = prepare_audio_prompt(self.model.config, [None] * B)
         dec = DecoderOutput(prefill, steps, self.device)
-        return self.model.generate_stream(input_ids, attention_mask, dec, max_tokens=max_audio_seconds * 50, min_tokens=min_audio_seconds * 50,
+        return self.model.generate_stream(input_ids, attention_mask, dec, max_tokens=_scaled(max_audio_seconds, 50),
+                                          min_tokens=_scaled(min_audio_seconds, 50),
                                           codec_input_ids=codec_input_ids, chunk_frames=chunk_frames, **gen)
 
     @torch.no_grad()
@@ -140,7 +181,8 @@ class UniMoEAudio:
                               top_p: float = 0.95, cfg_filter_top_k: int = 45, eos_prob_mul_factor: float = 0.8, do_sample: bool = True,
                               seed: int = 0, chunk_frames: int = 25):
         """generate_codes() as a stream: yields (row, codes [n, 12]) as the decode loop makes frames final, every `chunk_frames`
-        steps.  Concatenated per row, the chunks are generate_codes()'s codes at the same seed."""
+        steps.  Concatenated per row, the chunks are generate_codes()'s codes at the same seed.  The settings take sequences as
+        generate_codes()'s do; a row with a shorter max_audio_seconds is complete while the longer rows still decode."""
         upds = self._stream_updates(input_ids, attention_mask, codec_input_ids, max_audio_seconds, min_audio_seconds, chunk_frames,
                                     cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
                                     eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
@@ -154,7 +196,8 @@ class UniMoEAudio:
                       **gen):
         """The streamed twin of generate_codes + _finish: every state read, the frames that became final go through
         umoe_rvq_from_delayed and the streaming DAC decoder, queued on the decode stream between two replays (never on a side
-        stream: see DecodeEngine.run_stream).  A row's last chunk carries _finish's min_duration=1 zero pad."""
+        stream: see DecodeEngine.run_stream).  A row's last chunk carries _finish's min_duration=1 zero pad.
+        stem: one save_name, or one per row (generate_batch)."""
         from .dac import DacStreamDecoder, DelayedTokenSource, write_wav_pcm16
         B = input_ids.shape[0] // 2
         dm = self.dac.model
@@ -188,7 +231,8 @@ class UniMoEAudio:
         if output_dir is not None:
             os.makedirs(output_dir, exist_ok=True)
             for i in range(B):
-                write_wav_pcm16(os.path.join(output_dir, f"generated_{stem}_{i}.wav"), torch.cat(kept[i])[None], dm.sample_rate)
+                name = stem if isinstance(stem, str) else stem[i]
+                write_wav_pcm16(os.path.join(output_dir, f"generated_{name}_{i}.wav"), torch.cat(kept[i])[None], dm.sample_rate)
 
     # ---- reference task methods (both spellings) -----------------------------------------------------------------------
     def _texts(self, obj: Union[str, List[str]]) -> List[str]:
@@ -203,7 +247,7 @@ class UniMoEAudio:
         os.makedirs(output_dir, exist_ok=True)
         paths = []
         for i, a in enumerate(audios):
-            path = os.path.join(output_dir, f"generated_{stem}_{i}.wav")
+            path = os.path.join(output_dir, f"generated_{stem if isinstance(stem, str) else stem[i]}_{i}.wav")
             self.dac.decode(a.transpose(0, 1).unsqueeze(0), save_path=path, min_duration=1)
             paths.append(path)
         return paths
@@ -211,10 +255,10 @@ class UniMoEAudio:
     def text_to_music(self, caption: Union[str, List[str]], output_dir: str = "./", max_audio_seconds: int = 20,
                       min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                       save_name: str = "music", cfg_scale: float = 10.0, eos_prob_mul_factor: float = 0.6, do_sample: bool = True,
-                      **_) -> List[str]:
+                      seed: int = 0, **_) -> List[str]:
         enc = self._music_prompt(caption)
         audios = self.generate_codes(enc.input_ids, enc.attention_mask, None, max_audio_seconds, min_audio_seconds, cfg_scale,
-                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample)
+                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample, seed)
         return self._finish(audios, output_dir, save_name)
 
     def _music_prompt(self, caption):
@@ -228,21 +272,21 @@ class UniMoEAudio:
     def text_to_music_stream(self, caption: Union[str, List[str]], output_dir: Optional[str] = None, max_audio_seconds: int = 20,
                              min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                              save_name: str = "music", cfg_scale: float = 10.0, eos_prob_mul_factor: float = 0.6, do_sample: bool = True,
-                             chunk_frames: int = 25, **_):
+                             chunk_frames: int = 25, seed: int = 0, **_):
         """text_to_music() as a stream of AudioChunks (see _stream_audio); output_dir: also write text_to_music()'s wav files at the end"""
         enc = self._music_prompt(caption)
         return self._stream_audio(enc.input_ids, enc.attention_mask, None, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir,
                                   save_name, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
-                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample)
+                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
 
     def text_to_speech(self, transcription: Union[str, List[str], None] = None, prompt_transcription: Optional[str] = None,
                        prompt_wav: Optional[str] = None, output_dir: str = "./", max_audio_seconds: int = 10,
                        min_audio_seconds: int = 2, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                        caption=None, prompt_text=None, prompt_codec=None, save_name: str = "speech", cfg_scale: float = 1.0,
-                       eos_prob_mul_factor: float = 1.0, do_sample: bool = True, **_) -> List[str]:
+                       eos_prob_mul_factor: float = 1.0, do_sample: bool = True, seed: int = 0, **_) -> List[str]:
         enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec)
         audios = self.generate_codes(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, cfg_scale,
-                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample)
+                                     temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample, seed)
         return self._finish(audios, output_dir, save_name)
 
     def _speech_prompt(self, transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec):
@@ -269,12 +313,56 @@ class UniMoEAudio:
                               prompt_wav: Optional[str] = None, output_dir: Optional[str] = None, max_audio_seconds: int = 10,
                               min_audio_seconds: int = 2, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                               caption=None, prompt_text=None, prompt_codec=None, save_name: str = "speech", cfg_scale: float = 1.0,
-                              eos_prob_mul_factor: float = 1.0, do_sample: bool = True, chunk_frames: int = 25, **_):
+                              eos_prob_mul_factor: float = 1.0, do_sample: bool = True, chunk_frames: int = 25, seed: int = 0, **_):
         """text_to_speech() as a stream of AudioChunks (see _stream_audio); output_dir: also write text_to_speech()'s wav files at the end"""
         enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec)
         return self._stream_audio(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir,
                                   save_name, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
-                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample)
+                                  eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
+
+    def generate_batch(self, requests: Sequence[Union[SpeechRequest, MusicRequest]], output_dir: Optional[str] = "./", stream: bool = False,
+                       chunk_frames: int = 25):
+        """Speech and music requests with their OWN settings, lengths and seeds in ONE decode batch: a decode step streams the same
+        weights whatever it carries, so a mixed batch costs one generation instead of one per kind of request.
+        Each request's prompt pair is built as text_to_speech / text_to_music build it, the pairs are left-padded to one length, and
+        one generation runs with the per-request settings table (model.generate).  Returns one wav path per request,
+        `generated_<save_name>_<i>.wav` with i the request's position; stream=True returns the generator of AudioChunks instead
+        (row = position; output_dir, when not None, also gets the wav files at the end).
+        Voice prompts: every SpeechRequest carries its own (prompt_wav or prompt_codec, as text_to_speech requires); music requests
+        have none.  The two mix freely: the prompt codes fill the <|AUDIO_PLACEHOLDER|> positions of the batch in row order
+        (calculate_input_embedding), and a music prompt has no such position.  video_text_to_music requests are not batched here."""
+        if not requests:
+            raise ValueError("generate_batch: no requests")
+        encs, codecs = [], []
+        for r in requests:
+            if isinstance(r, SpeechRequest):
+                enc, codec = self._speech_prompt(r.transcription, r.prompt_transcription, r.prompt_wav, None, None, r.prompt_codec)
+                codecs.append(codec)
+            elif isinstance(r, MusicRequest):
+                enc = self._music_prompt(r.caption)
+            else:
+                raise TypeError(f"generate_batch: a SpeechRequest or a MusicRequest, not {type(r).__name__}")
+            if enc.input_ids.shape[0] != 2:
+                raise ValueError("generate_batch: one text per request")
+            encs.append(enc)
+        T = max(e.input_ids.shape[1] for e in encs)
+        pad_id = getattr(self.tokenizer, "pad_token_id", None) or 0
+        ids = torch.full((2 * len(encs), T), pad_id, dtype=encs[0].input_ids.dtype)
+        mask = torch.zeros((2 * len(encs), T), dtype=encs[0].attention_mask.dtype)
+        for i, e in enumerate(encs):                                  # left padding, like the tokenizer's own (mod.py:104)
+            ids[2 * i:2 * i + 2, T - e.input_ids.shape[1]:] = e.input_ids
+            mask[2 * i:2 * i + 2, T - e.input_ids.shape[1]:] = e.attention_mask
+        codec = torch.cat(codecs) if codecs else None
+        col = lambda f: [getattr(r, f) for r in requests]            # noqa: E731
+        gen = dict(cfg_scale=col("cfg_scale"), temperature=col("temperature"), top_p=col("top_p"), cfg_filter_top_k=col("cfg_filter_top_k"),
+                   eos_prob_mul_factor=col("eos_prob_mul_factor"), do_sample=col("do_sample"), seed=col("seed"))
+        if stream:
+            return self._stream_audio(ids, mask, codec, col("max_audio_seconds"), col("min_audio_seconds"), chunk_frames, output_dir,
+                                      col("save_name"), **gen)
+        if output_dir is None:
+            raise ValueError("generate_batch: output_dir is needed unless stream=True")
+        audios = self.generate_codes(ids, mask, codec, col("max_audio_seconds"), col("min_audio_seconds"), **gen)
+        return self._finish(audios, output_dir, col("save_name"))
 
     def video_text_to_music(self, video, caption: Union[str, List[str]], output_dir: str = "./", max_audio_seconds: int = 20,
                             min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,

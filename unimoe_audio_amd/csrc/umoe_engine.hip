@@ -1216,9 +1216,10 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     sa.logits = e->logits; sa.B = B; sa.C = C; sa.V = V; sa.cfg_scale = io->cfg_scale; sa.temperature = io->temperature;
     sa.top_p = io->top_p; sa.eos_mul = io->eos_mul; sa.top_k = io->top_k; sa.eos = c.eos; sa.min_tokens = io->min_tokens;
     sa.step = io->state + 4 * B; sa.do_sample = io->do_sample; sa.seed = io->seed; sa.pred = e->pred;
+    sa.row_params = io->row_params;      // per-request settings (NULL: the scalars above); every rank samples its own rows from its own io
     if ((rc = umoe_codec_head_cfg_sample(&sa, s))) return rc;
     PROF(K_SAMPLE);
-    rc = umoe_delay_step(e->pred, io->tokens, io->state, e->d_delay, B, C, c.Tmax, c.eos, c.pad, e->max_delay, s);
+    rc = umoe_delay_step_rows(e->pred, io->tokens, io->state, e->d_delay, B, C, c.Tmax, c.eos, c.pad, e->max_delay, io->row_params, s);
     PROF(K_DELAY);
     return rc;
 }

@@ -20,6 +20,7 @@ extern "C" size_t umoe_struct_size(const char* name) {
     UMOE_SZ(umoe_router_args) UMOE_SZ(umoe_group_t) UMOE_SZ(umoe_gemm_args) UMOE_SZ(umoe_tgroup_t) UMOE_SZ(umoe_tgemm_args) UMOE_SZ(umoe_tn_group_t) UMOE_SZ(umoe_tgemm_tn_args)
     UMOE_SZ(umoe_swiglu_bwd_args) UMOE_SZ(umoe_attn_bwd_args) UMOE_SZ(umoe_combine_args) UMOE_SZ(umoe_rope_args) UMOE_SZ(umoe_attn_args)
     UMOE_SZ(umoe_sample_args) UMOE_SZ(umoe_engine_cfg) UMOE_SZ(umoe_layer_weights) UMOE_SZ(umoe_decode_io)
+    UMOE_SZ(umoe_row_params)
 #undef UMOE_SZ
     return 0;
 }
@@ -483,7 +484,8 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
     return z ^ (z >> 31);
 }
 
-// one workgroup per (b, c) row of V logits; dynamic LDS: 3 * V floats
+// one workgroup per (b, c) row of V logits; dynamic LDS: 3 * V floats (the fast path's static arrays, ~1.6 KB, are allocated whichever
+// path a workgroup takes).  The sampling settings are workgroup-uniform: the launch's scalars, or row b of the device table.
 __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float shf[4];
@@ -495,18 +497,24 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
     float* tmp = pr + a.V;
     const int b = blockIdx.x / a.C, c = blockIdx.x - b * a.C, tid = threadIdx.x;
     const int V = a.V, eos = a.eos;
+    const umoe_row_params* __restrict__ rp = a.row_params ? a.row_params + b : nullptr;
+    const float cfg_scale = rp ? rp->cfg_scale : a.cfg_scale, temperature = rp ? rp->temperature : a.temperature;
+    const float top_p = rp ? rp->top_p : a.top_p, eos_mul = rp ? rp->eos_mul : a.eos_mul;
+    const int top_k = rp ? rp->top_k : a.top_k, do_sample = rp ? rp->do_sample : a.do_sample;
+    const int min_tokens = rp ? rp->min_tokens : a.min_tokens;
+    const uint64_t seed = rp ? rp->seed : a.seed;
     const int step = a.step ? *a.step : 0;
-    const bool enable_eos = a.step ? (a.min_tokens < 0 || step >= a.min_tokens) : (a.enable_eos != 0);
+    const bool enable_eos = a.step ? (min_tokens < 0 || step >= min_tokens) : (a.enable_eos != 0);
     const float* un = a.logits + ((size_t)(2 * b) * a.C + c) * V;
     const float* co = a.logits + ((size_t)(2 * b + 1) * a.C + c) * V;
     for (int v = tid; v < V; v += 256) {
-        float g = (a.cfg_scale != 0.f) ? co[v] + a.cfg_scale * (co[v] - un[v]) : co[v];
+        float g = (cfg_scale != 0.f) ? co[v] + cfg_scale * (co[v] - un[v]) : co[v];
         if (enable_eos) {
             if (v > eos || (c >= 1 && v >= eos)) g = -INFINITY;
         } else if (v >= eos) {
             g = -INFINITY;
         }
-        if (c == 0 && v == eos) g *= a.eos_mul;
+        if (c == 0 && v == eos) g *= eos_mul;
         x[v] = g;
     }
     __syncthreads();
@@ -544,13 +552,13 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         __syncthreads();
         return ri;
     };
-    if (!a.do_sample || a.temperature == 0.0f) {
+    if (!do_sample || temperature == 0.0f) {
         const int am = block_argmax(x);
         if (tid == 0) a.pred[(size_t)b * a.C + c] = am;
         return;
     }
     // temperature, EOS-unless-arg-max (model.py:884-891)
-    for (int v = tid; v < V; v += 256) x[v] = x[v] / a.temperature;
+    for (int v = tid; v < V; v += 256) x[v] = x[v] / temperature;
     __syncthreads();
     if (eos >= 0) {
         const int top = block_argmax(x);
@@ -558,7 +566,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         __syncthreads();
     }
     // ---- fast path (0 < top_k <= 64): radix-select the k-th largest, then everything on <= 64 candidates -------
-    if (a.top_k > 0 && a.top_k <= 64) {
+    if (top_k > 0 && top_k <= 64) {
         __shared__ unsigned hist[256];
         __shared__ unsigned sel_prefix, sel_remaining;
         __shared__ int wsum[4];
@@ -577,7 +585,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         for (int j = 0; j < PER; ++j) keys[j] = (v0 + j < V) ? key_of(x[v0 + j]) : 0u;
         if (tid == 0) {
             sel_prefix = 0u;
-            sel_remaining = (unsigned)min(a.top_k, V);
+            sel_remaining = (unsigned)min(top_k, V);
         }
         for (int pass = 3; pass >= 0; --pass) {
             hist[tid] = 0u;
@@ -665,18 +673,18 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
             const float e = (vv == -INFINITY) ? 0.f : expf(vv - mx);
             return e / wave_sum(e);
         };
-        if (a.top_p < 1.0f) {  // model.py:899-910 restricted to the survivors of top-k
+        if (top_p < 1.0f) {  // model.py:899-910 restricted to the survivors of top-k
             const float pme = lane_softmax64(val);
             float before = 0.f;
             for (int j = 0; j < n; ++j) {
                 const float pj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pme), j));
                 if (pj > pme || (pj == pme && j < tid)) before += pj;
             }
-            if (before > a.top_p) val = -INFINITY;
+            if (before > top_p) val = -INFINITY;
         }
         const float pr_me = lane_softmax64(val);
         if (a.probs_out && tid < n) a.probs_out[((size_t)b * a.C + c) * V + cand_idx[tid]] = pr_me;
-        const uint64_t hsh = mix64(a.seed ^ mix64(((uint64_t)(uint32_t)step << 32) | (uint32_t)blockIdx.x));
+        const uint64_t hsh = mix64(seed ^ mix64(((uint64_t)(uint32_t)step << 32) | (uint32_t)blockIdx.x));
         const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);
         float cum = pr_me;  // inclusive prefix in index order
 #pragma unroll
@@ -693,7 +701,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         return;
     }
     // top-k by rank (ties: lower index first) (model.py:893-897)
-    if (a.top_k > 0) {
+    if (top_k > 0) {
         for (int v = tid; v < V; v += 256) {
             const float t = x[v];
             int rank = 0;
@@ -701,7 +709,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
                 const float u = x[j];
                 rank += (u > t) || (u == t && j < v);
             }
-            tmp[v] = (rank < a.top_k) ? t : -INFINITY;
+            tmp[v] = (rank < top_k) ? t : -INFINITY;
         }
         __syncthreads();
         for (int v = tid; v < V; v += 256) x[v] = tmp[v];
@@ -725,7 +733,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         for (int v = tid; v < V; v += 256) out[v] = out[v] / sm;
         __syncthreads();
     };
-    if (a.top_p < 1.0f) {  // model.py:899-910
+    if (top_p < 1.0f) {  // model.py:899-910
         block_softmax(x, pr);
         for (int v = tid; v < V; v += 256) {
             const float t = pr[v];
@@ -734,7 +742,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
                 const float u = pr[j];
                 if ((u > t) || (u == t && j < v)) before += u;
             }
-            tmp[v] = (before > a.top_p) ? -INFINITY : x[v];
+            tmp[v] = (before > top_p) ? -INFINITY : x[v];
         }
         __syncthreads();
         for (int v = tid; v < V; v += 256) x[v] = tmp[v];
@@ -745,7 +753,7 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
         for (int v = tid; v < V; v += 256) a.probs_out[((size_t)b * a.C + c) * V + v] = pr[v];
     // inverse-CDF draw in index order
     if (tid == 0) {
-        const uint64_t h = mix64(a.seed ^ mix64(((uint64_t)(uint32_t)step << 32) | (uint32_t)blockIdx.x));
+        const uint64_t h = mix64(seed ^ mix64(((uint64_t)(uint32_t)step << 32) | (uint32_t)blockIdx.x));
         const float u = (float)((h >> 40) + 0.5) * (1.0f / 16777216.0f);
         float cum = 0.f;
         int pick = -1, last = 0;
@@ -769,6 +777,7 @@ extern "C" int umoe_codec_head_cfg_sample(const umoe_sample_args* a, umoe_stream
     UMOE_REQUIRE(a->eos >= 0 && a->eos < a->V, "umoe_codec_head_cfg_sample: eos %d outside vocabulary %d", a->eos, a->V);
     const size_t lds = (size_t)3 * a->V * sizeof(float);
     UMOE_REQUIRE(lds <= 60 * 1024 && a->V <= 2048, "umoe_codec_head_cfg_sample: vocabulary %d too large for the LDS sampler", a->V);
+    UMOE_REQUIRE(((size_t)a->row_params & 7) == 0, "umoe_codec_head_cfg_sample: row_params must be 8-byte aligned");
     cfg_sample_kernel<<<dim3((unsigned)(a->B * a->C)), 256, lds, (hipStream_t)stream>>>(*a);
     UMOE_LAUNCH_CHECK();
     return 0;
@@ -778,7 +787,7 @@ extern "C" int umoe_codec_head_cfg_sample(const umoe_sample_args* a, umoe_stream
 // state layout: eos_detected[B], countdown[B], finished[B], prefill_step[B], {step, max_tokens, all_done, bos_over}
 __global__ __launch_bounds__(256) void delay_step_kernel(int64_t* pred, int32_t* tokens, int32_t* state,
                                                          const int32_t* __restrict__ delay, int B, int C, int Tmax,
-                                                         int eos, int pad, int md) {
+                                                         int eos, int pad, int md, const umoe_row_params* __restrict__ rp) {
     int32_t* eos_det = state;
     int32_t* countdown = state + B;
     int32_t* finished = state + 2 * B;
@@ -805,7 +814,8 @@ __global__ __launch_bounds__(256) void delay_step_kernel(int64_t* pred, int32_t*
         const int b = tid;
         const int cd = countdown[b];
         const bool active = cd != 0;
-        const bool trig = active && ((!eos_det[b] && pred[(size_t)b * C] == eos) || (cur >= max_tokens - md));
+        const int row_max = rp ? rp[b].max_tokens : max_tokens;     // the row's own length; the loop bound above stays the largest
+        const bool trig = active && ((!eos_det[b] && pred[(size_t)b * C] == eos) || (cur >= row_max - md));
         if (trig) eos_det[b] = 1;
         if (trig && cd < 0) {
             countdown[b] = md;
@@ -846,12 +856,19 @@ __global__ __launch_bounds__(256) void delay_step_kernel(int64_t* pred, int32_t*
     }
 }
 
-extern "C" int umoe_delay_step(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C,
-                               int Tmax, int eos, int pad, int max_delay, umoe_stream_t stream) {
+extern "C" int umoe_delay_step_rows(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C,
+                                    int Tmax, int eos, int pad, int max_delay, const umoe_row_params* row_params,
+                                    umoe_stream_t stream) {
     UMOE_REQUIRE(pred && tokens && state && delay && B > 0 && B <= 256 && C > 0, "umoe_delay_step: bad argument (B=%d)", B);
-    delay_step_kernel<<<1, 256, 0, (hipStream_t)stream>>>(pred, tokens, state, delay, B, C, Tmax, eos, pad, max_delay);
+    UMOE_REQUIRE(((size_t)row_params & 7) == 0, "umoe_delay_step: row_params must be 8-byte aligned");
+    delay_step_kernel<<<1, 256, 0, (hipStream_t)stream>>>(pred, tokens, state, delay, B, C, Tmax, eos, pad, max_delay, row_params);
     UMOE_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int umoe_delay_step(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C,
+                               int Tmax, int eos, int pad, int max_delay, umoe_stream_t stream) {
+    return umoe_delay_step_rows(pred, tokens, state, delay, B, C, Tmax, eos, pad, max_delay, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------ RVQ

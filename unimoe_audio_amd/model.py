@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops, quant
+from . import row_params as RP
 from .codec_utils import DecoderOutput
 from .config import UniMoEAudioConfig
 from .dcmoe import UniMoEAudioSparseMoeBlock
@@ -391,14 +392,23 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         (model.py:708-790): vision tower, embeddings scattered over the pad tokens, 3-D mRoPE positions from get_rope_index.
         use_cache=False: the reference recomputes the whole prefix every step without a cache (model.py:964-980) and allows it only
         without a codec prompt (:1092-1093); the result is the same tokens, so the engine serves it from its KV cache.
-        expert_weights (not in the reference): "bf16" / "fp8" expert weights of the decode engine (None: fp8 after quantize_experts_)."""
+        expert_weights (not in the reference): "bf16" / "fp8" expert weights of the decode engine (None: fp8 after quantize_experts_).
+        Per-request settings (not in the reference): each of max_tokens, min_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k,
+        eos_prob_mul_factor, do_sample and seed may be a sequence with one value per batch entry (DecodeEngine.start_decode); the
+        engine is sized by the largest max_tokens.  Scalars take exactly the path they took before.  Not with teacher labels."""
         if not use_cache and codec_input_ids is not None:
             raise AssertionError("use_cache=False with a codec prompt: the reference asserts use_cache here (model.py:1092-1093)")
         dev = self.device
         input_ids, attention_mask = input_ids.to(dev), attention_mask.to(dev)
         B = input_ids.shape[0] // 2
         T = input_ids.shape[1]
-        eng = self.engine(B, T, int(max_tokens), expert_weights=expert_weights)
+        per_row = [n for n, v in (("max_tokens", max_tokens), ("min_tokens", min_tokens), ("cfg_scale", cfg_scale), ("temperature", temperature),
+                                  ("top_p", top_p), ("cfg_filter_top_k", cfg_filter_top_k), ("eos_prob_mul_factor", eos_prob_mul_factor),
+                                  ("do_sample", do_sample), ("seed", seed)) if RP.is_sequence(v)]
+        if per_row and getattr(dec_output, "labels_prefill", None) is not None:
+            raise L.UmoeError(f"generate: teacher labels (DecoderOutput.labels_prefill) take one setting for the batch, not a sequence ({', '.join(per_row)})")
+        top_tokens = RP.largest(max_tokens)                  # the engine is sized by the longest row
+        eng = self.engine(B, T, top_tokens, expert_weights=expert_weights)
         pos3 = deltas = None
         if vision_in_generate and (pixel_values is not None or pixel_values_videos is not None):
             x = self.multimodal_embedding(input_ids, None if codec_input_ids is None else codec_input_ids.to(dev), pixel_values, image_grid_thw,
@@ -407,8 +417,8 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         else:
             x = self.calculate_input_embedding(input_ids, None if codec_input_ids is None else codec_input_ids.to(dev))
         eng.prefill(x.reshape(-1, x.shape[-1]).contiguous(), attention_mask, position_ids=pos3, rope_deltas=deltas)
-        eng.start_decode(dec_output.generated_tokens, dec_output.prefill_steps, int(max_tokens), min_tokens,
-                         cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, top_k=cfg_filter_top_k,
+        eng.start_decode(dec_output.generated_tokens, dec_output.prefill_steps, max_tokens if RP.is_sequence(max_tokens) else int(max_tokens),
+                         min_tokens, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, top_k=cfg_filter_top_k,
                          eos_mul=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
         if getattr(dec_output, "labels_prefill", None) is not None:
             self._run_with_labels(eng, dec_output, int(max_tokens), min_tokens, cfg_scale, eos_prob_mul_factor, int(debug_guidance_step),
@@ -442,7 +452,7 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         input_ids, attention_mask = input_ids.to(dev), attention_mask.to(dev)
         B = input_ids.shape[0] // 2
         T = input_ids.shape[1]
-        eng = self.engine(B, T, int(max_tokens), expert_weights=expert_weights)
+        eng = self.engine(B, T, RP.largest(max_tokens), expert_weights=expert_weights)
         if (eng.ep is not None and eng.ep.size > 1) or getattr(eng, "sharded", False):
             raise L.UmoeError("generate_stream: expert-parallel decode is not streamed; use generate()")
         pos3 = deltas = None
@@ -453,8 +463,8 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         else:
             x = self.calculate_input_embedding(input_ids, None if codec_input_ids is None else codec_input_ids.to(dev))
         eng.prefill(x.reshape(-1, x.shape[-1]).contiguous(), attention_mask, position_ids=pos3, rope_deltas=deltas)
-        eng.start_decode(dec_output.generated_tokens, dec_output.prefill_steps, int(max_tokens), min_tokens,
-                         cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, top_k=cfg_filter_top_k,
+        eng.start_decode(dec_output.generated_tokens, dec_output.prefill_steps, max_tokens if RP.is_sequence(max_tokens) else int(max_tokens),
+                         min_tokens, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, top_k=cfg_filter_top_k,
                          eos_mul=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
         ends = {}
         for upd in eng.run_stream(int(chunk_frames), use_graph=use_graph):
@@ -531,6 +541,7 @@ class DecodeEngine:
         self.tokens = None
         self.state = None
         self.io = None
+        self.row_params = None
         self.captured = False
 
     def _k(self, t):
@@ -662,10 +673,21 @@ class DecodeEngine:
         L.check(L.lib().umoe_engine_prefill_external(self.h, valid.data_ptr(), T, pos_p, nxt_p, self._stream()), "umoe_engine_prefill_external")
         self.captured = False
 
-    def start_decode(self, prefill_tokens: torch.Tensor, prefill_steps: List[int], max_tokens: int, min_tokens,
+    def start_decode(self, prefill_tokens: torch.Tensor, prefill_steps: List[int], max_tokens, min_tokens,
                      cfg_scale, temperature, top_p, top_k, eos_mul, do_sample, seed=0):
+        """Each of max_tokens, min_tokens, cfg_scale, temperature, top_p, top_k, eos_mul, do_sample and seed is one value for the batch
+        or a sequence with one value per batch entry.  All scalars: the scalar members of umoe_decode_io, no table.  Any sequence: the
+        rest is broadcast into a device table of umoe_row_params (row_params.pack_row_params) which the sampler and the delay step of
+        every step read; the loop bound is the largest max_tokens, and a row ends by its own."""
         B, Cc = self.batch, self.cfg.codec_channels
         assert prefill_tokens.shape[0] == B and prefill_tokens.shape[2] == Cc
+        table = RP.pack_row_params(B, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, top_k=top_k, eos_mul=eos_mul,
+                                   do_sample=do_sample, seed=seed, min_tokens=min_tokens, max_tokens=max_tokens)
+        if table is not None:
+            r0 = table[0]         # (the scalar members are not read when a table is set; they carry entry 0's values)
+            cfg_scale, temperature, top_p, eos_mul = float(r0["cfg_scale"]), float(r0["temperature"]), float(r0["top_p"]), float(r0["eos_mul"])
+            top_k, do_sample, min_tokens, seed = int(r0["top_k"]), int(r0["do_sample"]), int(r0["min_tokens"]), int(r0["seed"])
+            max_tokens = int(table["max_tokens"].max())
         if max_tokens + 2 > self.Tmax or self.T_prompt + max_tokens + 1 > self.Lmax:
             raise L.UmoeError("engine buffers too small for max_tokens")
         tok = torch.full((B, self.Tmax, Cc), -1, dtype=torch.int32, device=self.dev)
@@ -678,9 +700,12 @@ class DecodeEngine:
         st[4 * B + 0], st[4 * B + 1], st[4 * B + 4] = step0, max_tokens, step0
         self.tokens, self.state = tok, st.to(self.dev)
         self.prefill_steps, self.max_tokens = list(prefill_steps), max_tokens
+        # the table lives as long as the io that points at it (a captured step graph records the pointer)
+        self.row_params = None if table is None else ops.row_params_tensor(table, self.dev)
         self.io = L.DecodeIO(tokens=tok.data_ptr(), state=self.state.data_ptr(), cfg_scale=cfg_scale, temperature=temperature,
                              top_p=top_p, eos_mul=eos_mul, top_k=-1 if top_k is None else int(top_k), do_sample=int(bool(do_sample)),
-                             min_tokens=-1 if min_tokens is None else int(min_tokens), seed=seed)
+                             min_tokens=-1 if min_tokens is None else int(min_tokens), seed=seed,
+                             row_params=None if self.row_params is None else self.row_params.data_ptr())
         self.captured = False
         self.steps_run = 0
 

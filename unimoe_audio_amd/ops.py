@@ -372,9 +372,14 @@ def codec_embed_sum_bwd(tok: torch.Tensor, d_out: torch.Tensor, V: int) -> torch
 
 def cfg_sample(logits: torch.Tensor, B: int, Cc: int, V: int, *, cfg_scale, temperature, top_p, top_k, eos, eos_mul,
                enable_eos=True, do_sample=True, seed=0, want_probs=False, step: Optional[torch.Tensor] = None,
-               min_tokens: Optional[int] = None):
+               min_tokens: Optional[int] = None, row_params: Optional[torch.Tensor] = None):
     """step: a device int32 scalar, the decode engine's step counter. Given, it replaces 0 in the hash, and EOS is enabled iff
-    min_tokens is None or *step >= min_tokens (enable_eos is then ignored), as in an engine step."""
+    min_tokens is None or *step >= min_tokens (enable_eos is then ignored), as in an engine step.
+    row_params: a device table from row_params_tensor ([B] records of umoe_row_params): batch entry b then samples with ITS cfg_scale,
+    temperature, top_p, eos_mul, top_k, do_sample, min_tokens and seed, and the scalar arguments of those names are not read."""
+    if row_params is not None:
+        assert row_params.dtype == torch.uint8 and tuple(row_params.shape) == (B, C.sizeof(L.RowParams)) and row_params.is_contiguous() \
+            and row_params.device == logits.device, "row_params: the [B, 40] uint8 device tensor of row_params_tensor"
     pred = torch.empty((B, Cc), dtype=torch.int64, device=logits.device)
     probs = torch.empty((B * Cc, V), dtype=torch.float32, device=logits.device) if want_probs else None
     if step is not None:
@@ -382,15 +387,33 @@ def cfg_sample(logits: torch.Tensor, B: int, Cc: int, V: int, *, cfg_scale, temp
     a = L.SampleArgs(logits=_p(logits), B=B, C=Cc, V=V, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p,
                      eos_mul=eos_mul, top_k=-1 if top_k is None else top_k, eos=eos, enable_eos=int(enable_eos),
                      min_tokens=-1 if min_tokens is None else int(min_tokens), step=None if step is None else _p(step),
-                     do_sample=int(do_sample), seed=seed, pred=_p(pred), probs_out=_p(probs))
+                     do_sample=int(do_sample), seed=seed, pred=_p(pred), probs_out=_p(probs),
+                     row_params=None if row_params is None else _p(row_params))
     L.check(L.lib().umoe_codec_head_cfg_sample(C.byref(a), _stream()), "umoe_codec_head_cfg_sample")
     return (pred, probs) if want_probs else pred
 
 
-def delay_step(pred, tokens, state, delay, eos, pad):
+def delay_step(pred, tokens, state, delay, eos, pad, row_params: Optional[torch.Tensor] = None):
+    """row_params (row_params_tensor): row b is forced to end by ITS max_tokens; state[4B + 1] stays the loop bound (the largest)"""
     B, Tmax, Cc = tokens.shape
-    L.check(L.lib().umoe_delay_step(_p(pred), _p(tokens), _p(state), _p(delay), B, Cc, Tmax, eos, pad,
-                                    int(delay.max().item()), _stream()), "umoe_delay_step")
+    if row_params is None:
+        L.check(L.lib().umoe_delay_step(_p(pred), _p(tokens), _p(state), _p(delay), B, Cc, Tmax, eos, pad,
+                                        int(delay.max().item()), _stream()), "umoe_delay_step")
+        return
+    assert row_params.dtype == torch.uint8 and tuple(row_params.shape) == (B, C.sizeof(L.RowParams)) and row_params.is_contiguous() \
+        and row_params.device == tokens.device, "row_params: the [B, 40] uint8 device tensor of row_params_tensor"
+    L.check(L.lib().umoe_delay_step_rows(_p(pred), _p(tokens), _p(state), _p(delay), B, Cc, Tmax, eos, pad,
+                                         int(delay.max().item()), _p(row_params), _stream()), "umoe_delay_step_rows")
+
+
+def row_params_tensor(table, device) -> torch.Tensor:
+    """A table of row_params.pack_row_params (numpy, ROW_DTYPE) as ONE device tensor [B, 40] uint8: what the kernels read.  The caller
+    keeps it alive for as long as a launch (or a captured step graph) may read it."""
+    import numpy as np
+    from .row_params import ROW_DTYPE
+    assert table.dtype == ROW_DTYPE and table.ndim == 1 and ROW_DTYPE.itemsize == C.sizeof(L.RowParams)
+    raw = np.ascontiguousarray(table).view(np.uint8).reshape(table.shape[0], ROW_DTYPE.itemsize)
+    return torch.from_numpy(raw.copy()).to(device)
 
 
 def rvq_from_codes(codes, codebooks, out_w, out_b):
