@@ -1,6 +1,7 @@
 """CLI mirror of the reference's examples/inference.py (flags --task/-t --input/-i --ref-audio/-ra --ref-text/-rt
 --video/-v --output/-o --model/-m --device/-d --no-reuse; exit code 0/1, reference examples/inference.py:152-235).
---requests FILE.json (not in the reference): speech and music requests with their own settings in ONE decode batch."""
+--requests FILE.json (not in the reference): speech and music requests with their own settings in ONE decode batch; with --serve the
+list is a queue served by --slots rows, each request admitted as soon as a row is free."""
 import argparse
 import json
 import os
@@ -47,13 +48,22 @@ def load_requests(path):
     return reqs
 
 
-def batch_inference(requests_file, model_path, output="./output", device=0, reuse=True, expert_weights="bf16", stream=False):
+def batch_inference(requests_file, model_path, output="./output", device=0, reuse=True, expert_weights="bf16", stream=False, serve=False,
+                    slots=8):
     global _MODEL
     from unimoe_audio_amd.api import UniMoEAudio
     try:
         reqs = load_requests(requests_file)
         if _MODEL is None or not reuse:
             _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights)
+        if serve:
+            # continuous batching: `slots` rows decode together, a request takes a row as soon as one is free
+            import time
+            t0, paths = time.perf_counter(), {}
+            for i, path in _MODEL.serve(reqs, slots=slots, output_dir=output, max_audio_seconds=max(r.max_audio_seconds for r in reqs)):
+                print(f"{time.perf_counter() - t0:8.3f} s  request {i}  {path}", flush=True)
+                paths[i] = path
+            return [paths[i] for i in sorted(paths)]
         if not stream:
             return _MODEL.generate_batch(reqs, output_dir=output)
         import time
@@ -104,9 +114,14 @@ def main():
     ap.add_argument("--expert-weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step)")
     ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
+    ap.add_argument("--serve", action="store_true", help="with --requests: serve the list as a queue (UniMoEAudio.serve): --slots rows decode "
+                                                         "together and a request is admitted as soon as a row is free; any number of requests")
+    ap.add_argument("--slots", type=int, default=8, help="rows of the serving batch (1..8)")
     a = ap.parse_args()
     if a.requests:
-        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream)
+        if a.serve and a.stream:
+            ap.error("--serve does not stream chunks")
+        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream, a.serve, a.slots)
         sys.exit(0 if out else 1)
     if not a.task or a.input is None:
         ap.error("--task and --input are required (or --requests FILE.json)")

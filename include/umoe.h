@@ -593,6 +593,9 @@ typedef struct {
     uint64_t seed;
     int64_t* pred;            /* [B][C] */
     float* probs_out;
+    const int32_t* row_clock;          /* device int32 [2B] {step_off[b], t_prompt[b]} or NULL (= the one clock *step).  Set: workgroup (b, c)
+                                        * lives on row b's local clock, local = *step - step_off[b]: min_tokens is compared with `local`
+                                        * and the draw is u(seed, local, b * C + c) (the sampler reads step_off only) */
     const umoe_row_params* row_params; /* device [B] or NULL.  Set: workgroup (b, c) takes cfg_scale, temperature, top_p, eos_mul, top_k,
                                         * do_sample, min_tokens and seed from row_params[b]; the draw of row (b, c) stays
                                         * u(seed, step, b * C + c), what it is in a launch whose one seed is row_params[b].seed */
@@ -611,6 +614,13 @@ int umoe_delay_step(int64_t* pred, int32_t* tokens, int32_t* state, const int32_
  * largest row value. */
 int umoe_delay_step_rows(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C, int Tmax,
                          int eos, int pad, int max_delay, const umoe_row_params* row_params, umoe_stream_t stream);
+/* the same on per-row clocks: row_clock = device int32 [2B] {step_off[b], t_prompt[b]} (NULL = umoe_delay_step_rows).  Row b lives at
+ * cur_b = (step - step_off[b]) + 1: its forced ending, finished[b], its term of bos_over and the slot tokens[b][cur_b] it writes use
+ * cur_b.  A row whose countdown is 0 at entry (ended, or never used) writes no token.  "Every countdown is 0" still ends a run;
+ * step >= max_tokens does not (rows come and go, each ends by its own max_tokens).  The step word advances by one per launch. */
+int umoe_delay_step_clock(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C, int Tmax,
+                          int eos, int pad, int max_delay, const umoe_row_params* row_params, const int32_t* row_clock,
+                          umoe_stream_t stream);
 
 /* Per-channel codec cross-entropy of the training loss (model.py:830-847) on already shifted logits [N][C][V] fp32 and
  * labels [N][C] int64 (-100 = ignore): ch_loss[c] = mean nll over valid labels, total = ch_loss[0] + sum of channels with
@@ -760,6 +770,10 @@ typedef struct {
     float cfg_scale, temperature, top_p, eos_mul;
     int top_k, do_sample, min_tokens;
     uint64_t seed;
+    int32_t* row_clock;       /* device int32 [rows] {step_off[b], t_prompt[b]} per batch entry, or NULL (= one clock for the batch: the
+                               * step word, its first value state[4B + 4] and the prompt length of the last prefill).  Set: row b
+                               * decodes on its local clock step - step_off[b] behind a prompt of t_prompt[b] cache slots, and a row
+                               * whose countdown is 0 is parked (attends to one key).  umoe_engine_admit writes the entries. */
     const umoe_row_params* row_params; /* device [rows / 2] or NULL (= the scalar members above): per-request sampling settings and
                                         * max_tokens, handed to the sampler and the delay step of every step */
 } umoe_decode_io;
@@ -771,6 +785,23 @@ int umoe_engine_replay(umoe_engine* e, umoe_stream_t stream);
  * {qkv, rope, attn, oproj, router, dispatch, gateup, down, combine, embed, head, sample, delay} */
 int umoe_engine_profile_step(umoe_engine* e, const umoe_decode_io* io, umoe_stream_t stream, float* ms, int* launches,
                              int n);
+/* Admission of a request into a free row of a batch that is decoding (io->row_clock set; ep_size 1; 1-D positions).
+ * umoe_engine_reserve: sizes the workspace for prompts of up to n_tok tokens (2 * T of the longest admitted prompt) and puts the group
+ *   table into decode shape.  The workspace is re-allocated (and zeroed) here and never afterwards by an admission, so a captured step
+ *   graph stays valid across admissions: call it once when serving starts, before the first admission.
+ * umoe_engine_admit: prefills the CFG pair x [2 * T][D] (valid_host [2][T], left padded) into cache rows 2b, 2b + 1 -- the prefill body
+ *   of umoe_engine_prefill over 2 rows -- and resets batch entry b on the device, in stream order and without a host read of the state:
+ *   row_clock[b] = {step - (prefill_step - 1), T}, eos_detected 0, countdown -1, finished -1, prefill_step, tokens[b][t >= prefix_len]
+ *   = -1 (the caller has written the request's prefix tokens[b][0 .. prefix_len) -- the buffer of the reference's _prepare_audio_prompt,
+ *   prefill_step <= prefix_len, with its own -1 entries -- and row_params[b] before the call).  Of the engine's
+ *   persistent state only kv_start / valid_count of rows 2b, 2b + 1 and the cache slabs of those rows change.  Refuses (before anything
+ *   is enqueued) a prompt beyond the reservation, an expert parallel engine, a row outside the batch.
+ * umoe_engine_admit_external: the caller has written slots [0, T) of rows 2b, 2b + 1 of the K / V slabs; sets the state only. */
+int umoe_engine_reserve(umoe_engine* e, int n_tok);
+int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* x, const uint8_t* valid_host, int T,
+                      int prefill_step, int prefix_len, umoe_stream_t stream);
+int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step,
+                               int prefix_len, umoe_stream_t stream);
 /* Expert parallel decode (ep_size > 1).  umoe_engine_set_layer then takes exp_gu / exp_dn of the n_real / ep_size LOCAL experts
  * (global ids [ep_rank * E_loc, (ep_rank + 1) * E_loc), core.py:505) and EITHER the row-major tensors of ALL n_real experts (the
  * engine then prefills replicated on its tiled path) OR no row-major expert tensors at all (rm_exp_* NULL: the rank holds its local

@@ -115,7 +115,7 @@ class SampleArgs(C.Structure):
     _fields_ = [("logits", vp), ("B", i32), ("C", i32), ("V", i32), ("cfg_scale", f32), ("temperature", f32),
                 ("top_p", f32), ("eos_mul", f32), ("top_k", i32), ("eos", i32), ("enable_eos", i32),
                 ("min_tokens", i32), ("step", vp), ("do_sample", i32), ("seed", u64), ("pred", vp), ("probs_out", vp),
-                ("row_params", vp)]
+                ("row_clock", vp), ("row_params", vp)]
 
 
 class EngineCfg(C.Structure):
@@ -137,7 +137,7 @@ class LayerWeights(C.Structure):
 
 class DecodeIO(C.Structure):
     _fields_ = [("tokens", vp), ("state", vp), ("cfg_scale", f32), ("temperature", f32), ("top_p", f32),
-                ("eos_mul", f32), ("top_k", i32), ("do_sample", i32), ("min_tokens", i32), ("seed", u64), ("row_params", vp)]
+                ("eos_mul", f32), ("top_k", i32), ("do_sample", i32), ("min_tokens", i32), ("seed", u64), ("row_clock", vp), ("row_params", vp)]
 
 
 EXPORTS = [
@@ -155,6 +155,7 @@ EXPORTS = [
     "umoe_ep_ipc_export", "umoe_ep_ipc_open", "umoe_ep_ipc_close", "umoe_engine_ep_region", "umoe_engine_ep_connect",
     "umoe_engine_ep_error", "umoe_token_drop", "umoe_router_bwd_drop", "umoe_router_bwd_ex", "umoe_dac_conv1d", "umoe_dac_conv_transpose1d", "umoe_dac_resample", "umoe_vision_rope", "umoe_vision_attn", "umoe_swiglu_pair", "umoe_gelu", "umoe_engine_prefill_pos", "umoe_engine_set_probe", "umoe_engine_info", "umoe_engine_prefill_external", "umoe_engine_set_layer_fp8", "umoe_fp8_convert_probe",
     "umoe_dac_conv1d_win", "umoe_dac_conv_transpose1d_win", "umoe_rvq_from_delayed", "umoe_delay_step_rows",
+    "umoe_delay_step_clock", "umoe_engine_reserve", "umoe_engine_admit", "umoe_engine_admit_external",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -262,6 +263,12 @@ def lib():
         if not hasattr(L, "umoe_delay_step_rows"):
             raise UmoeError(f"{_SO} predates this package (no umoe_delay_step_rows): rebuild it (`make -C unimoe_audio_amd/csrc`)")
         L.umoe_delay_step_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+        if not hasattr(L, "umoe_engine_admit"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_engine_admit): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_delay_step_clock.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.umoe_engine_reserve.argtypes = [vp, i32]
+        L.umoe_engine_admit.argtypes = [vp, C.POINTER(DecodeIO), i32, vp, vp, i32, i32, i32, vp]
+        L.umoe_engine_admit_external.argtypes = [vp, C.POINTER(DecodeIO), i32, vp, i32, i32, i32, vp]
         L.umoe_rvq_from_codes.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_nearest.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.umoe_codec_ce_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]

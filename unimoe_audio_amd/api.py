@@ -364,6 +364,74 @@ class UniMoEAudio:
         audios = self.generate_codes(ids, mask, codec, col("max_audio_seconds"), col("min_audio_seconds"), **gen)
         return self._finish(audios, output_dir, col("save_name"))
 
+    @torch.no_grad()
+    def serve(self, requests, slots: int = 8, output_dir: Optional[str] = "./", poll_every: int = 16, max_prompt_tokens: int = 512,
+              max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None):
+        """Continuous batching: a generator that takes SpeechRequest / MusicRequest objects from any iterable (read lazily) and yields
+        (index, wav path) as each request ends -- index = the request's position in `requests`, the file is
+        `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows decode together;
+        a request is admitted into a row as soon as one is free (first in, first out, checked every `poll_every` steps), while the other
+        rows keep decoding (DecodeEngine.admit, unimoe_audio_amd/serve.py).  Each request's prompt pair is built as generate_batch builds it
+        and keeps its own length.  The engine is sized once: max_prompt_tokens per prompt, max_audio_seconds per request; a request beyond
+        either is refused when its turn comes.  Not for expert-parallel engines, video prompts or streamed chunks."""
+        from .serve import MAX_SLOTS, Scheduler
+        if not 1 <= slots <= MAX_SLOTS:
+            raise ValueError(f"serve: slots must be 1..{MAX_SLOTS} (got {slots})")
+        cfg = self.model.config
+        eng = self.model.engine(slots, int(max_prompt_tokens), 50 * int(max_audio_seconds), expert_weights=expert_weights)
+        eng.start_serving(int(max_prompt_tokens))
+        app = self
+
+        class Rows:
+            """the engine as unimoe_audio_amd.serve.Scheduler drives it"""
+            held = {}
+
+            def admit(self, row, r):
+                if isinstance(r, SpeechRequest):
+                    enc, codec = app._speech_prompt(r.transcription, r.prompt_transcription, r.prompt_wav, None, None, r.prompt_codec)
+                elif isinstance(r, MusicRequest):
+                    enc, codec = app._music_prompt(r.caption), None
+                else:
+                    raise TypeError(f"serve: a SpeechRequest or a MusicRequest, not {type(r).__name__}")
+                if enc.input_ids.shape[0] != 2:
+                    raise ValueError("serve: one text per request")
+                if r.max_audio_seconds > max_audio_seconds:
+                    raise ValueError(f"serve: a request of {r.max_audio_seconds} s on an engine sized for {max_audio_seconds} s (max_audio_seconds)")
+                x = app.model.calculate_input_embedding(enc.input_ids.to(app.device), None if codec is None else codec.to(app.device))
+                prefill, steps = prepare_audio_prompt(cfg, [None])
+                eng.admit(row, x.reshape(-1, x.shape[-1]).contiguous(), enc.attention_mask, prefill[0], steps[0],
+                          max_tokens=50 * r.max_audio_seconds, min_tokens=50 * r.min_audio_seconds, cfg_scale=r.cfg_scale,
+                          temperature=r.temperature, top_p=r.top_p, top_k=r.cfg_filter_top_k, eos_mul=r.eos_prob_mul_factor,
+                          do_sample=r.do_sample, seed=r.seed)
+                self.held[row] = r
+
+            def steps(self, n):
+                for _ in range(n):
+                    eng.step(use_graph)
+
+            def poll(self):
+                return eng.poll()
+
+            def row_done(self, state, row):
+                return eng.row_done(state, row)
+
+            def take(self, row):
+                codes, length = eng.take(row)
+                return self.held.pop(row), codes, length
+
+        sched = Scheduler(Rows(), slots, poll_every)
+        self.served_rows = {}                              # request index -> the row it decoded in (of the last / the running serve())
+        for index, (r, codes, length) in sched.run(requests):
+            self.served_rows.update({i: row for i, row, _ in sched.admitted})
+            audio = generate_output(cfg, codes[None], torch.tensor([length], device=codes.device))[0]
+            if output_dir is None:
+                yield index, audio
+                continue
+            os.makedirs(output_dir, exist_ok=True)
+            path = os.path.join(output_dir, f"generated_{r.save_name}_{index}.wav")
+            self.dac.decode(audio.transpose(0, 1).unsqueeze(0), save_path=path, min_duration=1)
+            yield index, path
+
     def video_text_to_music(self, video, caption: Union[str, List[str]], output_dir: str = "./", max_audio_seconds: int = 20,
                             min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                             save_name: str = "video_music", cfg_scale: float = 10.0, eos_prob_mul_factor: float = 0.6, do_sample: bool = True,

@@ -75,6 +75,10 @@ struct umoe_engine {
     int32_t* all_mask = nullptr;
     int64_t* all_topk = nullptr;
     int T_prompt = 0;
+    // admission into a running batch (umoe_engine_admit): the prefill body runs over the 2 cache rows from adm_row0 (-1: the whole batch)
+    int adm_row0 = -1;
+    int32_t* adm_q0 = nullptr;   // [2] zeros: q_pos0 of an admission prefill (the batch's own q_pos0 belongs to the decode steps)
+    int reserved_tok = 0;        // umoe_engine_reserve: the workspace does not move for prompts up to this many tokens
     // per-layer probe of the parity tests (umoe_engine_set_probe): eager steps only
     const uint16_t* probe_teach = nullptr;
     uint16_t *probe_x1 = nullptr, *probe_x = nullptr, *probe_logits = nullptr;
@@ -199,6 +203,7 @@ static int ensure_workspace(umoe_engine* e, int n_tok) {
 // group table for a pass over n_tok tokens
 static bool dense_mode(const umoe_engine* e, int n_tok) {
     if (e->ep_decode(n_tok)) return true;   // expert parallel decode IS the dense layout: every rank's rows visit every expert
+    if (e->adm_row0 >= 0) return false;     // an admission prefill of rows tokens is a prefill: ragged dispatch, never the decode launches
     return e->dense_experts && n_tok == e->c.rows && n_tok <= 16 && n_tok >= e->dense_min_rows;
 }
 
@@ -365,6 +370,7 @@ extern "C" void umoe_engine_destroy(umoe_engine* e) {
     if (e->graph) (void)hipGraphDestroy(e->graph);
     for (hipEvent_t x : e->ev) (void)hipEventDestroy(x);
     if (e->ws) (void)hipFree(e->ws);
+    if (e->adm_q0) (void)hipFree(e->adm_q0);
     if (e->ep_region) (void)hipFree(e->ep_region);
     if (e->ep_words) (void)hipFree(e->ep_words);
     if (e->epf_tasks) (void)hipFree(e->epf_tasks);
@@ -789,7 +795,8 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     const LayerDev& L = e->layers[l];
     const umoe_group_t* g = e->d_groups + (size_t)l * GPL;
     const umoe_group_t* gh = e->h_groups.data() + (size_t)l * GPL;   // same table, host side
-    const size_t kv_l = (size_t)l * c.rows * c.kv_heads * c.Lmax * c.head_dim;
+    const bool adm = e->adm_row0 >= 0;       // admission prefill: cache rows [adm_row0, adm_row0 + 2) only
+    const size_t kv_l = ((size_t)l * c.rows + (adm ? e->adm_row0 : 0)) * c.kv_heads * c.Lmax * c.head_dim;
     int rc;
     // 1. RMSNorm + QKV (+bias)                                   model.py:227, Qwen2_5_VLAttention q/k/v_proj
     umoe_gemm_args a{};
@@ -850,7 +857,8 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     // 3. attention (decode: mRoPE of q / new k and the KV append are fused into the kernel)
     umoe_attn_args t{};
     t.q = e->q_r; t.k_cache = r.k_cache; t.v_cache = r.v_cache; t.kv_start = e->kv_start; t.q_pos0 = e->q_pos0;
-    t.rows = c.rows; t.nq = T; t.H = c.heads; t.KVH = c.kv_heads; t.hd = c.head_dim; t.Lmax = c.Lmax; t.splits = splits;
+    t.rows = c.rows; t.nq = T;
+    if (adm) { t.kv_start = e->kv_start + e->adm_row0; t.q_pos0 = e->adm_q0; t.rows = 2; } t.H = c.heads; t.KVH = c.kv_heads; t.hd = c.head_dim; t.Lmax = c.Lmax; t.splits = splits;
     t.scale = 1.0f / sqrtf((float)c.head_dim); t.part_o = e->part_o; t.part_ml = e->part_ml; t.out = e->attn_out;
     if (fuse_rope) {
         t.qkv_raw = e->qkv; t.cos_tab = e->cos_tab; t.sin_tab = e->sin_tab; t.pos3 = e->pos3;
@@ -875,7 +883,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     }
     if (rc) return rc;
     PROF(K_OPROJ);
-    if (e->probe_x1 && n_tok == c.rows)
+    if (e->probe_x1 && n_tok == c.rows && !adm)
         UMOE_HIP(hipMemcpyAsync(e->probe_x1 + (size_t)l * c.rows * D, e->x1, (size_t)c.rows * D * 2, hipMemcpyDeviceToDevice, s));
     if (e->ep_decode(n_tok)) return run_moe_ep(e, l, n_tok, s);
     // 5. RMSNorm + router                                         model.py:240, core.py:246-291
@@ -886,7 +894,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     ra.fixed_top_k = c.fixed_top_k; ra.jitter_eps = c.jitter_eps; ra.rms_eps = c.rms_eps;
     ra.logits_out = e->r_logits; ra.top_k = e->r_topk; ra.sel = e->r_sel; ra.expert_mask = e->r_mask;
     ra.routing_w = e->r_routing; ra.global_w = e->r_global; ra.moe_w = e->r_moe;
-    if (n_tok == c.rows) {  // keep per-layer statistics of decode steps for the parity tests
+    if (n_tok == c.rows && !adm) {  // keep per-layer statistics of decode steps for the parity tests
         ra.expert_mask = e->all_mask + (size_t)l * c.rows * E;
         ra.top_k = e->all_topk + (size_t)l * c.rows;
     }
@@ -1155,22 +1163,29 @@ extern "C" int umoe_engine_prefill_external(umoe_engine* e, const uint8_t* valid
 
 // ------------------------------------------------------------------------------------ decode step
 // tokens[b][step] -> tok_in (CFG row doubling, model.py:945), positions / cache slots from device state
+// clk (umoe_decode_io.row_clock, {step_off[b], t_prompt[b]}): row b reads its token, cache slot and rope position on its local clock
+// step - step_off[b]; the T_prompt argument is then not read, so a captured step survives admissions of other prompt lengths.  A row
+// whose countdown is 0 (ended, or never used) is PARKED: its key range is the one slot kv_start[row], so its attention workgroups read
+// one key per layer instead of up to Lmax (its outputs are never read).
 __global__ void step_prep_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ state, int B, int C,
                                  int Tmax, int T_prompt, int Lmax, const int32_t* __restrict__ valid_count,
-                                 int32_t* tok_in, int32_t* pos3, int32_t* kv_pos, int32_t* q_pos0, uint32_t* ep_step) {
+                                 int32_t* tok_in, int32_t* pos3, int32_t* kv_pos, int32_t* q_pos0, uint32_t* ep_step,
+                                 const int32_t* __restrict__ clk, const int32_t* __restrict__ kv_start) {
     const int row = blockIdx.x, b = row >> 1;
     if (row == 0 && threadIdx.x == 0) {
         ep_step[0] += 1u;   // epoch base of this step's in-launch hand-offs (read by later launches; a prefill bumps it too)
         ep_step[2] += 1u;   // decode steps only: base of the expert-parallel return counters' rounds (umoe_moe_ep.hip)
     }
-    const int step = state[4 * B];
-    const int n_dec = step - state[4 * B + 4];  // state[4B+4] = dec_step of the first decode call
+    const int step = state[4 * B] - (clk ? clk[2 * b] : 0);
+    // state[4B+4] = dec_step of the first decode call; local clock: the row's first decode step is prefill_step[b] - 1
+    const int n_dec = step - (clk ? state[3 * B + b] - 1 : state[4 * B + 4]);
     const int ts = min(max(step, 0), Tmax - 1);
     if ((int)threadIdx.x < C) tok_in[row * C + threadIdx.x] = tokens[((size_t)b * Tmax + ts) * C + threadIdx.x];
     if (threadIdx.x == 0) {
         const int rows = 2 * B;
-        const int slot = min(T_prompt + n_dec, Lmax - 1);
-        const int p = valid_count[row] + n_dec;
+        const bool parked = clk && state[B + b] == 0;
+        const int slot = parked ? kv_start[row] : min(max((clk ? clk[2 * b + 1] : T_prompt) + n_dec, 0), Lmax - 1);
+        const int p = parked ? 0 : valid_count[row] + n_dec;
         pos3[row] = p;
         pos3[rows + row] = p;
         pos3[2 * rows + row] = p;
@@ -1185,7 +1200,8 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     int rc;
     PROF(-1);
     step_prep_kernel<<<dim3((unsigned)c.rows), 64, 0, s>>>(io->tokens, io->state, B, C, c.Tmax, e->T_prompt, c.Lmax,
-                                                           e->valid_count, e->tok_in, e->pos3, e->kv_pos, e->q_pos0, e->ep_words);
+                                                           e->valid_count, e->tok_in, e->pos3, e->kv_pos, e->q_pos0, e->ep_words,
+                                                           io->row_clock, e->kv_start);
     UMOE_LAUNCH_CHECK();
     if ((rc = umoe_codec_embed_sum(e->tok_in, e->codec_emb, c.rows, C, V, c.hidden, e->x, s))) return rc;
     if ((rc = umoe_rmsnorm_residual_fwd(e->x, nullptr, e->layers[0].w.in_norm, c.rms_eps, c.rows, c.hidden, nullptr, e->hin, s)))
@@ -1217,11 +1233,148 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     sa.top_p = io->top_p; sa.eos_mul = io->eos_mul; sa.top_k = io->top_k; sa.eos = c.eos; sa.min_tokens = io->min_tokens;
     sa.step = io->state + 4 * B; sa.do_sample = io->do_sample; sa.seed = io->seed; sa.pred = e->pred;
     sa.row_params = io->row_params;      // per-request settings (NULL: the scalars above); every rank samples its own rows from its own io
+    sa.row_clock = io->row_clock;        // per-row clocks (NULL: the one step word)
     if ((rc = umoe_codec_head_cfg_sample(&sa, s))) return rc;
     PROF(K_SAMPLE);
-    rc = umoe_delay_step_rows(e->pred, io->tokens, io->state, e->d_delay, B, C, c.Tmax, c.eos, c.pad, e->max_delay, io->row_params, s);
+    rc = umoe_delay_step_clock(e->pred, io->tokens, io->state, e->d_delay, B, C, c.Tmax, c.eos, c.pad, e->max_delay, io->row_params, io->row_clock, s);
     PROF(K_DELAY);
     return rc;
+}
+
+
+// ------------------------------------------------------------------------------------ admission into a running batch
+// Batch entry b starts a new request at the global step the stream has reached: its clock entry and its bookkeeping words are reset on
+// the device, in stream order between two decode steps, so the host never reads the step word.  Vector stores only.
+__global__ __launch_bounds__(256) void row_admit_kernel(int32_t* tokens, int32_t* state, int32_t* clk, int b, int B, int C, int Tmax,
+                                                        int prefill_step, int prefix_len, int T) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int g = state[4 * B];
+        clk[2 * b] = g - (prefill_step - 1);
+        clk[2 * b + 1] = T;
+        state[b] = 0;                   // eos_detected
+        state[B + b] = -1;              // countdown
+        state[2 * B + b] = -1;          // finished
+        state[3 * B + b] = prefill_step;
+        state[4 * B + 2] = 0;           // all_done: a row is live again
+    }
+    const int n = (Tmax - prefix_len) * C;          // the slots behind the request's prefix are to be generated
+    int32_t* t = tokens + ((size_t)b * Tmax + prefix_len) * C;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) t[i] = -1;
+}
+
+extern "C" int umoe_engine_reserve(umoe_engine* e, int n_tok) {
+    UMOE_REQUIRE(e && n_tok > 0, "umoe_engine_reserve: bad argument");
+    UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_reserve: admission is not supported expert parallel (ep_size %d)", e->c.ep_size);
+    UMOE_REQUIRE(e->final_norm, "umoe_engine_reserve: globals not set");
+    int rc;
+    if ((rc = ensure_workspace(e, n_tok > e->c.rows ? n_tok : e->c.rows))) return rc;
+    if (!e->adm_q0) {
+        UMOE_HIP(hipMalloc(&e->adm_q0, 2 * sizeof(int32_t)));
+        UMOE_HIP(hipMemset(e->adm_q0, 0, 2 * sizeof(int32_t)));
+    }
+    e->cb_pending = false;
+    if ((rc = build_groups(e, e->c.rows, nullptr))) return rc;
+    e->reserved_tok = e->cap_tok;
+    return 0;
+}
+
+// checks of an admission, all before anything is enqueued; fills start / vc (kv_start, valid_count) of the two rows
+static int admit_check(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step, int prefix_len,
+                       int32_t* start, int32_t* vc, const char* who) {
+    UMOE_REQUIRE(e && io && io->tokens && io->state && valid_host && T > 0, "%s: bad argument", who);
+    const umoe_engine_cfg& c = e->c;
+    UMOE_REQUIRE(c.ep_size == 1, "%s: admission is not supported expert parallel (ep_size %d)", who, c.ep_size);
+    UMOE_REQUIRE(io->row_clock, "%s: the batch has no per-row clocks (umoe_decode_io.row_clock)", who);
+    UMOE_REQUIRE(e->reserved_tok > 0, "%s: umoe_engine_reserve first", who);
+    UMOE_REQUIRE(2 * T <= e->reserved_tok, "%s: a prompt of %d tokens per row is larger than the reservation (%d tokens for the pair)", who, T, e->reserved_tok);
+    UMOE_REQUIRE(b >= 0 && b < c.rows / 2, "%s: row %d outside the batch of %d", who, b, c.rows / 2);
+    UMOE_REQUIRE(T < c.Lmax, "%s: prompt length %d does not fit Lmax %d", who, T, c.Lmax);
+    UMOE_REQUIRE(prefill_step >= 1 && prefill_step <= prefix_len && prefix_len <= c.Tmax,
+                 "%s: need 1 <= prefill_step (%d) <= prefix_len (%d) <= Tmax (%d)", who, prefill_step, prefix_len, c.Tmax);
+    UMOE_REQUIRE(!e->probe_on(), "%s: not with the per-layer probe", who);
+    for (int r = 0; r < 2; ++r) {
+        int cnt = 0, first = T;
+        for (int t = 0; t < T; ++t) {
+            const int v = valid_host[(size_t)r * T + t] != 0;
+            cnt += v;
+            if (v && first == T) first = t;
+        }
+        for (int t = first; t < T; ++t) UMOE_REQUIRE(valid_host[(size_t)r * T + t], "%s: row %d is not left-padded", who, r);
+        UMOE_REQUIRE(cnt > 0, "%s: row %d of the pair has no valid token", who, r);
+        start[r] = first;
+        vc[r] = cnt;
+        UMOE_REQUIRE(cnt + c.Lmax - T < e->max_pos, "%s: rope table too short", who);
+    }
+    return 0;
+}
+
+static int admit_state(umoe_engine* e, const umoe_decode_io* io, int b, int T, int prefill_step, int prefix_len, const int32_t* start, const int32_t* vc,
+                       hipStream_t s) {
+    const umoe_engine_cfg& c = e->c;
+    UMOE_HIP(hipMemcpyAsync(e->kv_start + 2 * b, start, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    UMOE_HIP(hipMemcpyAsync(e->valid_count + 2 * b, vc, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    const int n = (c.Tmax - prefix_len) * c.codec_channels;
+    row_admit_kernel<<<dim3((unsigned)(n > 256 * 64 ? 64 : ceil_div(n > 0 ? n : 1, 256))), 256, 0, s>>>(io->tokens, io->state, io->row_clock, b, c.rows / 2,
+                                                                                                     c.codec_channels, c.Tmax, prefill_step, prefix_len, T);
+    UMOE_LAUNCH_CHECK();
+    UMOE_HIP(hipStreamSynchronize(s));  // start / vc are the caller's stack
+    return 0;
+}
+
+extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* x, const uint8_t* valid_host, int T, int prefill_step,
+                                 int prefix_len, umoe_stream_t stream) {
+    int32_t start[2], vc[2];
+    int rc;
+    if ((rc = admit_check(e, io, b, valid_host, T, prefill_step, prefix_len, start, vc, "umoe_engine_admit"))) return rc;
+    UMOE_REQUIRE(x, "umoe_engine_admit: null prompt");
+    const umoe_engine_cfg& c = e->c;
+    hipStream_t s = (hipStream_t)stream;
+    const int n_tok = 2 * T;
+    // positions cumsum(mask) - 1, masked -> 1; kv slot = t (prefill_state, for the pair)
+    std::vector<int32_t> pos((size_t)3 * n_tok), kvp(n_tok);
+    for (int r = 0; r < 2; ++r) {
+        int cnt = 0;
+        for (int t = 0; t < T; ++t) {
+            const int v = valid_host[(size_t)r * T + t] != 0;
+            cnt += v;
+            const int p = v ? cnt - 1 : 1;
+            for (int k = 0; k < 3; ++k) pos[(size_t)k * n_tok + r * T + t] = p;
+            kvp[r * T + t] = t;
+        }
+    }
+    e->adm_row0 = 2 * b;
+    e->groups_for_tok = -1;              // (a table of the same token count in decode shape is not this pass's table)
+    rc = build_groups(e, n_tok, s);
+    if (!rc) {
+        rc = [&]() -> int {
+            UMOE_HIP(hipMemcpyAsync(e->pos3, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
+            UMOE_HIP(hipMemcpyAsync(e->kv_pos, kvp.data(), kvp.size() * 4, hipMemcpyHostToDevice, s));
+            UMOE_HIP(hipMemcpyAsync(e->kv_start + 2 * b, start, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            UMOE_HIP(hipMemcpyAsync(e->x, x, (size_t)n_tok * c.hidden * 2, hipMemcpyDeviceToDevice, s));
+            int r2;
+            if ((r2 = umoe_rmsnorm_residual_fwd(e->x, nullptr, e->layers[0].w.in_norm, c.rms_eps, n_tok, c.hidden, nullptr, e->hin, s))) return r2;
+            e->cb_pending = false;
+            epoch_bump_kernel<<<1, 64, 0, s>>>(e->ep_words);
+            UMOE_LAUNCH_CHECK();
+            for (int l = 0; l < c.layers; ++l)
+                if ((r2 = run_layer(e, l, n_tok, T, 1, s))) return r2;
+            return 0;
+        }();
+    }
+    e->adm_row0 = -1;
+    e->cb_pending = false;
+    e->groups_for_tok = -1;
+    const int rg = build_groups(e, c.rows, s);      // back to decode shape (synchronises: pos / kvp stay alive until here)
+    if (rc) return rc;
+    if (rg) return rg;
+    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, s);
+}
+
+extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step,
+                                          int prefix_len, umoe_stream_t stream) {
+    int32_t start[2], vc[2];
+    if (int rc = admit_check(e, io, b, valid_host, T, prefill_step, prefix_len, start, vc, "umoe_engine_admit_external")) return rc;
+    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, (hipStream_t)stream);
 }
 
 // An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch: the box grid and the
@@ -1248,7 +1401,8 @@ static int fp8_step_check(umoe_engine* e) {
 
 extern "C" int umoe_engine_decode_step(umoe_engine* e, const umoe_decode_io* io, umoe_stream_t stream) {
     UMOE_REQUIRE(e && io && io->tokens && io->state, "umoe_engine_decode_step: null argument");
-    UMOE_REQUIRE(e->T_prompt > 0, "umoe_engine_decode_step: prefill first");
+    UMOE_REQUIRE(e->T_prompt > 0 || (io->row_clock && e->reserved_tok > 0), "umoe_engine_decode_step: prefill first");
+    UMOE_REQUIRE(!io->row_clock || e->c.ep_size == 1, "umoe_engine_decode_step: per-row clocks are not supported expert parallel");
     if (int rc = fp8_step_check(e)) return rc;
     return enqueue_step(e, io, (hipStream_t)stream);
 }
@@ -1279,7 +1433,8 @@ extern "C" int umoe_engine_profile_step(umoe_engine* e, const umoe_decode_io* io
 
 extern "C" int umoe_engine_capture(umoe_engine* e, const umoe_decode_io* io, umoe_stream_t stream) {
     UMOE_REQUIRE(e && io && io->tokens && io->state, "umoe_engine_capture: null argument");
-    UMOE_REQUIRE(e->T_prompt > 0, "umoe_engine_capture: prefill first");
+    UMOE_REQUIRE(e->T_prompt > 0 || (io->row_clock && e->reserved_tok > 0), "umoe_engine_capture: prefill first");
+    UMOE_REQUIRE(!io->row_clock || e->c.ep_size == 1, "umoe_engine_capture: per-row clocks are not supported expert parallel");
     UMOE_REQUIRE(!e->probe_on(), "umoe_engine_capture: the per-layer probe works on eager steps only (umoe_engine_set_probe)");
     if (int rc = fp8_step_check(e)) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -1334,6 +1489,9 @@ extern "C" const void* umoe_engine_buffer(umoe_engine* e, const char* name, size
         {"counts", e->counts, (size_t)c.n_real * 4},
         {"xg", e->xg, (size_t)(c.ep_size > 1 ? c.ep_size : 0) * c.rows * c.hidden * 2},
         {"ep_words", e->ep_words, 8},
+        {"q_pos0", e->q_pos0, (size_t)c.rows * 4},
+        {"kv_start", e->kv_start, (size_t)c.rows * 4},
+        {"valid_count", e->valid_count, (size_t)c.rows * 4},
     };
     for (const Item& it : items)
         if (!strcmp(it.n, name)) {

@@ -503,7 +503,8 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const umoe_sample_args 
     const int top_k = rp ? rp->top_k : a.top_k, do_sample = rp ? rp->do_sample : a.do_sample;
     const int min_tokens = rp ? rp->min_tokens : a.min_tokens;
     const uint64_t seed = rp ? rp->seed : a.seed;
-    const int step = a.step ? *a.step : 0;
+    // the row's local clock (umoe_sample_args.row_clock): b is workgroup-uniform, so these stay scalar loads like row_params
+    const int step = (a.step ? *a.step : 0) - (a.row_clock ? a.row_clock[2 * b] : 0);
     const bool enable_eos = a.step ? (min_tokens < 0 || step >= min_tokens) : (a.enable_eos != 0);
     const float* un = a.logits + ((size_t)(2 * b) * a.C + c) * V;
     const float* co = a.logits + ((size_t)(2 * b + 1) * a.C + c) * V;
@@ -778,6 +779,7 @@ extern "C" int umoe_codec_head_cfg_sample(const umoe_sample_args* a, umoe_stream
     const size_t lds = (size_t)3 * a->V * sizeof(float);
     UMOE_REQUIRE(lds <= 60 * 1024 && a->V <= 2048, "umoe_codec_head_cfg_sample: vocabulary %d too large for the LDS sampler", a->V);
     UMOE_REQUIRE(((size_t)a->row_params & 7) == 0, "umoe_codec_head_cfg_sample: row_params must be 8-byte aligned");
+    UMOE_REQUIRE(!a->row_clock || a->step, "umoe_codec_head_cfg_sample: row_clock needs the step word");
     cfg_sample_kernel<<<dim3((unsigned)(a->B * a->C)), 256, lds, (hipStream_t)stream>>>(*a);
     UMOE_LAUNCH_CHECK();
     return 0;
@@ -785,22 +787,25 @@ extern "C" int umoe_codec_head_cfg_sample(const umoe_sample_args* a, umoe_stream
 
 // ------------------------------------------------------------------------------------ delay / EOS step
 // state layout: eos_detected[B], countdown[B], finished[B], prefill_step[B], {step, max_tokens, all_done, bos_over}
+// clk (umoe_delay_step_clock): {step_off[b], t_prompt[b]} per row; row b then lives at cur_b = step - step_off[b] + 1
 __global__ __launch_bounds__(256) void delay_step_kernel(int64_t* pred, int32_t* tokens, int32_t* state,
                                                          const int32_t* __restrict__ delay, int B, int C, int Tmax,
-                                                         int eos, int pad, int md, const umoe_row_params* __restrict__ rp) {
+                                                         int eos, int pad, int md, const umoe_row_params* __restrict__ rp,
+                                                         const int32_t* __restrict__ clk) {
     int32_t* eos_det = state;
     int32_t* countdown = state + B;
     int32_t* finished = state + 2 * B;
     const int32_t* prefill = state + 3 * B;
     int32_t* sc = state + 4 * B;
     __shared__ int s_all_done, s_bos_over;
+    __shared__ int s_cur[256];      // the slot row b writes this step; -1: none (clock mode: a row that was parked at entry)
     const int tid = threadIdx.x;
     const int dec_step = sc[0], max_tokens = sc[1];
     // the reference checks `(eos_countdown == 0).all()` and `dec_step < max_tokens` at the loop head
     if (tid == 0) {
         int done = 1;
         for (int b = 0; b < B; ++b) done &= (countdown[b] == 0);
-        s_all_done = done || (dec_step >= max_tokens);
+        s_all_done = done || (!clk && dec_step >= max_tokens);     // clock mode: rows come and go, each ends by its own max_tokens
         s_bos_over = sc[3];
     }
     __syncthreads();
@@ -808,12 +813,13 @@ __global__ __launch_bounds__(256) void delay_step_kernel(int64_t* pred, int32_t*
         if (tid == 0) sc[2] = 1;
         return;
     }
-    const int cur = dec_step + 1;
     __syncthreads();
     if (tid < B) {  // per-sample EOS logic (model.py:1173-1183)
         const int b = tid;
         const int cd = countdown[b];
         const bool active = cd != 0;
+        const int cur = dec_step - (clk ? clk[2 * b] : 0) + 1;
+        s_cur[b] = (clk && !active) ? -1 : cur;
         const int row_max = rp ? rp[b].max_tokens : max_tokens;     // the row's own length; the loop bound above stays the largest
         const bool trig = active && ((!eos_det[b] && pred[(size_t)b * C] == eos) || (cur >= row_max - md));
         if (trig) eos_det[b] = 1;
@@ -836,34 +842,42 @@ __global__ __launch_bounds__(256) void delay_step_kernel(int64_t* pred, int32_t*
     if (tid < B && countdown[tid] > 0) countdown[tid] -= 1;
     if (tid == 0 && !s_bos_over) {  // model.py:1199-1200
         int over = 1;
-        for (int b = 0; b < B; ++b) over &= (cur - prefill[b] >= md);
+        for (int b = 0; b < B; ++b) over &= (dec_step - (clk ? clk[2 * b] : 0) + 1 - prefill[b] >= md);
         sc[3] = over;
     }
     __syncthreads();
     // DecoderOutput.update_one (utils.py:290-298): keep prompt/BOS entries, fill the -1 ones
-    if (cur < Tmax)
-        for (int i = tid; i < B * C; i += blockDim.x) {
-            const int b = i / C, c = i - b * C;
-            int32_t* t = tokens + ((size_t)b * Tmax + cur) * C + c;
-            if (*t == -1) *t = (int32_t)pred[i];
-        }
+    for (int i = tid; i < B * C; i += blockDim.x) {
+        const int b = i / C, c = i - b * C;
+        const int cur = s_cur[b];
+        if (cur < 0 || cur >= Tmax) continue;
+        int32_t* t = tokens + ((size_t)b * Tmax + cur) * C + c;
+        if (*t == -1) *t = (int32_t)pred[i];
+    }
     __syncthreads();
     if (tid == 0) {
         sc[0] = dec_step + 1;
         int done = 1;
         for (int b = 0; b < B; ++b) done &= (countdown[b] == 0);
-        sc[2] = (done || (dec_step + 1 >= max_tokens)) ? 1 : 0;
+        sc[2] = (done || (!clk && dec_step + 1 >= max_tokens)) ? 1 : 0;
     }
+}
+
+extern "C" int umoe_delay_step_clock(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C,
+                                     int Tmax, int eos, int pad, int max_delay, const umoe_row_params* row_params,
+                                     const int32_t* row_clock, umoe_stream_t stream) {
+    UMOE_REQUIRE(pred && tokens && state && delay && B > 0 && B <= 256 && C > 0, "umoe_delay_step: bad argument (B=%d)", B);
+    UMOE_REQUIRE(((size_t)row_params & 7) == 0, "umoe_delay_step: row_params must be 8-byte aligned");
+    UMOE_REQUIRE(((size_t)row_clock & 3) == 0, "umoe_delay_step: row_clock must be 4-byte aligned");
+    delay_step_kernel<<<1, 256, 0, (hipStream_t)stream>>>(pred, tokens, state, delay, B, C, Tmax, eos, pad, max_delay, row_params, row_clock);
+    UMOE_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int umoe_delay_step_rows(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C,
                                     int Tmax, int eos, int pad, int max_delay, const umoe_row_params* row_params,
                                     umoe_stream_t stream) {
-    UMOE_REQUIRE(pred && tokens && state && delay && B > 0 && B <= 256 && C > 0, "umoe_delay_step: bad argument (B=%d)", B);
-    UMOE_REQUIRE(((size_t)row_params & 7) == 0, "umoe_delay_step: row_params must be 8-byte aligned");
-    delay_step_kernel<<<1, 256, 0, (hipStream_t)stream>>>(pred, tokens, state, delay, B, C, Tmax, eos, pad, max_delay, row_params);
-    UMOE_LAUNCH_CHECK();
-    return 0;
+    return umoe_delay_step_clock(pred, tokens, state, delay, B, C, Tmax, eos, pad, max_delay, row_params, nullptr, stream);
 }
 
 extern "C" int umoe_delay_step(int64_t* pred, int32_t* tokens, int32_t* state, const int32_t* delay, int B, int C,

@@ -542,6 +542,8 @@ class DecodeEngine:
         self.state = None
         self.io = None
         self.row_params = None
+        self.row_clock = None
+        self.reserved_prompt = 0
         self.captured = False
 
     def _k(self, t):
@@ -702,6 +704,7 @@ class DecodeEngine:
         self.prefill_steps, self.max_tokens = list(prefill_steps), max_tokens
         # the table lives as long as the io that points at it (a captured step graph records the pointer)
         self.row_params = None if table is None else ops.row_params_tensor(table, self.dev)
+        self.row_clock, self.reserved_prompt = None, 0
         self.io = L.DecodeIO(tokens=tok.data_ptr(), state=self.state.data_ptr(), cfg_scale=cfg_scale, temperature=temperature,
                              top_p=top_p, eos_mul=eos_mul, top_k=-1 if top_k is None else int(top_k), do_sample=int(bool(do_sample)),
                              min_tokens=-1 if min_tokens is None else int(min_tokens), seed=seed,
@@ -842,6 +845,123 @@ class DecodeEngine:
                 seg = tokens[i, self.prefill_steps[i]: self.prefill_steps[i] + n]
                 out[i, : seg.shape[0]] = seg.long()
         return out, lengths.to(self.dev), tokens
+
+    # ---- rows that come and go: per-row clocks and admission into a batch that is decoding -------------------------
+    def _refuse_clock(self, what: str):
+        if (self.ep is not None and self.ep.size > 1) or self.ep_size > 1 or getattr(self, "sharded", False):
+            raise L.UmoeError(f"{what}: per-row clocks and admission are not supported with expert-parallel engines")
+
+    def use_row_clock(self):
+        """After start_decode: the same batch on per-row clocks (umoe_decode_io.row_clock), every row at offset 0 behind the prompt of
+        the prefill.  With equal prefill steps the tokens are those of the scalar clock; a row that ended is parked."""
+        self._refuse_clock("use_row_clock")
+        if self.io is None:
+            raise L.UmoeError("use_row_clock: start_decode first")
+        if len(set(self.prefill_steps)) != 1:
+            raise L.UmoeError("use_row_clock: rows with different prefill steps start at different local steps; admit them one by one")
+        clk = torch.zeros((self.batch, 2), dtype=torch.int32)
+        clk[:, 1] = self.T_prompt
+        self.row_clock = clk.to(self.dev)
+        self.io.row_clock = self.row_clock.data_ptr()
+        self.captured = False
+
+    def start_serving(self, max_prompt: int):
+        """An empty batch on per-row clocks: every row parked (countdown 0), the workspace reserved for prompts of up to `max_prompt`
+        tokens per row (it never moves afterwards, so the captured step survives admissions), a settings table with one record per
+        row.  admit() then puts requests into rows; step() decodes whatever rows are live."""
+        self._refuse_clock("start_serving")
+        B, Cc = self.batch, self.cfg.codec_channels
+        if B > 8:
+            raise L.UmoeError(f"start_serving: at most 8 rows (got {B})")
+        if max_prompt < 1 or max_prompt + 2 > self.Lmax:
+            raise L.UmoeError(f"start_serving: max_prompt {max_prompt} does not fit Lmax {self.Lmax}")
+        L.check(L.lib().umoe_engine_reserve(self.h, 2 * int(max_prompt)), "umoe_engine_reserve")
+        self.reserved_prompt = int(max_prompt)
+        self.tokens = torch.full((B, self.Tmax, Cc), -1, dtype=torch.int32, device=self.dev)
+        st = torch.zeros(4 * B + 8, dtype=torch.int32)       # eos_detected 0, countdown 0 = parked
+        st[2 * B:3 * B] = -1
+        st[3 * B:4 * B] = 1
+        st[4 * B + 1], st[4 * B + 2] = self.Tmax - 2, 1
+        self.state = st.to(self.dev)
+        self.row_clock = torch.zeros((B, 2), dtype=torch.int32, device=self.dev)
+        table = RP.pack_row_params(B, cfg_scale=[1.0] * B, temperature=1.0, top_p=1.0, top_k=None, eos_mul=1.0, do_sample=False, seed=0,
+                                   min_tokens=None, max_tokens=0)
+        self.row_params = ops.row_params_tensor(table, self.dev)
+        self.prefill_steps, self.max_tokens, self.T_prompt = [1] * B, self.Tmax - 2, int(max_prompt)
+        self.io = L.DecodeIO(tokens=self.tokens.data_ptr(), state=self.state.data_ptr(), cfg_scale=1.0, temperature=1.0, top_p=1.0, eos_mul=1.0,
+                             top_k=-1, do_sample=0, min_tokens=-1, seed=0, row_params=self.row_params.data_ptr(),
+                             row_clock=self.row_clock.data_ptr())
+        self.captured = False
+        self.steps_run = 0
+
+    def admit(self, b: int, x: Optional[torch.Tensor], attention_mask: torch.Tensor, prefill_tokens: torch.Tensor, prefill_step: int, *,
+              max_tokens: int, min_tokens, cfg_scale, temperature, top_p, top_k, eos_mul, do_sample, seed=0, position_ids=None,
+              external: bool = False):
+        """One request into row b of a batch that is decoding: x [2 * T, D] the CFG pair's prompt embeddings (negative, positive),
+        attention_mask [2, T] left padded, prefill_tokens [P, C] the row's token prefix as prepare_audio_prompt lays it out (P >=
+        prefill_step; -1 = to be generated), the request's own settings.
+        The pair is prefilled into cache rows 2b, 2b + 1 and the row is reset on the device at the step the stream has reached; no
+        other row changes, and a captured step stays valid.  external=True: the caller has written the pair's K / V slabs
+        (write_buffer); only the state is set.  Every refusal is raised before anything is enqueued."""
+        self._refuse_clock("admit")
+        if self.row_clock is None or not self.reserved_prompt:
+            raise L.UmoeError("admit: start_serving first")
+        if position_ids is not None:
+            raise L.UmoeError("admit: 3-D positions (vision prompts) are not admitted into a running batch; use generate()")
+        B, Cc, D = self.batch, self.cfg.codec_channels, self.cfg.hidden_size
+        if not 0 <= b < B:
+            raise L.UmoeError(f"admit: row {b} outside the batch of {B}")
+        if attention_mask.dim() != 2 or attention_mask.shape[0] != 2:
+            raise L.UmoeError("admit: attention_mask is [2, T], one CFG pair")
+        T = int(attention_mask.shape[1])
+        if T > self.reserved_prompt:
+            raise L.UmoeError(f"admit: a prompt of {T} tokens is larger than the reservation of start_serving ({self.reserved_prompt})")
+        prefill_step, max_tokens = int(prefill_step), int(max_tokens)
+        if prefill_step < 1 or prefill_tokens.dim() != 2 or prefill_tokens.shape[0] < prefill_step or prefill_tokens.shape[1] != Cc:
+            raise L.UmoeError("admit: prefill_tokens is [P, C] with P >= prefill_step >= 1")
+        if max_tokens + 2 > self.Tmax or prefill_tokens.shape[0] > self.Tmax or T + max_tokens + 1 > self.Lmax:
+            raise L.UmoeError("admit: engine buffers too small for max_tokens")
+        if not external and (x is None or tuple(x.shape) != (2 * T, D) or x.dtype != torch.bfloat16 or x.device != self.dev):
+            raise L.UmoeError(f"admit: x is the pair's [2 * T, {D}] bfloat16 prompt embeddings on the engine's device")
+        rec = RP.pack_row_params(1, cfg_scale=[cfg_scale], temperature=temperature, top_p=top_p, top_k=top_k, eos_mul=eos_mul, do_sample=do_sample,
+                                 seed=seed, min_tokens=min_tokens, max_tokens=max_tokens)
+        valid = attention_mask.to(torch.uint8).cpu().contiguous()
+        self.row_params[b].copy_(ops.row_params_tensor(rec, self.dev)[0])
+        P = int(prefill_tokens.shape[0])
+        self.tokens[b, :P] = prefill_tokens.to(self.dev, torch.int32)
+        if external:
+            L.check(L.lib().umoe_engine_admit_external(self.h, C.byref(self.io), b, valid.data_ptr(), T, prefill_step, P, self._stream()),
+                    "umoe_engine_admit_external")
+        else:
+            L.check(L.lib().umoe_engine_admit(self.h, C.byref(self.io), b, x.contiguous().data_ptr(), valid.data_ptr(), T, prefill_step, P,
+                                              self._stream()), "umoe_engine_admit")
+        self.prefill_steps[b] = prefill_step
+
+    def poll(self) -> torch.Tensor:
+        """The state words on the host (one synchronising read); raises when an in-launch hand-off timed out, as all_done() does."""
+        st = self.state.cpu()
+        code = self.handoff_error()
+        if code:
+            raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_RIDER_PUB=0 selects the launch-per-kernel path")
+        return st
+
+    def row_done(self, state_cpu: torch.Tensor, b: int) -> bool:
+        """row b has ended (or was never used): its countdown is 0, so it is parked"""
+        return int(state_cpu[self.batch + b]) == 0
+
+    def take(self, b: int):
+        """finish() for one row on its local clock: (codes [length + max_delay, C] int64, length) of the request that ended in row b"""
+        B, cfg = self.batch, self.cfg
+        md = max(cfg.codec_delay_pattern)
+        st = self.state.cpu()
+        fin, ps = int(st[2 * B + b]), self.prefill_steps[b]
+        if int(st[B + b]) != 0 or fin == -1:
+            raise L.UmoeError(f"take: row {b} has not ended")
+        length = max(fin - ps, 0)
+        seg = self.tokens[b, ps: ps + length + md].long()
+        out = torch.full((length + md, cfg.codec_channels), cfg.codec_pad_value, dtype=torch.long, device=self.dev)
+        out[: seg.shape[0]] = seg
+        return out, length
 
     def copy_buffer(self, name: str, dtype: torch.dtype, shape) -> torch.Tensor:
         """Copies an engine workspace buffer into a fresh device tensor (parity tests)."""

@@ -372,11 +372,15 @@ def codec_embed_sum_bwd(tok: torch.Tensor, d_out: torch.Tensor, V: int) -> torch
 
 def cfg_sample(logits: torch.Tensor, B: int, Cc: int, V: int, *, cfg_scale, temperature, top_p, top_k, eos, eos_mul,
                enable_eos=True, do_sample=True, seed=0, want_probs=False, step: Optional[torch.Tensor] = None,
-               min_tokens: Optional[int] = None, row_params: Optional[torch.Tensor] = None):
+               min_tokens: Optional[int] = None, row_params: Optional[torch.Tensor] = None, row_clock: Optional[torch.Tensor] = None):
     """step: a device int32 scalar, the decode engine's step counter. Given, it replaces 0 in the hash, and EOS is enabled iff
     min_tokens is None or *step >= min_tokens (enable_eos is then ignored), as in an engine step.
     row_params: a device table from row_params_tensor ([B] records of umoe_row_params): batch entry b then samples with ITS cfg_scale,
-    temperature, top_p, eos_mul, top_k, do_sample, min_tokens and seed, and the scalar arguments of those names are not read."""
+    temperature, top_p, eos_mul, top_k, do_sample, min_tokens and seed, and the scalar arguments of those names are not read.
+    row_clock: a device int32 [B, 2] table {step_off, t_prompt} (needs step): batch entry b samples at its local step *step - step_off[b]."""
+    if row_clock is not None:
+        assert step is not None and row_clock.dtype == torch.int32 and tuple(row_clock.shape) == (B, 2) and row_clock.is_contiguous() \
+            and row_clock.device == logits.device, "row_clock: a contiguous [B, 2] int32 device tensor, with step"
     if row_params is not None:
         assert row_params.dtype == torch.uint8 and tuple(row_params.shape) == (B, C.sizeof(L.RowParams)) and row_params.is_contiguous() \
             and row_params.device == logits.device, "row_params: the [B, 40] uint8 device tensor of row_params_tensor"
@@ -388,14 +392,21 @@ def cfg_sample(logits: torch.Tensor, B: int, Cc: int, V: int, *, cfg_scale, temp
                      eos_mul=eos_mul, top_k=-1 if top_k is None else top_k, eos=eos, enable_eos=int(enable_eos),
                      min_tokens=-1 if min_tokens is None else int(min_tokens), step=None if step is None else _p(step),
                      do_sample=int(do_sample), seed=seed, pred=_p(pred), probs_out=_p(probs),
-                     row_params=None if row_params is None else _p(row_params))
+                     row_params=None if row_params is None else _p(row_params), row_clock=None if row_clock is None else _p(row_clock))
     L.check(L.lib().umoe_codec_head_cfg_sample(C.byref(a), _stream()), "umoe_codec_head_cfg_sample")
     return (pred, probs) if want_probs else pred
 
 
-def delay_step(pred, tokens, state, delay, eos, pad, row_params: Optional[torch.Tensor] = None):
-    """row_params (row_params_tensor): row b is forced to end by ITS max_tokens; state[4B + 1] stays the loop bound (the largest)"""
+def delay_step(pred, tokens, state, delay, eos, pad, row_params: Optional[torch.Tensor] = None, row_clock: Optional[torch.Tensor] = None):
+    """row_params (row_params_tensor): row b is forced to end by ITS max_tokens; state[4B + 1] stays the loop bound (the largest).
+    row_clock (int32 [B, 2] {step_off, t_prompt}): umoe_delay_step_clock, every row on its local clock step - step_off[b]."""
     B, Tmax, Cc = tokens.shape
+    if row_clock is not None:
+        assert row_clock.dtype == torch.int32 and tuple(row_clock.shape) == (B, 2) and row_clock.is_contiguous() and row_clock.device == tokens.device
+        assert row_params is None or (row_params.dtype == torch.uint8 and tuple(row_params.shape) == (B, C.sizeof(L.RowParams)) and row_params.is_contiguous())
+        L.check(L.lib().umoe_delay_step_clock(_p(pred), _p(tokens), _p(state), _p(delay), B, Cc, Tmax, eos, pad, int(delay.max().item()),
+                                              None if row_params is None else _p(row_params), _p(row_clock), _stream()), "umoe_delay_step_clock")
+        return
     if row_params is None:
         L.check(L.lib().umoe_delay_step(_p(pred), _p(tokens), _p(state), _p(delay), B, Cc, Tmax, eos, pad,
                                         int(delay.max().item()), _stream()), "umoe_delay_step")

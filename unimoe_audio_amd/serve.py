@@ -1,0 +1,100 @@
+"""Continuous batching policy of a decode engine on per-row clocks: plain host code, no device, no library.
+
+A queue of requests is served by a fixed number of rows.  Requests are admitted first in, first out, one per free row, at every
+poll; between two polls the engine takes `poll_every` decode steps (as DecodeEngine.run() does between two reads of its flag); a row
+whose request ended is retired at the poll that sees it, its result handed out, and the row is free for the next request.
+
+The engine is anything with
+
+    admit(row, request)       put `request` into the free row `row`
+    steps(n)                  take n decode steps
+    poll() -> state           one read of the engine's state
+    row_done(state, row)      whether the request in `row` has ended
+    take(row) -> result       the ended request's result; the row is free afterwards
+
+DecodeEngine (through the adapter of UniMoEAudio.serve) is one; tests/test_serve_cpu.py drives a fake whose request lengths are known.
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import Any, Deque, Dict, Iterable, Iterator, List, Tuple
+
+MAX_SLOTS = 8
+
+
+class Scheduler:
+    def __init__(self, engine, slots: int, poll_every: int = 16):
+        if not 1 <= slots <= MAX_SLOTS:
+            raise ValueError(f"slots must be 1..{MAX_SLOTS} (got {slots})")
+        if poll_every < 1:
+            raise ValueError("poll_every must be >= 1")
+        self.engine, self.slots, self.poll_every = engine, int(slots), int(poll_every)
+        self.queue: Deque[Tuple[int, Any]] = deque()
+        self.free: List[int] = list(range(self.slots))     # ascending: the lowest free row takes the next request
+        self.live: Dict[int, int] = {}                      # row -> index of the request it holds
+        self.steps_run = 0
+        self.admitted: List[Tuple[int, int, int]] = []      # (request index, row, step count at admission), in admission order
+
+    def _admit_free_rows(self, source: Iterator[Tuple[int, Any]]):
+        while self.free:
+            if not self.queue:
+                nxt = next(source, None)
+                if nxt is None:
+                    return
+                self.queue.append(nxt)
+            index, request = self.queue.popleft()
+            row = self.free.pop(0)
+            self.engine.admit(row, request)
+            self.live[row] = index
+            self.admitted.append((index, row, self.steps_run))
+
+    def run(self, requests: Iterable[Any]) -> Iterator[Tuple[int, Any]]:
+        """Serves every request of `requests` (any iterable, read lazily: one request ahead of the free rows) and yields
+        (index, result) as each ends, index = the request's position in `requests`."""
+        source = iter(enumerate(requests))
+        while True:
+            self._admit_free_rows(source)
+            if not self.live:
+                return
+            self.engine.steps(self.poll_every)
+            self.steps_run += self.poll_every
+            state = self.engine.poll()
+            for row in sorted(self.live):
+                if self.engine.row_done(state, row):
+                    index = self.live.pop(row)
+                    result = self.engine.take(row)
+                    self.free.append(row)
+                    self.free.sort()
+                    yield index, result
+
+
+def makespan_steps(lengths: Iterable[int], slots: int, poll_every: int) -> int:
+    """Decode steps Scheduler.run takes for requests that need `lengths` steps each, in queue order: a request admitted at step a
+    is seen ended at the first poll at or after a + length."""
+    sched = Scheduler(_Lengths(), slots, poll_every)
+    for _ in sched.run(list(lengths)):
+        pass
+    return sched.steps_run
+
+
+class _Lengths:
+    """the engine of makespan_steps: a request IS its length in steps"""
+
+    def __init__(self):
+        self.left: Dict[int, int] = {}
+
+    def admit(self, row, request):
+        self.left[row] = int(request)
+
+    def steps(self, n):
+        for r in self.left:
+            self.left[r] -= n
+
+    def poll(self):
+        return self.left
+
+    def row_done(self, state, row):
+        return state[row] <= 0
+
+    def take(self, row):
+        return self.left.pop(row)
