@@ -200,9 +200,8 @@ typedef struct {
     const umoe_router_args* fused_router; /* optional HOST pointer (SwiGLU, nt = 14, <= 16 rows, n_dyn 9 / n_fix 2, D 2048 / 4096, S <= 16):
                                * the router of these tokens runs INSIDE this launch as S extra workgroups (its outputs are complete when
                                * the launch is); the GEMM itself must not depend on them (dense-expert decode: h_out NULL, see norm_only) */
-    const void* rider_pub;    /* decode engine only (NULL otherwise), with fused_router: HOST pointer to the hand-off descriptor -- the riders
-                               * also produce the normalised rows `a` (fused_router->h_out == a) and HAND them to the GEMM workgroups of
-                               * this same launch, which stream their first weight chunk while they wait: no RMSNorm launch in front */
+    const void* rider_pub;    /* decode engine only, with fused_router: HOST pointer to the hand-off descriptor (epoch and error words) of
+                               * the flat expert launch, which takes these arguments; umoe_grouped_gemm refuses anything but NULL */
 } umoe_gemm_args;
 #define UMOE_GROUPS_INLINE 12
 
@@ -736,8 +735,8 @@ void umoe_engine_destroy(umoe_engine* e);
 int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer_weights* w);
 /* fp8 expert weights of one layer (after umoe_engine_set_layer): host arrays [n_real + n_fix] (routed experts, then shared) of device
  * pointers to WP8 gate/up pairs, their exponents, WP8 down blocks and theirs.  An engine with fp8 weights runs every dense decode layer's
- * experts through the fp8 flat launch and nothing else: a decode step it cannot run that way (UMOE_FLAT_MOE=0, UMOE_RIDER_PUB=0, too few
- * compute units for a schedule) is refused before anything is enqueued; expert parallel engines (ep_size > 1) are refused here.
+ * experts through the fp8 flat launch and nothing else: a decode step it cannot run that way (the launch-per-kernel form UMOE_FLAT_MOE=0
+ * UMOE_FUSE_CQ=0, UMOE_FUSE_ROUTER=0, too few compute units for a schedule) is refused before anything is enqueued; expert parallel engines (ep_size > 1) are refused here.
  * umoe_engine_info(e, "expert_fp8") = 1 when the last dense decode layer ran the fp8 launch.  Prefill keeps the bf16 weights. */
 int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* gu8, const int8_t* const* gu_e, const uint8_t* const* dn8,
                               const int8_t* const* dn_e);
@@ -824,9 +823,8 @@ int umoe_engine_ep_error(umoe_engine* e, umoe_stream_t stream, int* code_out);
  * is replaced); every other launch is the decode step's own. */
 int umoe_engine_set_probe(umoe_engine* e, const uint16_t* teach_x, uint16_t* dump_x1, uint16_t* dump_x, uint16_t* dump_logits);
 /* host-side facts about the engine: "expert_launch" = what the last dense decode layer enqueued for its experts (0 gate/up and down as
- * two launches, 1 the box-grid fused launch moe_fused_kernel, 2 the flat launch moe_flat_kernel, 3 the one-launch expert-parallel MoE half
- * moe_ep_kernel), "n_cu" = compute units the
- * co-residency guards assume; -1 for an unknown key */
+ * two launches, 2 the flat launch moe_flat_kernel, 3 the one-launch expert-parallel MoE half moe_ep_kernel; 1 was the box-grid fused
+ * launch, which no longer exists, and is never returned), "n_cu" = compute units the co-residency guards assume; -1 for an unknown key */
 int umoe_engine_info(umoe_engine* e, const char* key);
 /* introspection for parity tests: device pointers into the workspace */
 const void* umoe_engine_buffer(umoe_engine* e, const char* name, size_t* bytes);

@@ -440,9 +440,9 @@ def test_checkpoint_round_trip_generates_identical_codes(dev, tmp_path):
 
 @pytest.mark.parametrize("B", [1, 3, 5])
 def test_fused_launches_with_fewer_than_16_rows_are_bit_identical(dev, monkeypatch, B):
-    """2, 6 and 10 decode rows (batch 1, 3, 5): the dense layout with the fused expert launch, the riders' hand-off and the combine riding
-    in the QKV launch against the launch-per-kernel form (UMOE_RIDER_PUB=0 switches all three off) and against the ragged dispatch path
-    where it still exists (UMOE_DENSE_MIN_ROWS=17): identical codes -- the partial-tile guards of every hand-off."""
+    """2, 6 and 10 decode rows (batch 1, 3, 5): the dense layout with the flat expert launch and the combine riding in the QKV launch
+    against the launch-per-kernel form (UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0) and against the ragged dispatch path where it still exists
+    (UMOE_DENSE_MIN_ROWS=17): identical codes -- the partial-tile guards of every hand-off."""
     from unimoe_audio_amd.codec_utils import DecoderOutput, prepare_audio_prompt
     cfg = small_cfg(hidden_size=2048, num_attention_heads=16, num_key_value_heads=2, num_hidden_layers=2,
                     dynamic_intermediate_size=2752, shared_intermediate_size=1376)
@@ -450,8 +450,9 @@ def test_fused_launches_with_fewer_than_16_rows_are_bit_identical(dev, monkeypat
     ids, am, codec = prompt(cfg, B, T, 4, [1] + [0] * (2 * B - 1))
     pre, psteps = prepare_audio_prompt(cfg, [None] * B)
     outs = []
-    for pub, dense_min in (("1", "2"), ("0", "2"), ("1", "17")):
-        monkeypatch.setenv("UMOE_RIDER_PUB", pub)
+    for fused, dense_min in (("1", "2"), ("0", "2"), ("1", "17")):
+        monkeypatch.setenv("UMOE_FLAT_MOE", fused)
+        monkeypatch.setenv("UMOE_FUSE_CQ", fused)
         monkeypatch.setenv("UMOE_DENSE_MIN_ROWS", dense_min)
         m, _ = build(cfg, 31, 0.03)
         m = m.to(dev)
@@ -467,9 +468,10 @@ def test_fused_launches_with_fewer_than_16_rows_are_bit_identical(dev, monkeypat
 
 
 def test_router_riding_in_the_gate_up_launch_is_bit_identical(dev, monkeypatch):
-    """Dense decode runs the Top-P router as rider workgroups inside the gate/up launch (umoe_gemm_args.fused_router) behind an
-    RMSNorm-only launch (umoe_router_args.norm_only).  Same arithmetic, same order: the generated codes and the per-layer router
-    integers equal those of the separate router launch (UMOE_FUSE_ROUTER=0) bit for bit, in both rider placements."""
+    """Dense decode runs the Top-P router as rider workgroups: inside the flat expert launch (the default), or, launch per kernel
+    (UMOE_FLAT_MOE=0), inside the gate/up launch (umoe_gemm_args.fused_router) behind an RMSNorm-only launch
+    (umoe_router_args.norm_only).  Same arithmetic, same order: the generated codes and the per-layer router integers equal those of
+    the separate router launch (UMOE_FUSE_ROUTER=0) bit for bit, in both rider placements, with and without the combine rider."""
     from unimoe_audio_amd.codec_utils import DecoderOutput, prepare_audio_prompt
     cfg = small_cfg(hidden_size=2048, num_attention_heads=16, num_key_value_heads=2, num_hidden_layers=2,
                     dynamic_intermediate_size=2752, shared_intermediate_size=1376)      # the fused path needs the real D / expert sizes
@@ -477,17 +479,14 @@ def test_router_riding_in_the_gate_up_launch_is_bit_identical(dev, monkeypatch):
     ids, am, codec = prompt(cfg, B, T, 4, [1] + [0] * (2 * B - 1))
     pre, psteps = prepare_audio_prompt(cfg, [None] * B)
     outs = []
-    # fourth: the hand-off off (RMSNorm launch in front, gate/up and down as plain launches); fifth: gate/up and down as two launches
-    # instead of one expert launch; sixth: the combine as a launch of its own instead of riding in the next layer's QKV launch;
-    # seventh: the box-grid fused expert launch instead of the flat one (the default is the third)
-    for fuse, mode, pub, fm, cq, flat in (("0", "0", "1", "1", "1", "1"), ("1", "1", "1", "1", "1", "1"), ("1", "0", "1", "1", "1", "1"),
-                                          ("1", "0", "0", "1", "1", "1"), ("1", "0", "1", "0", "1", "1"), ("1", "0", "1", "1", "0", "1"),
-                                          ("1", "0", "1", "1", "1", "0")):
+    # first: the router launch (the reference); second: the default; third and fourth: launch per kernel with the riders in the gate/up
+    # launch, in its dead workgroups and in a z-slice of their own, the combine still riding in the QKV launch; fifth: the flat launch with
+    # the combine as a launch of its own; sixth: launch per kernel throughout
+    for fuse, mode, cq, flat in (("0", "0", "1", "1"), ("1", "0", "1", "1"), ("1", "0", "1", "0"), ("1", "1", "1", "0"), ("1", "0", "0", "1"),
+                                 ("1", "0", "0", "0")):
         monkeypatch.setenv("UMOE_FUSE_CQ", cq)
-        monkeypatch.setenv("UMOE_FUSE_MOE", fm)
         monkeypatch.setenv("UMOE_FUSE_ROUTER", fuse)
         monkeypatch.setenv("UMOE_RIDER_MODE", mode)
-        monkeypatch.setenv("UMOE_RIDER_PUB", pub)
         monkeypatch.setenv("UMOE_FLAT_MOE", flat)
         m, _ = build(cfg, 31, 0.03)
         m = m.to(dev)
@@ -508,9 +507,9 @@ def test_router_riding_in_the_gate_up_launch_is_bit_identical(dev, monkeypatch):
 
 def test_flat_expert_launch_is_bit_identical_and_respects_the_cu_count(dev, monkeypatch):
     """The byte-balanced flat expert launch (umoe_moe_flat.hip: one workgroup per CU, static schedule, riders inside, two down slices)
-    against the box-grid launch of round 2 (UMOE_FLAT_MOE=0), on a device that claims 240 CUs (another schedule, 240 workgroups) and
-    on one that claims 200 (no schedule, and the 250-workgroup box would not be resident either: the engine must take the
-    launch-per-kernel path by itself instead of timing out in a hand-off): identical codes and router integers everywhere."""
+    against the launch-per-kernel form (UMOE_FLAT_MOE=0), on a device that claims 240 CUs (another schedule, 240 workgroups) and on
+    ones that claim 200 and 100 (no schedule: the engine must take the launch-per-kernel form by itself instead of timing out in a
+    hand-off): identical codes and router integers everywhere, and the engine reports the form it chose."""
     from unimoe_audio_amd.codec_utils import DecoderOutput, prepare_audio_prompt
     cfg = small_cfg(hidden_size=2048, num_attention_heads=16, num_key_value_heads=2, num_hidden_layers=2,
                     dynamic_intermediate_size=2752, shared_intermediate_size=1376)
@@ -518,7 +517,7 @@ def test_flat_expert_launch_is_bit_identical_and_respects_the_cu_count(dev, monk
     ids, am, codec = prompt(cfg, B, T, 4, [1] + [0] * (2 * B - 1))
     pre, psteps = prepare_audio_prompt(cfg, [None] * B)
     outs = []
-    for flat, cus in (("1", None), ("0", None), ("1", "240"), ("1", "200"), ("1", "100")):
+    for flat, cus, launch in (("1", None, 2), ("0", None, 0), ("1", "240", 2), ("1", "200", 0), ("1", "100", 0)):
         monkeypatch.setenv("UMOE_FLAT_MOE", flat)
         if cus is None:
             monkeypatch.delenv("UMOE_FAKE_CUS", raising=False)
@@ -531,6 +530,7 @@ def test_flat_expert_launch_is_bit_identical_and_respects_the_cu_count(dev, monk
                                     top_p=0.9, eos_prob_mul_factor=0.8, seed=3)
         eng = m._engine
         assert eng.handoff_error() == 0
+        assert eng.info("expert_launch") == launch, (flat, cus)
         stats = eng.router_stats() if hasattr(eng, "router_stats") else None
         outs.append((codes.cpu(), lengths.cpu(), stats))
         del m

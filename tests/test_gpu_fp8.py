@@ -142,7 +142,8 @@ def test_quantized_parameters_are_exact_and_the_engine_needs_them_fresh(dev):
 @pytest.mark.parametrize("B", [1, 3, 8])
 def test_fp8_engine_is_bit_identical_to_bf16_on_the_dequantized_weights(dev, monkeypatch, B):
     """2 layers at the reference width: the fp8 flat launch against the bf16 engine on the same quantized model -- eager and graph
-    replay, on the device's own schedule and on a 240-CU one: identical codes, router integers, router logits and final logits."""
+    replay, on the device's own schedule and on a 240-CU one: identical codes, router integers, router logits and final logits.  The fp8
+    engine with the combine as a launch of its own (UMOE_FUSE_CQ=0) decodes too, bit-identical to the fp8 engine with the combine rider."""
     cfg = ref_cfg()
     m = build(cfg, 31).to(dev)
     m.quantize_experts_("fp8")
@@ -156,6 +157,12 @@ def test_fp8_engine_is_bit_identical_to_bf16_on_the_dequantized_weights(dev, mon
         assert a["handoff"] == 0 and b["handoff"] == 0
         assert a["expert_fp8"] == 0 and b["expert_fp8"] == 1 and b["expert_launch"] == 2
         assert_same(a, b)
+        if use_graph and cus is None:
+            monkeypatch.setenv("UMOE_FUSE_CQ", "0")
+            c = run_engine(m, cfg, B, "fp8", 6, use_graph, dev)
+            monkeypatch.delenv("UMOE_FUSE_CQ")
+            assert c["handoff"] == 0 and c["expert_fp8"] == 1 and c["expert_launch"] == 2
+            assert_same(b, c)
 
 
 def test_fp8_engine_full_depth_is_bit_identical(dev):
@@ -170,7 +177,7 @@ def test_fp8_engine_full_depth_is_bit_identical(dev):
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("env", [{"UMOE_FLAT_MOE": "0"}, {"UMOE_RIDER_PUB": "0"}, {"UMOE_FAKE_CUS": "100"}])
+@pytest.mark.parametrize("env", [{"UMOE_FLAT_MOE": "0"}, {"UMOE_FUSE_ROUTER": "0"}, {"UMOE_FAKE_CUS": "100"}])
 def test_fp8_engine_refuses_every_path_but_the_flat_launch(dev, monkeypatch, env):
     """No silent fall-back to a bf16 expert path: the step is refused on the host, before anything is enqueued."""
     from unimoe_audio_amd import _lib as L

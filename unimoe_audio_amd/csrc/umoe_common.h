@@ -223,7 +223,8 @@ int umoe_ep_pull_pack(const umoe_ep_xfer& x, const uint16_t* own_rows, hipStream
 int umoe_router_norm_push(const umoe_router_args* a, const umoe_ep_xfer& x, hipStream_t s);
 int umoe_ep_rccl_allgather(void* comm, const void* send, void* recv, size_t bytes, hipStream_t s);
 
-// ---- riders publish the normalised rows inside the gate/up launch (umoe_gemm_args.rider_pub -> this, host side) ------------
+// ---- hand-offs inside one launch: epoch, error word and row flags (umoe_gemm_args.rider_pub -> this, host side) ------------
+// Row riders (umoe_riders_dev.h) publish the rows a GEMM of the same launch stages; the flat expert launches read step / layer / err.
 // The row flags are REPLICATED: UMOE_FLAG_REPL copies of the 16-word line, 64 bytes apart; a rider stores its epoch into every copy,
 // a polling workgroup reads copy (its id % UMOE_FLAG_REPL) -- 226 workgroups polling ONE line serialised at that line's home
 // (scripts/timeline_wgs.py: 3 us from flag store to detection).
@@ -233,17 +234,13 @@ struct umoe_rider_pub {
     const uint32_t* step;      // device word: decode steps taken so far
     int layer, layers;         // epoch = *step * layers + layer + 1
     uint32_t* err;             // device word, sticky: 2 = a workgroup gave up waiting for the riders
-    unsigned long long* rs;    // second hand-off form (fused expert launch with the RMSNorm prologue): device [16] granules {rs, epoch}
 };
 
-// The two expert GEMMs of a dense decode layer (gate/up SwiGLU with riders + rider_pub, then the down projections) in ONE launch
-// (umoe_gemm.hip moe_fused_kernel; decode engine only).  `gu` as for umoe_grouped_gemm with nt 14, fused_router and rider_pub; `dn`
-// with nt 6, dn->a == gu->out; `flags`: device words, one per gate/up workgroup of the launch box (>= num_groups * ceil(max pairs / 7)).
-// Returns 1 (nothing launched) when the shapes do not allow the fusion: the caller then issues the two launches.
-int umoe_moe_fused(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, hipStream_t s);
-// The same two GEMMs as ONE workgroup per CU with a static, byte-balanced schedule (umoe_moe_flat.hip): `n_wg` workgroups (<= the
-// device's CU count: every workgroup must be resident), the riders are the first S of them.  `gu` / `dn` as for umoe_moe_fused (any
-// nt); `flags`: >= n_wg device words.  Returns 1 (nothing launched) when the shapes or n_wg do not allow a schedule.
+// The two expert GEMMs of a dense decode layer (gate/up SwiGLU, then the down projections) in ONE launch, ONE workgroup per CU with a
+// static, byte-balanced schedule (umoe_moe_flat.hip; decode engine only): `n_wg` workgroups (<= the device's CU count: every workgroup
+// must be resident), the router riders are the first S of them.  `gu` as for umoe_grouped_gemm with fused_router and rider_pub (any nt);
+// `dn` with dn->a == gu->out; `flags`: >= n_wg device words.  Returns 1 (nothing launched) when the shapes or n_wg do not allow a
+// schedule: umoe_moe_flat_feasible answers that beforehand.
 int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s);
 bool umoe_moe_flat_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
 // The same launch on WP8 (fp8 e4m3) expert weights: the groups' `w` are WP8 blocks (include/umoe.h), e_gu / e_dn [num_groups] their

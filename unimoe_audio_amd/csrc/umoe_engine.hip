@@ -57,8 +57,7 @@ struct umoe_engine {
     int32_t* d_delay = nullptr;
     umoe_group_t* d_groups = nullptr;  // per layer: [qkv 1][o 1][gateup G][down G]; then [head 1]
     std::vector<umoe_group_t> h_groups;  // host copy: descriptors travel by value in the GEMM kernel arguments
-    std::vector<umoe_group_t> h_gu_pub;  // per layer: the gate/up groups with the SHARED experts first -- their tile-less workgroups
-                                         // (the riders) then come early in dispatch order, in front of almost every workgroup that waits for them
+    std::vector<umoe_group_t> h_gu_pub;  // per layer: the gate/up groups in the order of the flat expert launch, the SHARED experts first
     int groups_for_tok = -1;
     // carved buffers
     uint16_t *x = nullptr, *hin = nullptr, *x1 = nullptr, *h2 = nullptr, *qkv = nullptr, *q_r = nullptr, *attn_out = nullptr,
@@ -85,28 +84,22 @@ struct umoe_engine {
     bool probe_on() const { return probe_teach || probe_x1 || probe_x || probe_logits; }
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    // decode with >= 6 rows: every routed expert is hit with probability ~1, so each expert computes ALL rows (no gather
-    // lists, no dispatch kernel, no device-produced row counts in the GEMM prologues) and the combine selects by mask
-    bool dense_experts = true;
     bool fuse_router = true;     // UMOE_FUSE_ROUTER: dense decode runs the router inside the gate/up launch (see run_layer)
     bool fuse_cq = true;         // UMOE_FUSE_CQ: the MoE combine of layer l rides in the QKV launch of layer l + 1 (umoe_gemm_riders kind 2)
     int cb_ep_layer = -1;        // expert parallel: the layer whose return slab the stashed combine reads (>= 0 selects rider kind 4)
     bool cb_pending = false;     // a combine stashed at the end of a layer, issued with the next layer's QKV launch
     umoe_combine_args cb_stash{};
+    // dense-expert layout of a decode step: each expert computes ALL rows (no gather lists, no dispatch kernel, no device-produced row
+    // counts in the GEMM prologues) and the combine selects by mask -- with >= 6 rows every routed expert is hit with probability ~1
     int dense_min_rows = 2;      // UMOE_DENSE_MIN_ROWS: fewest decode rows that take the dense-expert layout (below: ragged dispatch).  Batch 1
                                  // (2 CFG rows, BASELINE configs[0]) hits 5-6 of the 8 experts: streaming all 8 in the fused launches costs
                                  // fewer microseconds than the ragged path's four extra launches -- 2.91 vs 3.33 ms/step
-    int expert_launch = 0;       // what the last dense decode layer enqueued for its experts: 0 launch per GEMM, 1 box-grid fused, 2 flat, 3 the
-                                 // one-launch expert-parallel MoE half (umoe_engine_info)
+    int expert_launch = 0;       // what the last dense decode layer enqueued for its experts: 0 launch per GEMM, 2 flat, 3 the one-launch
+                                 // expert-parallel MoE half (umoe_engine_info; 1 was the removed box-grid launch)
     bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
     int expert_fp8 = 0;          // the last dense decode layer ran the fp8 flat launch (umoe_engine_info "expert_fp8")
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
-    bool flat_moe = true;        // UMOE_FLAT_MOE: both expert GEMMs as ONE workgroup per CU with a byte-balanced static schedule
-                                 // (umoe_moe_flat.hip); 0 / shapes that do not fit: the box-grid launch below
-    bool fuse_moe = true;        // UMOE_FUSE_MOE: gate/up and down projections of a dense decode layer in ONE launch (umoe_moe_fused)
-    bool rider_pub = true;       // UMOE_RIDER_PUB: the riders also produce the normalised rows and hand them to the GEMM workgroups of the
-                                 // same launch (umoe_gemm_args.rider_pub): no RMSNorm launch in front of gate/up
     bool tiled_prefill = true;   // UMOE_TILED_PREFILL=0: weight-streaming kernels for every row count (A/B, tests)
     // optional per-kernel-class timing of one eager step (hipEvents on the launch stream)
     bool prof = false;
@@ -204,7 +197,7 @@ static int ensure_workspace(umoe_engine* e, int n_tok) {
 static bool dense_mode(const umoe_engine* e, int n_tok) {
     if (e->ep_decode(n_tok)) return true;   // expert parallel decode IS the dense layout: every rank's rows visit every expert
     if (e->adm_row0 >= 0) return false;     // an admission prefill of rows tokens is a prefill: ragged dispatch, never the decode launches
-    return e->dense_experts && n_tok == e->c.rows && n_tok <= 16 && n_tok >= e->dense_min_rows;
+    return n_tok == e->c.rows && n_tok <= 16 && n_tok >= e->dense_min_rows;
 }
 
 static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
@@ -322,8 +315,9 @@ extern "C" int umoe_engine_create(const umoe_engine_cfg* cfg, umoe_engine** out)
         umoe_engine_destroy(e);
         return -2;
     }
-    // [0] decode steps taken, [1] sticky hand-off error, [2] expert-parallel round, [64, 512) flags of the fused / flat expert launch,
-    // [1024, 1280) row flags of the rider hand-offs (umoe_gemm_args.rider_pub), [2048, 2688) flags of the expert-parallel flat launch;
+    // [0] decode steps taken, [1] sticky hand-off error, [2] expert-parallel round, [64, 512) flags of the flat expert launch,
+    // [1024, 1280) row flags of the rider hand-offs (umoe_rider_pub.flags; polled only from 1152 up, by the QKV launch with the combine
+    // riders, umoe_gemm_riders), [2048, 2688) flags of the expert-parallel flat launch;
     // words from 2688 up are unused
     if (hipMalloc(&e->ep_words, 32768) != hipSuccess || hipMemset(e->ep_words, 0, 32768) != hipSuccess) {
         umoe_set_error("umoe_engine_create: hipMalloc failed (state words)");
@@ -351,13 +345,9 @@ extern "C" int umoe_engine_create(const umoe_engine_cfg* cfg, umoe_engine** out)
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) e->n_cu = cus;
         if (const char* v = getenv("UMOE_FAKE_CUS")) e->n_cu = atoi(v);
     }
-    if (const char* v = getenv("UMOE_FLAT_MOE")) e->flat_moe = atoi(v) != 0;
     if (const char* v = getenv("UMOE_EP_FLAT")) e->ep_flat = atoi(v) != 0;
-    if (const char* v = getenv("UMOE_DENSE_EXPERTS")) e->dense_experts = atoi(v) != 0;
     if (const char* v = getenv("UMOE_TILED_PREFILL")) e->tiled_prefill = atoi(v) != 0;
     if (const char* v = getenv("UMOE_FUSE_ROUTER")) e->fuse_router = atoi(v) != 0;
-    if (const char* v = getenv("UMOE_RIDER_PUB")) e->rider_pub = atoi(v) != 0;
-    if (const char* v = getenv("UMOE_FUSE_MOE")) e->fuse_moe = atoi(v) != 0;
     if (const char* v = getenv("UMOE_DENSE_MIN_ROWS")) e->dense_min_rows = atoi(v);
     if (const char* v = getenv("UMOE_FUSE_CQ")) e->fuse_cq = atoi(v) != 0;
     *out = e;
@@ -476,7 +466,7 @@ extern "C" int umoe_engine_ep_connect(umoe_engine* e, void* const* peers, void* 
     // assume (UMOE_FAKE_CUS: several ranks sharing one card take a share each).
     e->epf_ready = false;
     const umoe_engine_cfg& c = e->c;
-    if (mode != UMOE_EP_RCCL && e->ep_flat && e->rider_pub && e->fuse_router && e->n_cu > 0 && c.hidden == 2048 && c.n_dyn == 9 && c.n_fix == 2 && c.rows <= 16 &&
+    if (mode != UMOE_EP_RCCL && e->ep_flat && e->fuse_router && e->n_cu > 0 && c.hidden == 2048 && c.n_dyn == 9 && c.n_fix == 2 && c.rows <= 16 &&
         e->E_loc >= 1 && e->E_loc <= UMOE_MT_MAXG) {
         umoe_epf_desc& d = e->epf;
         memset(&d, 0, sizeof(d));
@@ -786,6 +776,85 @@ static int run_moe_ep(umoe_engine* e, int l, int n_tok, hipStream_t s) {
     return rc;
 }
 
+// ------------------------------------------------------------------------------------ the MoE half of one layer (ep_size 1)
+// What a layer's router and experts are enqueued as: decided ONCE per layer on the host, from the shape and the switches, and each
+// form is one block of run_layer with no fall-through into another.
+enum MoeForm {
+    MOE_TILED,     // >= 64 rows (prefill): router + dispatch tables, tiled MFMA GEMMs on the row-major weights
+    MOE_RAGGED,    // router + dispatch tables, weight-streaming GEMMs over the experts' ragged row lists
+    MOE_FLAT,      // dense decode, ONE launch: router riders, RMSNorm, gate/up and down, one workgroup per CU (umoe_moe_flat.hip)
+    MOE_RIDERS,    // dense decode, launch per kernel: RMSNorm | gate/up with the router riding in it | down
+    MOE_ROUTER,    // dense decode, launch per kernel: router | gate/up | down
+};
+
+// UMOE_FLAT_MOE=0: never the flat expert launch.  Read per enqueue: the step graph captures the choice, A/B scripts toggle it on a live engine.
+static bool flat_moe_on() {
+    const char* v = getenv("UMOE_FLAT_MOE");
+    return !v || atoi(v) != 0;
+}
+// workgroups of the flat expert launch: one per CU.  Its in-launch hand-offs need every workgroup RESIDENT at once (a waiting workgroup
+// never yields its CU), so a device that exposes fewer CUs than a schedule needs (partition, CU mask, UMOE_FAKE_CUS) takes the
+// launch-per-kernel form instead of discovering it by a timeout.
+static int flat_wgs(const umoe_engine* e) { return e->n_cu < 256 ? e->n_cu : 256; }
+
+static MoeForm moe_form(const umoe_engine* e, const LayerDev& L, int n_tok) {
+    const umoe_engine_cfg& c = e->c;
+    if (!dense_mode(e, n_tok)) return (L.has_rm && n_tok >= 64 && e->tiled_prefill && c.n_real + c.n_fix <= 12) ? MOE_TILED : MOE_RAGGED;
+    // the shapes the router riders are written for (router4_body<9, 2>; dense_mode: <= 16 rows)
+    if (!(e->fuse_router && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096))) return MOE_ROUTER;
+    const int n_wg = flat_wgs(e);
+    if (flat_moe_on() && n_wg > 0 && umoe_moe_flat_feasible(n_wg, n_tok, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix)) return MOE_FLAT;
+    return MOE_RIDERS;
+}
+
+// gate/up SwiGLU, then the down projections: one weight-streaming launch each
+static int experts_two_launches(umoe_engine* e, const umoe_gemm_args* gu, const umoe_gemm_args* dn, hipStream_t s) {
+    int rc;
+    if ((rc = umoe_grouped_gemm(gu, s))) return rc;
+    PROF(K_GATEUP);
+    if ((rc = umoe_grouped_gemm(dn, s))) return rc;
+    PROF(K_DOWN);
+    return 0;
+}
+
+// the same two GEMMs on the tiled MFMA kernel; gu_groups: the layer's gate/up groups, the down groups behind them (same row tables)
+static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* gu_groups, int n_tok, hipStream_t s) {
+    const umoe_engine_cfg& c = e->c;
+    const int D = c.hidden, G = c.n_real + c.n_fix, Imax = c.inter_dyn > c.inter_shared ? c.inter_dyn : c.inter_shared;
+    int rc;
+    umoe_tgroup_t tg[12];
+    memset(tg, 0, sizeof(tg));
+    for (int x = 0; x < G; ++x) {
+        const umoe_group_t& src = gu_groups[x];
+        const bool sh = x >= c.n_real;
+        tg[x].w = sh ? L.rm_sg[x - c.n_real] : L.rm_eg[x];
+        tg[x].w2 = sh ? L.rm_su[x - c.n_real] : L.rm_eu[x];
+        tg[x].rows = src.rows; tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
+        tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
+        tg[x].n = sh ? c.inter_shared : c.inter_dyn; tg[x].k = D; tg[x].ldw = D;
+    }
+    umoe_tgemm_args ta{};
+    ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok; ta.a = e->h2; ta.lda = D; ta.out = e->hbuf; ta.ldo = Imax;
+    ta.epilogue = UMOE_EPI_SWIGLU;
+    if ((rc = umoe_tiled_gemm(&ta, s))) return rc;
+    PROF(K_GATEUP);
+    memset(tg, 0, sizeof(tg));
+    for (int x = 0; x < G; ++x) {
+        const umoe_group_t& src = gu_groups[G + x];
+        const bool sh = x >= c.n_real;
+        tg[x].w = sh ? L.rm_sd[x - c.n_real] : L.rm_ed[x];
+        tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
+        tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
+        tg[x].n = D; tg[x].k = sh ? c.inter_shared : c.inter_dyn; tg[x].ldw = tg[x].k;
+    }
+    umoe_tgemm_args td{};
+    td.groups = tg; td.num_groups = G; td.max_rows = n_tok; td.a = e->hbuf; td.lda = Imax; td.out = e->ybuf; td.ldo = D;
+    td.epilogue = UMOE_EPI_BF16;
+    if ((rc = umoe_tiled_gemm(&td, s))) return rc;
+    PROF(K_DOWN);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------ one layer
 static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStream_t s) {
     const umoe_engine_cfg& c = e->c;
@@ -886,9 +955,11 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     if (e->probe_x1 && n_tok == c.rows && !adm)
         UMOE_HIP(hipMemcpyAsync(e->probe_x1 + (size_t)l * c.rows * D, e->x1, (size_t)c.rows * D * 2, hipMemcpyDeviceToDevice, s));
     if (e->ep_decode(n_tok)) return run_moe_ep(e, l, n_tok, s);
-    // 5. RMSNorm + router                                         model.py:240, core.py:246-291
+    // 5.-8. RMSNorm + router, experts                             model.py:240, core.py:246-291,406-416,344-351
+    const MoeForm form = moe_form(e, L, n_tok);
+    const bool dense = form == MOE_FLAT || form == MOE_RIDERS || form == MOE_ROUTER;
+    UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
     umoe_router_args ra{};
-    const bool dense = dense_mode(e, n_tok);
     ra.x = e->x1; ra.gate_w = L.w.gate_w; ra.norm_w = L.w.post_norm; ra.h_out = e->h2; ra.S = n_tok; ra.D = D;
     ra.n_dyn = c.n_dyn; ra.n_real = c.n_real; ra.n_fix = c.n_fix; ra.logits_bf16 = 1; ra.top_p = c.top_p;
     ra.fixed_top_k = c.fixed_top_k; ra.jitter_eps = c.jitter_eps; ra.rms_eps = c.rms_eps;
@@ -898,107 +969,40 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
         ra.expert_mask = e->all_mask + (size_t)l * c.rows * E;
         ra.top_k = e->all_topk + (size_t)l * c.rows;
     }
-    // dense decode: the GEMMs do not read the routing results (every expert computes every row), only the combine does -- so the
-    // router rides INSIDE the gate/up launch as 16 extra workgroups and only the RMSNorm (h2, which gate/up needs) stays in the
-    // chain as its own small launch: the 4.4 us serial routing chain per token leaves the critical path.
-    const bool fuse_router = dense && e->fuse_router && !tiled && c.n_dyn == 9 && c.n_fix == 2 &&
-                             (D == 2048 || D == 4096) && n_tok <= 16;
-    // In-launch hand-offs need every workgroup of the launch RESIDENT at once (a waiting workgroup never yields its CU): the gate/up box
-    // of 8-wave, 256-register workgroups admits ONE per CU, the flat launch is sized to the CU count itself.  A device that exposes
-    // fewer CUs (partition, CU mask) takes the launch-per-kernel path instead of discovering it by a timeout.
-    const int gu_box = G * ceil_div(2 * Imax / 16, 14);
-    const bool box_fits = e->n_cu <= 0 || gu_box <= e->n_cu;
-    const bool flat_ok = dense && e->flat_moe && e->fuse_moe && e->n_cu > 0 && c.n_dyn == 9 && c.n_fix == 2 &&
-                         umoe_moe_flat_feasible(e->n_cu < 256 ? e->n_cu : 256, n_tok, D, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix);
-    const bool pub_riders = fuse_router && e->rider_pub && (box_fits || flat_ok);
-    if (pub_riders) {
-        rc = 0;                  // no launch here: the riders write h2 inside the gate/up launch and hand it over (ra.h_out stays h2)
-    } else if (fuse_router) {
-        umoe_router_args rn = ra;
-        rn.norm_only = 1;
-        rc = umoe_router_fwd(&rn, s);
-        ra.h_out = nullptr;
-    } else if (dense) {
-        rc = umoe_router_fwd(&ra, s);   // no dispatch tables: the combine reads the mask
-    } else {
-        rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s);
-    }
-    if (rc) return rc;
-    PROF(K_ROUTER);
-    umoe_rider_pub rpub{};
-    rpub.flags = e->ep_words + 1024; rpub.step = e->ep_words; rpub.layer = l; rpub.layers = c.layers; rpub.err = e->ep_words + 1;
-    // 7./8. experts: routed + shared share one launch (the fused / flat launch) or one launch per GEMM
+    // routed + shared experts share every launch.  Dense decode: 7 gate/up pairs / 6 down blocks per 8-wave workgroup -- the per-CU byte
+    // balance decides these kernels (see umoe_gemm.hip; down: 220 workgroups, 22.2 vs 23.7 us with 8 blocks, scripts/kbench.py flat)
     umoe_gemm_args gu{};
     gu.groups = g + 2; gu.groups_host = gh + 2; gu.num_groups = G; gu.max_rows = n_tok;
     gu.max_n_blocks = 2 * Imax / 16; gu.max_k = D;
     gu.a = e->h2; gu.lda = D; gu.out = e->hbuf; gu.ldo = Imax; gu.n_valid = Imax;
-    gu.prologue = UMOE_PRO_PLAIN; gu.epilogue = UMOE_EPI_SWIGLU;
-    if (dense) {             // per-CU byte balance decides this kernel (see umoe_gemm.hip): 7 pairs per workgroup, flat slices
-        gu.nt = 14;
-        if (fuse_router) gu.fused_router = &ra;
-        if (pub_riders) {
-            gu.rider_pub = &rpub;
-            gu.groups_host = e->h_gu_pub.data() + (size_t)l * G;     // shared experts first (riders early in dispatch order)
-        }
-    }
-    // (dense mode with the post-attention RMSNorm in this launch's staging prologue, so that it would not wait for the
-    //  router at all, was measured: 46.9 vs 37.7 us per launch -- 387 workgroups redoing the norm of all 16 rows costs
-    //  more than the dependency it removes; the router kernel writes the normalised rows h2 once instead)
-    if (tiled && G <= 12) {
-        umoe_tgroup_t tg[12];
-        memset(tg, 0, sizeof(tg));
-        for (int x = 0; x < G; ++x) {
-            const umoe_group_t& src = gh[2 + x];     // same row tables as the weight-streaming groups
-            const bool sh = x >= c.n_real;
-            tg[x].w = sh ? L.rm_sg[x - c.n_real] : L.rm_eg[x];
-            tg[x].w2 = sh ? L.rm_su[x - c.n_real] : L.rm_eu[x];
-            tg[x].rows = src.rows; tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
-            tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
-            tg[x].n = sh ? c.inter_shared : c.inter_dyn; tg[x].k = D; tg[x].ldw = D;
-        }
-        umoe_tgemm_args ta{};
-        ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok; ta.a = e->h2; ta.lda = D; ta.out = e->hbuf; ta.ldo = Imax;
-        ta.epilogue = UMOE_EPI_SWIGLU;
-        rc = umoe_tiled_gemm(&ta, s);
-    } else if (!(pub_riders && e->fuse_moe)) {
-        rc = umoe_grouped_gemm(&gu, s);
-    }
-    if (rc) return rc;
-    if (!(pub_riders && e->fuse_moe)) PROF(K_GATEUP);
+    gu.prologue = UMOE_PRO_PLAIN; gu.epilogue = UMOE_EPI_SWIGLU; gu.nt = dense ? 14 : 0;
     umoe_gemm_args dn{};
     dn.groups = g + 2 + G; dn.groups_host = gh + 2 + G; dn.num_groups = G; dn.max_rows = n_tok; dn.max_n_blocks = D / 16;
     dn.max_k = Imax;
     dn.a = e->hbuf; dn.lda = Imax; dn.out = e->ybuf; dn.ldo = D; dn.n_valid = D;
-    dn.prologue = UMOE_PRO_PLAIN; dn.epilogue = UMOE_EPI_BF16;
-    if (dense) dn.nt = 6;    // 220 workgroups of 8 waves: 22.2 vs 23.7 us with 8 blocks per workgroup (scripts/kbench.py flat)
-    if (tiled && G <= 12) {
-        umoe_tgroup_t tg[12];
-        memset(tg, 0, sizeof(tg));
-        for (int x = 0; x < G; ++x) {
-            const umoe_group_t& src = gh[2 + G + x];
-            const bool sh = x >= c.n_real;
-            tg[x].w = sh ? L.rm_sd[x - c.n_real] : L.rm_ed[x];
-            tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
-            tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
-            tg[x].n = D; tg[x].k = sh ? c.inter_shared : c.inter_dyn; tg[x].ldw = tg[x].k;
-        }
-        umoe_tgemm_args ta{};
-        ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok; ta.a = e->hbuf; ta.lda = Imax; ta.out = e->ybuf; ta.ldo = D;
-        ta.epilogue = UMOE_EPI_BF16;
-        rc = umoe_tiled_gemm(&ta, s);
-        if (rc) return rc;
-        PROF(K_DOWN);
-    } else if (pub_riders && e->fuse_moe) {
-        // both expert GEMMs in one launch (words 64.. of ep_words: one flag per gate/up workgroup); shapes that do not allow it
-        // fall back to the two launches
-        rc = 1;
-        {
-            const char* fv = getenv("UMOE_FLAT_MOE");      // (read per enqueue: the step graph captures the choice; A/B scripts toggle it)
-            const bool flat = fv ? atoi(fv) != 0 : e->flat_moe;
-            const int n_wg = e->n_cu < 256 ? e->n_cu : 256;
-            if (e->fp8) {
-                // fp8 expert weights: the same launch on the WP8 blocks -- and nothing else (no bf16 path streams these weights)
-                UMOE_REQUIRE(flat && n_wg > 0 && L.has_f8 && G <= UMOE_MAXE, "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
+    dn.prologue = UMOE_PRO_PLAIN; dn.epilogue = UMOE_EPI_BF16; dn.nt = dense ? 6 : 0;
+    switch (form) {
+        case MOE_TILED:
+            if ((rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s))) return rc;
+            PROF(K_ROUTER);
+            if ((rc = experts_tiled(e, L, gh + 2, n_tok, s))) return rc;
+            break;
+        case MOE_RAGGED:
+            if ((rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s))) return rc;
+            PROF(K_ROUTER);
+            if ((rc = experts_two_launches(e, &gu, &dn, s))) return rc;
+            break;
+        case MOE_FLAT: {
+            // nothing in front: the first S workgroups route one row each (their tables feed the combine), every workgroup normalises
+            // the rows it stages itself (ra.x / ra.norm_w) and publishes its SwiGLU rows to the down slices of the same launch
+            umoe_rider_pub rpub{};
+            rpub.flags = e->ep_words + 1024; rpub.step = e->ep_words; rpub.layer = l; rpub.layers = c.layers; rpub.err = e->ep_words + 1;
+            gu.fused_router = &ra;
+            gu.rider_pub = &rpub;
+            gu.groups_host = e->h_gu_pub.data() + (size_t)l * G;
+            const int n_wg = flat_wgs(e);
+            if (e->fp8) {        // the same launch on the WP8 blocks -- and nothing else (no bf16 path streams these weights)
+                UMOE_REQUIRE(L.has_f8 && G <= UMOE_MAXE, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
                 umoe_group_t g8u[UMOE_MAXE], g8d[UMOE_MAXE];
                 const int8_t* e8u[UMOE_MAXE];
                 const int8_t* e8d[UMOE_MAXE];
@@ -1010,31 +1014,41 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
                 umoe_gemm_args gu8 = gu, dn8 = dn;
                 gu8.groups_host = g8u; dn8.groups_host = g8d;
                 rc = umoe_moe_flat_fp8(&gu8, &dn8, e8u, e8d, e->ep_words + 64, 512 - 64, n_wg, s);
-                UMOE_REQUIRE(rc != 1, "umoe_engine: the fp8 flat expert launch has no schedule for this shape on %d workgroups (layer %d)", n_wg, l);
-                if (rc) return rc;
-                e->expert_launch = 2;
-                e->expert_fp8 = 1;
             } else {
-                if (flat && n_wg > 0) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);
-                e->expert_launch = rc == 0 ? 2 : 0;
-                e->expert_fp8 = 0;
+                rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);
             }
+            UMOE_REQUIRE(rc != 1, "umoe_engine: the %sflat expert launch has no schedule for this shape on %d workgroups (layer %d)", e->fp8 ? "fp8 " : "", n_wg, l);
+            if (rc) return rc;
+            e->expert_launch = 2;
+            e->expert_fp8 = e->fp8 ? 1 : 0;
+            PROF(K_GATEUP);      // (booked as gate/up: zero down launches tell the reader which form ran)
+            break;
         }
-        if (rc == 1 && box_fits) {
-            rc = umoe_moe_fused(&gu, &dn, e->ep_words + 64, 512 - 64, s);
-            if (rc == 0) e->expert_launch = 1;
+        case MOE_RIDERS: {
+            // the GEMMs do not read the routing results (every expert computes every row), only the combine does -- so the router rides
+            // INSIDE the gate/up launch on workgroups that have no tile and only the RMSNorm (h2, which gate/up stages) stays in the chain
+            // as its own small launch: the 4.4 us serial routing chain per token leaves the critical path.  Nothing waits inside these
+            // launches, so they need no co-residency: this is what a device with too few CUs for the flat schedule runs.
+            // (measured and not kept: the RMSNorm in the gate/up launch's staging prologue instead -- 46.9 vs 37.7 us per launch, 387
+            //  workgroups redoing the norm of all 16 rows cost more than the dependency removed)
+            umoe_router_args rn = ra;
+            rn.norm_only = 1;
+            if ((rc = umoe_router_fwd(&rn, s))) return rc;
+            PROF(K_ROUTER);
+            ra.h_out = nullptr;
+            gu.fused_router = &ra;
+            if ((rc = experts_two_launches(e, &gu, &dn, s))) return rc;
+            e->expert_launch = 0;
+            e->expert_fp8 = 0;
+            break;
         }
-        UMOE_REQUIRE(!(rc == 1 && !box_fits), "umoe_engine: no expert launch with in-launch hand-offs fits %d compute units (UMOE_RIDER_PUB=0 selects the launch-per-kernel path)", e->n_cu);
-        if (rc == 1) {
-            if ((rc = umoe_grouped_gemm(&gu, s))) return rc;
-            rc = umoe_grouped_gemm(&dn, s);
-        }
-        if (rc) return rc;
-        PROF(K_GATEUP);          // (the fused launch is booked as gate/up: zero down launches tell the reader which form ran)
-    } else {
-        rc = umoe_grouped_gemm(&dn, s);
-        if (rc) return rc;
-        PROF(K_DOWN);
+        case MOE_ROUTER:
+            if ((rc = umoe_router_fwd(&ra, s))) return rc;      // no dispatch tables: the combine reads the mask
+            PROF(K_ROUTER);
+            if ((rc = experts_two_launches(e, &gu, &dn, s))) return rc;
+            e->expert_launch = 0;
+            e->expert_fp8 = 0;
+            break;
     }
     // 9. combine + residual -> next layer input                   core.py:488,342-351; model.py:242
     umoe_combine_args cb{};
@@ -1045,7 +1059,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     // fused RMSNorm for the consumer of x: the next layer's input_layernorm, or the final norm in front of the head
     cb.norm_w = (l + 1 < c.layers) ? e->layers[l + 1].w.in_norm : e->final_norm; cb.norm_out = e->hin; cb.rms_eps = c.rms_eps;
     const bool cq_fits = e->n_cu <= 0 || n_tok + QKV / 16 <= 2 * e->n_cu;      // riders + QKV tiles resident at once (two 4-wave workgroups per CU)
-    if (dense && T == 1 && !tiled && e->fuse_cq && e->rider_pub && cq_fits && l + 1 < c.layers && D == 2048 && n_tok <= 16 && c.n_fix >= 1 && !e->probe_on()) {
+    if (dense && T == 1 && e->fuse_cq && cq_fits && l + 1 < c.layers && D == 2048 && n_tok <= 16 && c.n_fix >= 1 && !e->probe_on()) {
         e->cb_stash = cb;        // issued by the next layer's QKV launch (run_layer(l + 1) follows immediately)
         e->cb_pending = true;
         return 0;
@@ -1377,20 +1391,17 @@ extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* 
     return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, (hipStream_t)stream);
 }
 
-// An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch: the box grid and the
-// launch-per-GEMM paths would stream bf16 expert weights it does not run on.  Checked on the host before anything is enqueued.
+// An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch (moe_form: MOE_FLAT): the
+// launch-per-kernel forms would stream bf16 expert weights it does not run on.  Checked on the host before anything is enqueued.
 static int fp8_step_check(umoe_engine* e) {
     if (!e->fp8) return 0;
     const umoe_engine_cfg& c = e->c;
-    const char* fv = getenv("UMOE_FLAT_MOE");
-    const bool flat = fv ? atoi(fv) != 0 : e->flat_moe;
     UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: fp8 expert weights are not supported expert parallel (ep_size %d)", c.ep_size);
-    UMOE_REQUIRE(flat, "umoe_engine: fp8 expert weights need the flat expert launch (UMOE_FLAT_MOE=0 selects a bf16 path)");
-    UMOE_REQUIRE(e->rider_pub && e->fuse_router && e->fuse_moe,
-                 "umoe_engine: fp8 expert weights need the flat expert launch with published riders (UMOE_RIDER_PUB / UMOE_FUSE_ROUTER / UMOE_FUSE_MOE = 0 select a bf16 path)");
+    UMOE_REQUIRE(flat_moe_on(), "umoe_engine: fp8 expert weights need the flat expert launch (UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 is the bf16 launch-per-kernel form)");
+    UMOE_REQUIRE(e->fuse_router, "umoe_engine: fp8 expert weights need the flat expert launch with its router riders (UMOE_FUSE_ROUTER=0 selects a bf16 path)");
     UMOE_REQUIRE(dense_mode(e, c.rows) && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096),
                  "umoe_engine: fp8 expert weights need the dense decode layout of the flat expert launch (rows %d)", c.rows);
-    const int n_wg = e->n_cu < 256 ? e->n_cu : 256;
+    const int n_wg = flat_wgs(e);
     UMOE_REQUIRE(n_wg > 0 && umoe_moe_flat_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix) &&
                      umoe_moe_flat_fp8_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix),
                  "umoe_engine: fp8 expert weights: the flat expert launch has no schedule on %d compute units", e->n_cu);

@@ -1,6 +1,6 @@
 // Device side of the flat expert launch (umoe_moe_flat.hip) shared with the expert-parallel flat launch (umoe_moe_ep.hip): the argument
 // block, the LDS tile layout, the bounded flag wait and the two slice bodies (gate/up SwiGLU, down projection) whose tiles, K split and
-// reduction order are those of moe_fused_kernel (umoe_gemm.hip) -- bit-identical outputs whichever launch computes a tile.
+// reduction order are those of wstream_body<14, 1, PLAIN, SWIGLU, 8> / <6, 2, PLAIN, BF16, 8> (umoe_gemm.hip) -- bit-identical outputs whichever launch computes a tile.
 #pragma once
 #include "umoe_common.h"
 #include "umoe_router_dev.h"

@@ -80,26 +80,14 @@ struct umoe_group_pack { umoe_group_t g[UMOE_GROUPS_INLINE]; };
 // FR ("fused router", umoe_gemm_args.fused_router): the z-slice in front of the first group holds one workgroup per token that runs the
 // Top-P router (threads 0..255; umoe_router_dev.h) instead of a GEMM tile -- 16 workgroups on CUs the 226 GEMM workgroups leave
 // idle.  The GEMM of the dense-expert decode layout does not read the router's outputs, the combine launch after it does.
-// PUB (umoe_gemm_args.rider_pub, with FR): the riders also WRITE the normalised rows this GEMM stages (ra.h_out == p.a) and publish
-// one flag per row; the GEMM workgroups request their first weight chunk, then wait for the 16 flags (one lane each, bounded), then
-// stage the rows with sc1 loads -- the hand-off hides behind the weight stream's first round trip and the RMSNorm launch disappears.
-// XW (fused expert launch, moe_fused_kernel below): 1 = this GEMM PUBLISHES its output tile to workgroups of the same launch (SwiGLU
-// epilogue: write-through stores, drain, one flag per workgroup); 2 = this GEMM's activation rows were published that way (weights
-// first, then wait for the producers' flags, then sc1 loads; the second register stage of the weight stream is requested right
-// behind the rows).  Returns 0 when the workgroup finished a tile, 1 when it had none (riders, tile-less workgroups of the box).
+// PUB (wstream_gemm_rk only, never with FR): ROW riders in front of this launch's tiles WRITE the rows this GEMM stages and publish one
+// flag per row (pub); the GEMM workgroups request their first weight chunk, then wait for the flags (one lane each, bounded), then
+// stage the rows with sc1 loads -- the hand-off hides behind the weight stream's first round trip.
 struct wg_coord { unsigned x, y, z, gx; };     // workgroup coordinates inside this GEMM's grid box and the box's x extent
-struct umoe_fuse_x {
-    uint32_t* flags;                        // one word per workgroup of the PRODUCING GEMM (z * gx + x); epochs as in umoe_rider_pub
-    int prod_base[UMOE_GROUPS_INLINE];      // per group of the CONSUMING GEMM: first flag and number of flags it waits for
-    int prod_n[UMOE_GROUPS_INLINE];
-};
-template <int NT, int U, int PRO, int EPI, int WV, bool FR, bool PUB, int XW, bool BV = false>
-__device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_group_pack& gp, const umoe_router_args& ra, const int rider_mode,
-                                            const umoe_rider_pub& pub, const umoe_fuse_x& fx, const wg_coord blk, char* smem
-#ifdef UMOE_TIMELINE
-                                            , tl_state* tl_carry = nullptr      // XW 1: the stamps leave with the caller, written after the second GEMM
-#endif
-) {
+template <int NT, int U, int PRO, int EPI, int WV, bool FR, bool PUB, bool BV = false>
+__device__ __forceinline__ void wstream_body(const umoe_gemm_args& p, const umoe_group_pack& gp, const umoe_router_args& ra, const int rider_mode,
+                                             const umoe_rider_pub& pub, const wg_coord blk, char* smem) {
+    static_assert(!(FR && PUB) && (!PUB || PRO == UMOE_PRO_PLAIN), "wstream_body: row hand-off only without router riders, plain prologue");
     // riders (FR).  rider_mode 1: an extra z-slice in front of the first group (x = token); 2: the launch's DEAD workgroups (x beyond
     // a short group's tiles -- the grid is a box over the widest group) take the tokens in (z, x) order: no extra workgroups, the
     // launch still fits the chip in one wave (with the extra slice 275 workgroups were launched on 256 CUs and 7 real GEMM tiles
@@ -118,22 +106,11 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
         if (token >= 0) {
             if (token < ra.S && blk.y == 0 && threadIdx.x < 256) {
                 TL_ENTER(5);
-                uint32_t* pf = nullptr;
-                uint32_t pe = 0;
-                if constexpr (PUB) {
-                    pf = pub.flags;
-                    pe = *pub.step * (uint32_t)pub.layers + (uint32_t)pub.layer + 1u;
-                }
-                unsigned long long* rsp = nullptr;
-                if constexpr (PUB && PRO == UMOE_PRO_RMSNORM) {   // the scale only (see router4_body rs_pub); no row flags
-                    rsp = pub.rs;
-                    pf = nullptr;
-                }
-                if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, token, threadIdx.x, reinterpret_cast<float*>(smem) TL_PASS, pf, pe, rsp);
-                else router4_body<9, 2, 0, false>(ra, token, threadIdx.x, reinterpret_cast<float*>(smem) TL_PASS, pf, pe, rsp);
+                if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, token, threadIdx.x, reinterpret_cast<float*>(smem) TL_PASS);
+                else router4_body<9, 2, 0, false>(ra, token, threadIdx.x, reinterpret_cast<float*>(smem) TL_PASS);
                 TL_EXIT(5);
             }
-            return 1;
+            return;
         }
     }
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -144,14 +121,14 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
     // (measured and removed: blockIdx.x enumerating equal slices of ALL groups' gate/up pairs inside THIS kernel -- 42.4 vs 37.3 us: a
     //  6-pair slice re-read its 7th register slot; the byte-balanced form is its own launch now, umoe_moe_flat.hip)
     const unsigned zg = blk.z - ((FR && rider_mode == 1) ? 1u : 0u);      // group index
-    // BV (descriptors known to be by value: riders / the fused launch need them, the small decode launches are dispatched on it): plain
+    // BV (descriptors known to be by value: the riders need them, the small decode launches are dispatched on it): plain
     // kernel-argument reads = scalar loads.  Left to a run-time choice the compiler selects between the two ADDRESSES and reads the
     // descriptor with flat loads through the vector memory path -- two dependent round trips in front of the first request.
-    const umoe_group_t g = (BV || FR || XW != 0) ? gp.g[zg] : (p.groups_host ? gp.g[zg] : p.groups[zg]);
+    const umoe_group_t g = (BV || FR) ? gp.g[zg] : (p.groups_host ? gp.g[zg] : p.groups[zg]);
     const int ksplit = p.ksplit > 1 ? p.ksplit : 1;
     const int ks = ksplit > 1 ? (int)(blk.x % ksplit) : 0;      // K-slice of this workgroup (fp32 partial slab `ks`)
     const int nb0 = (ksplit > 1 ? (int)(blk.x / ksplit) : (int)blk.x) * NT;
-    if (nb0 >= g.n_blocks) return 1;
+    if (nb0 >= g.n_blocks) return;
 
     const int K = g.k, KB = K >> 5;
     // this workgroup covers MFMA k-steps [ia, ib) of every K-quarter; only those activation chunks are staged
@@ -203,10 +180,8 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
     //    requested FIRST, the weight stream right behind them -- the tile is staged while the first chunk is in flight;
     //  * ragged groups: the activation addresses hang on device-produced tables (count -> offset -> gather list), so the
     //    weight stream goes first and overlaps that chain.
-    // (PUB / XW 2: weights first too -- the rows do not exist yet; PUB with the RMSNorm prologue: the RAW rows exist, only their scale
-    //  is handed over, so the rows are requested first like any static group's)
-    constexpr bool ROWS_HANDED = (PUB && PRO != UMOE_PRO_RMSNORM) || XW == 2;
-    const bool ragged = ROWS_HANDED || g.count || g.row_off || g.rows;
+    // (PUB: weights first too -- the rows do not exist yet)
+    const bool ragged = PUB || g.count || g.row_off || g.rows;
     // second register stage requested before the staging too (static groups): HBM has work queued for the whole prologue.
     // Only where the registers allow it without spilling (checked per instantiation with -S: private_segment_fixed_size 0).
     constexpr bool DEEP = false;   // measured: gate/up NT 14 35.3 -> 42.6 us, down 23.8 -> 29.8 us -- MORE bytes in flight made it slower
@@ -215,43 +190,15 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
     // only when the rows were there.  Result (scripts/timeline_wgs.py): detection did NOT get earlier (rows staged 7.4 vs 6.6 us after
     // entry, riders' flag stored at 3.3 us either way) -- the 3 us between flag store and detection are the memory system's latency
     // under the weight stream (write-through of the flag, the poll's own round trip), not the wave's queue.
-    const bool poller = ROWS_HANDED && UMOE_POLLER_WAVE && wave == WV - 1;
+    const bool poller = PUB && UMOE_POLLER_WAVE && wave == WV - 1;
     if (ragged && i0 < i1 && !poller) load_chunk(w0, i0);
-    // (XW 2: measured on the fused expert launch, 300 decode steps: second register stage requested here, in front of the wait for
-    //  the producers, 3.26-3.29 ms/step; right behind the rows 3.26-3.28; a THIRD stage in front of the wait 3.40-3.43 -- more bytes
-    //  in flight per CU made the launch slower, as in the two-launch form)
     TL_MARK(KID, 4);
 
     const int count = g.count ? *g.count : g.static_count;
     const int roff = g.row_off ? *g.row_off : 0;
     const int row0 = blk.y * 16;
-    if (row0 >= count) return 1;   // (an expert no row chose: its first chunk was requested for nothing -- rare at 16 rows)
-    if constexpr (XW == 2) {
-        // wait for the workgroups of THIS launch that produced this group's rows: lane i of wave 0 polls producer i's flag (bounded)
-        const int np = fx.prod_n[zg];
-        if (UMOE_POLLER_WAVE ? (poller && lane < np) : (tid < np)) {
-            const int tid = lane;      // (flag index of this lane)
-            const uint32_t epoch = *pub.step * (uint32_t)pub.layers + (uint32_t)pub.layer + 1u;
-            umoe_gu32* f = reinterpret_cast<umoe_gu32*>(reinterpret_cast<uintptr_t>(fx.flags + fx.prod_base[zg] + tid));
-            umoe_gu32* err = reinterpret_cast<umoe_gu32*>(reinterpret_cast<uintptr_t>(pub.err));
-            const unsigned long long t0 = wall_clock64();
-            for (unsigned spins = 0;; ++spins) {
-                if ((int32_t)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - epoch) >= 0) break;
-                __builtin_amdgcn_s_sleep(1);
-                if ((spins & 1023u) == 1023u) {
-                    if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;      // an earlier cause (kept) ends every wait
-                    if (wall_clock64() - t0 > 200000000ull) {      // this lane's OWN timeout: first cause wins
-                        uint32_t zero = 0u;
-                        __hip_atomic_compare_exchange_strong(err, &zero, 3u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-            }
-        }
-        if (poller && i0 < i1) load_chunk(w0, i0);
-        __syncthreads();
-    }
-    if constexpr (PUB && PRO != UMOE_PRO_RMSNORM) {
+    if (row0 >= count) return;   // (an expert no row chose: its first chunk was requested for nothing -- rare at 16 rows)
+    if constexpr (PUB) {
         // wait for the riders of THIS launch: lanes 0..count-1 of wave 0 poll one row flag each; bounded (a rider that never runs --
         // an admitted workgroup that is not resident -- ends the wait with the sticky error word set)
         if (UMOE_POLLER_WAVE ? (poller && lane < count) : (tid < count)) {
@@ -320,9 +267,9 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
 #pragma unroll
             for (int n = 0; n < 16; ++n) {
                 const int h = n >> 2, i = min(ib0 + sub + TPR * (n & 3), QW - 1);
-                if constexpr (ROWS_HANDED) {   // rows handed over inside this launch: every load of them is an sc1 load
+                if constexpr (PUB) {   // rows handed over inside this launch: every load of them is an sc1 load
                     typedef uint32_t u32x4_pub __attribute__((ext_vector_type(4)));
-                    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.a), 0, XW == 2 ? 0x7fffffff : 16 * p.lda * 2, 0x00020000);
+                    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.a), 0, 16 * p.lda * 2, 0x00020000);
                     const u32x4_pub t4 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((arow * (long)p.lda + g.a_col_off + (h * Q8 + ia + i) * 8) * 2), 0, 16);
                     buf[n] = make_uint4(t4[0], t4[1], t4[2], t4[3]);
                 } else {
@@ -335,39 +282,8 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
                 if (DEEP && i0 + U < i1) load_chunk(w1, i0 + U);   // both register stages in flight while the tile is staged
                 __builtin_amdgcn_sched_barrier(0);
             }
-
-            if (XW == 2 && ib0 == 0) {     // the second register stage right behind the rows (returns: first stage, rows, second stage)
-                __builtin_amdgcn_sched_barrier(0);
-                if (i0 + U < i1) load_chunk(w1, i0 + U);
-                __builtin_amdgcn_sched_barrier(0);
-            }
             TL_MARK(KID, 9);
-            if (single && PUB) {
-                // the row's scale comes from its rider (one {rs, epoch} granule per row, umoe_router_dev.h rs_pub): every thread of the
-                // row polls that granule (two addresses per wave), bounded; the raw row is already in registers
-                if (tid < 4 * Q8) st16(nw_lds + tid * 16, nw1);
-                const uint32_t epoch = *pub.step * (uint32_t)pub.layers + (uint32_t)pub.layer + 1u;
-                typedef uint32_t u32x2_g __attribute__((ext_vector_type(2)));
-                const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(pub.rs, 0, 8 * UMOE_EP_PARTS, 0x00020000);
-                umoe_gu32* err = reinterpret_cast<umoe_gu32*>(reinterpret_cast<uintptr_t>(pub.err));
-                const unsigned long long t0 = wall_clock64();
-                u32x2_g gr = {0u, 0u};
-                for (unsigned spins = 0;; ++spins) {
-                    gr = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (valid ? r : row0) * 8, 0, 16);
-                    if ((int32_t)(gr[1] - epoch) >= 0) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((spins & 1023u) == 1023u) {
-                        if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;      // an earlier cause (kept) ends every wait
-                        if (wall_clock64() - t0 > 200000000ull) {      // this lane's OWN timeout: first cause wins
-                            uint32_t zero = 0u;
-                            __hip_atomic_compare_exchange_strong(err, &zero, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            break;
-                        }
-                    }
-                }
-                rs = __int_as_float((int)gr[0]);
-                __syncthreads();
-            } else if (single) {
+            if (single) {
                 float ss = 0.f;
                 if (TPR == 32 && Q8 == 64) {
                     // K = 2048 on 8 waves: the SAME summation tree as the router body (umoe_router_dev.h router4_body: lane l of wave h
@@ -490,7 +406,7 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
         }
     };
     for (int i = i0; i < i1; i += 2 * U) {
-        if (i + U < i1 && !(((DEEP && !ragged) || XW == 2) && i == i0)) load_chunk(w1, i + U);
+        if (i + U < i1 && !(DEEP && !ragged && i == i0)) load_chunk(w1, i + U);
         compute_chunk(w0, i);
         if (i + 2 * U < i1) load_chunk(w0, i + 2 * U);
         if (i + U < i1) compute_chunk(w1, i + U);
@@ -516,7 +432,7 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
 
     // ---- epilogue: lane (h, mm) owns features 4h..4h+3 of token row mm; tiles are spread over the waves -----
     const int r = row0 + mm;
-    if (XW != 1 && r >= count) return 0;
+    if (r >= count) return;
     const long orow = (long)g.out_row_base + roff + r;
     if (EPI == UMOE_EPI_SWIGLU) {
         for (int q = wave; q < NT / 2; q += WV) {
@@ -533,30 +449,10 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
                 y[j] = f2bf(si * up);
             }
             uint16_t* o = reinterpret_cast<uint16_t*>(p.out) + orow_q * p.ldo + col;
-            if constexpr (XW == 1) {     // handed to workgroups of this launch: write-through (sc1) store
-                typedef uint32_t u32x2_pub __attribute__((ext_vector_type(2)));
-                const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint16_t*>(p.out), 0, 0x7fffffff, 0x00020000);
-                const u32x2_pub v2 = {(uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16)};
-                if (r < count) __builtin_amdgcn_raw_buffer_store_b64(v2, rsrc, (int)((orow_q * p.ldo + col) * 2), 0, 16);
-            } else {
-                *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16));
-            }
+            *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16));
         }
-        if constexpr (XW == 1) {
-            // publish: every storing wave drains its write-through stores, the workgroup meets, one lane raises this workgroup's flag
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                const uint32_t epoch = *pub.step * (uint32_t)pub.layers + (uint32_t)pub.layer + 1u;
-                __hip_atomic_store(reinterpret_cast<umoe_gu32*>(reinterpret_cast<uintptr_t>(fx.flags + blk.z * blk.gx + blk.x)), epoch, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-#ifdef UMOE_TIMELINE
-        if (XW == 1 && tl_carry) { tl_st.m[2] = wall_clock64(); *tl_carry = tl_st; return 0; }
-#endif
         TL_EXIT(KID);
-        return 0;
+        return;
     }
 #pragma unroll
     for (int q = 0; q < TPW; ++q) {
@@ -599,15 +495,13 @@ __device__ __forceinline__ int wstream_body(const umoe_gemm_args& p, const umoe_
         }
     }
     TL_EXIT(KID);
-    return 0;
 }
 
-template <int NT, int U, int PRO, int EPI, int WV, bool FR = false, bool PUB = false, bool BV = false>
-__global__ __launch_bounds__(WV * 64, 2) void wstream_gemm(const umoe_gemm_args p, const umoe_group_pack gp, const umoe_router_args ra, const int rider_mode,
-                                                            const umoe_rider_pub pub) {
+template <int NT, int U, int PRO, int EPI, int WV, bool FR = false, bool BV = false>
+__global__ __launch_bounds__(WV * 64, 2) void wstream_gemm(const umoe_gemm_args p, const umoe_group_pack gp, const umoe_router_args ra, const int rider_mode) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const umoe_fuse_x fx{};
-    (void)wstream_body<NT, U, PRO, EPI, WV, FR, PUB, 0, BV>(p, gp, ra, rider_mode, pub, fx, wg_coord{blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x}, smem);
+    const umoe_rider_pub pub{};
+    wstream_body<NT, U, PRO, EPI, WV, FR, false, BV>(p, gp, ra, rider_mode, pub, wg_coord{blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x}, smem);
 }
 
 // A one-block-per-workgroup decode GEMM (QKV with bias / o_proj with residual: NT 1, 4 waves) with ROW riders in front
@@ -622,41 +516,9 @@ __global__ __launch_bounds__(256, 2) void wstream_gemm_rk(const umoe_gemm_args p
         combine_row_dense<RK == 4>(r2.cb, r2, (int)blockIdx.x, reinterpret_cast<float*>(smem), pub.flags + blockIdx.x, epoch);
         return;
     }
-    const umoe_fuse_x fx{};
     const umoe_router_args ra{};
-    (void)wstream_body<1, 16, UMOE_PRO_PLAIN, EPI, 4, false, true, 0, true>(p, gp, ra, 0, pub, fx,
-                                                                        wg_coord{blockIdx.x - (unsigned)r2.n_riders, 0u, 0u, gridDim.x - (unsigned)r2.n_riders}, smem);
-}
-
-// The two expert GEMMs of a dense decode layer in ONE launch (8 routed + 2 shared experts, 16 rows): every workgroup computes its
-// gate/up slice (7 pairs, riders and their hand-off as in the gate/up launch), publishes it, then takes a down-projection slice (6
-// blocks): it requests that slice's first weights, waits for the gate/up workgroups of ITS expert only, stages the rows and streams.
-// What the fusion buys: no launch boundary, and the down projection's weight stream starts while other workgroups still finish
-// gate/up -- as two launches the chip idled through the down projection's 7 us prologue.  Same tiles, same K split, same reduction
-// order as the two launches: bit-identical outputs.
-template <int GPRO>     // prologue of the gate/up GEMM: PLAIN = the riders hand the normalised rows over, RMSNORM = only their scales
-__global__ __launch_bounds__(512, 1) void moe_fused_kernel(const umoe_gemm_args pg, const umoe_group_pack gg, const umoe_gemm_args pd, const umoe_group_pack gd,
-                                                            const umoe_router_args ra, const int rider_mode, const umoe_rider_pub pub, const umoe_fuse_x fx,
-                                                            const int dn_per_group) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const wg_coord b{blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x};
-#ifdef UMOE_TIMELINE
-    tl_state tl_first;
-    if (wstream_body<14, 1, GPRO, UMOE_EPI_SWIGLU, 8, true, true, 1>(pg, gg, ra, rider_mode, pub, fx, b, smem, &tl_first)) return;
-#else
-    if (wstream_body<14, 1, GPRO, UMOE_EPI_SWIGLU, 8, true, true, 1>(pg, gg, ra, rider_mode, pub, fx, b, smem)) return;
-#endif
-    // live index of this workgroup among the gate/up tiles -> its down-projection slice
-    int li = (int)b.x;
-    for (unsigned i = 0; i < b.z; ++i) li += (gg.g[i].n_blocks + 13) / 14;
-    const unsigned dz = (unsigned)(li / dn_per_group), dx = (unsigned)(li % dn_per_group);
-    if ((int)dz < pd.num_groups) {
-        __syncthreads();     // (the reduction slab of the first GEMM is the staging area of the second)
-        (void)wstream_body<6, 2, UMOE_PRO_PLAIN, UMOE_EPI_BF16, 8, false, false, 2>(pd, gd, ra, 0, pub, fx, wg_coord{dx, 0u, dz, (unsigned)dn_per_group}, smem);
-    }
-#ifdef UMOE_TIMELINE
-    tl_exit(tl_first, 2, tl_first.m[2]);
-#endif
+    wstream_body<1, 16, UMOE_PRO_PLAIN, EPI, 4, false, true, true>(p, gp, ra, 0, pub, wg_coord{blockIdx.x - (unsigned)r2.n_riders, 0u, 0u, gridDim.x - (unsigned)r2.n_riders},
+                                                                   smem);
 }
 
 UMOE_TL_SETTER(gemm)
@@ -669,19 +531,19 @@ static size_t gemm_lds_bytes(int max_k, int NT, int WV, int ksplit, int pro = UM
     return a > red ? a : red;
 }
 
-template <int NT, int U, int PRO, int EPI, int WV = 4, bool FR = false, bool PUB = false, bool BV = false>
+template <int NT, int U, int PRO, int EPI, int WV = 4, bool FR = false, bool BV = false>
 static int launch_gemm(const umoe_gemm_args* a, hipStream_t s) {
     // the small decode launches (QKV, o_proj, codec head: one or two blocks per 4-wave workgroup, plain prologue) and the dense decode
     // down projection: by-value descriptors known at compile time when the host passed them (see wstream_body, BV)
     if constexpr (!BV && !FR && PRO == UMOE_PRO_PLAIN && ((NT <= 2 && WV == 4 && EPI != UMOE_EPI_SWIGLU) || (NT == 6 && WV == 8 && EPI == UMOE_EPI_BF16))) {
-        if (a->groups_host && a->num_groups <= UMOE_GROUPS_INLINE) return launch_gemm<NT, U, PRO, EPI, WV, FR, PUB, true>(a, s);
+        if (a->groups_host && a->num_groups <= UMOE_GROUPS_INLINE) return launch_gemm<NT, U, PRO, EPI, WV, FR, true>(a, s);
     }
     const int ksplit = a->ksplit > 1 ? a->ksplit : 1;
     const size_t lds = gemm_lds_bytes(a->max_k, NT, WV, ksplit, PRO);
     UMOE_REQUIRE(lds <= 160 * 1024, "umoe_grouped_gemm: K=%d needs %zu bytes of LDS (> 160 KiB)", a->max_k, lds);
     static size_t configured = 0;  // per instantiation
     if (lds > configured) {
-        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wstream_gemm<NT, U, PRO, EPI, WV, FR, PUB, BV>),
+        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wstream_gemm<NT, U, PRO, EPI, WV, FR, BV>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         configured = lds;
     }
@@ -706,18 +568,7 @@ static int launch_gemm(const umoe_gemm_args* a, hipStream_t s) {
         rider_mode = (dead >= ra.S && ksplit == 1 && grid.y == 1 && force != 1) ? 2 : 1;
         if (rider_mode == 1) grid.z += 1;        // the router's workgroups: x = token, z = 0 (in front of the first group)
     }
-    umoe_rider_pub pub;
-    memset(&pub, 0, sizeof(pub));
-    if (PUB) {
-        pub = *reinterpret_cast<const umoe_rider_pub*>(a->rider_pub);
-        UMOE_REQUIRE(pub.flags && pub.step && pub.err && ra.h_out == a->a && ra.norm_w && grid.y == 1 && a->max_rows <= 16 && a->groups_host,
-                     "umoe_grouped_gemm: rider_pub needs flags / step / err, fused_router->h_out == a (with norm_w), <= 16 rows, host descriptors");
-        for (int i = 0; i < a->num_groups; ++i)
-            UMOE_REQUIRE(!a->groups_host[i].rows && !a->groups_host[i].count && !a->groups_host[i].row_off && a->groups_host[i].a_row_base == 0 &&
-                             a->groups_host[i].a_col_off == 0 && a->groups_host[i].static_count == ra.S,
-                         "umoe_grouped_gemm: rider_pub needs static groups over rows [0, S) of `a` (group %d)", i);
-    }
-    wstream_gemm<NT, U, PRO, EPI, WV, FR, PUB, BV><<<grid, WV * 64, lds, s>>>(b, gp, ra, rider_mode, pub);
+    wstream_gemm<NT, U, PRO, EPI, WV, FR, BV><<<grid, WV * 64, lds, s>>>(b, gp, ra, rider_mode);
     UMOE_LAUNCH_CHECK();
     return 0;
 }
@@ -759,65 +610,6 @@ int umoe_gemm_riders(const umoe_gemm_args* a, int kind, const umoe_rider2* r2, c
         }
         wstream_gemm_rk<UMOE_EPI_BF16, 4><<<grid, 256, lds, s>>>(*a, gp, *pub, *r2);
     }
-    UMOE_LAUNCH_CHECK();
-    return 0;
-}
-
-int umoe_moe_fused(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, hipStream_t s) {
-    UMOE_REQUIRE(gu && dn && flags, "umoe_moe_fused: null argument");
-    const int G = gu->num_groups;
-    if (!(gu->fused_router && gu->rider_pub && gu->groups_host && dn->groups_host && G == dn->num_groups && G <= UMOE_GROUPS_INLINE && gu->nt == 14 &&
-          dn->nt == 6 && gu->prologue == UMOE_PRO_PLAIN &&
-          gu->epilogue == UMOE_EPI_SWIGLU && dn->prologue == UMOE_PRO_PLAIN &&
-          dn->epilogue == UMOE_EPI_BF16 && gu->ksplit <= 1 && dn->ksplit <= 1 && gu->max_rows <= 16 && dn->max_rows <= 16 &&
-          dn->a == gu->out && dn->lda == gu->ldo && !dn->fused_router && gu->max_k % 32 == 0 && dn->max_k % 32 == 0))
-        return 1;
-    const umoe_router_args* r = gu->fused_router;
-    const int gx = ceil_div(gu->max_n_blocks, 14), per = ceil_div(dn->max_n_blocks, 6);
-    int live = 0, dead = 0;
-    for (int i = 0; i < G; ++i) {
-        const umoe_group_t& a = gu->groups_host[i];
-        const umoe_group_t& b = dn->groups_host[i];
-        if (a.rows || a.count || a.row_off || a.a_row_base || a.a_col_off || a.static_count != r->S || b.rows || b.count || b.row_off || b.a_col_off ||
-            b.static_count != r->S || b.bias || a.bias)
-            return 1;
-        live += ceil_div(a.n_blocks, 14);
-        dead += gx - ceil_div(a.n_blocks, 14);
-    }
-    if (dead < r->S || live < G * per || G * gx > flag_words) return 1;
-    if (!(r->S <= 16 && r->n_dyn == 9 && r->n_fix == 2 && (r->D == 2048 || r->D == 4096) && r->x && r->gate_w && r->expert_mask && !r->logits_in &&
-          !r->norm_only && r->norm_w))
-        return 1;
-    // (measured and removed: the riders handing over only the rows' RMSNorm scales while the GEMM workgroups normalise the raw rows
-    //  themselves -- 3.105-3.11 vs 3.075-3.087 ms/step; and no hand-off at all, every workgroup normalising in its prologue: 3.42 vs 3.36)
-    if (!(r->h_out == gu->a)) return 1;
-    umoe_fuse_x fx;
-    memset(&fx, 0, sizeof(fx));
-    fx.flags = flags;
-    for (int i = 0; i < G; ++i) {      // the gate/up group whose output rows this down group reads
-        const umoe_group_t& b = dn->groups_host[i];
-        int j = -1;
-        for (int t = 0; t < G; ++t)
-            if (gu->groups_host[t].out_row_base == b.a_row_base) j = t;
-        if (j < 0 || gu->groups_host[j].n_blocks * 8 != b.k || ceil_div(gu->groups_host[j].n_blocks, 14) > 64) return 1;
-        fx.prod_base[i] = j * gx;
-        fx.prod_n[i] = ceil_div(gu->groups_host[j].n_blocks, 14);
-    }
-    const size_t l1 = gemm_lds_bytes(gu->max_k, 14, 8, 1, gu->prologue), l2 = gemm_lds_bytes(dn->max_k, 6, 8, 1), lds = l1 > l2 ? l1 : l2;
-    if (lds > 160 * 1024) return 1;
-    static size_t configured = 0;
-    if (lds > configured) {
-        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&moe_fused_kernel<UMOE_PRO_PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = lds;
-    }
-    umoe_group_pack gg, gd;
-    memset(&gg, 0, sizeof(gg));
-    memset(&gd, 0, sizeof(gd));
-    memcpy(gg.g, gu->groups_host, sizeof(umoe_group_t) * G);
-    memcpy(gd.g, dn->groups_host, sizeof(umoe_group_t) * G);
-    const umoe_rider_pub pub = *reinterpret_cast<const umoe_rider_pub*>(gu->rider_pub);
-    UMOE_REQUIRE(pub.flags && pub.step && pub.err, "umoe_moe_fused: rider_pub needs flags / step / err");
-    moe_fused_kernel<UMOE_PRO_PLAIN><<<dim3((unsigned)gx, 1, (unsigned)G), 512, lds, s>>>(*gu, gg, *dn, gd, *r, /*rider_mode*/ 2, pub, fx, per);
     UMOE_LAUNCH_CHECK();
     return 0;
 }
@@ -872,9 +664,9 @@ extern "C" int umoe_grouped_gemm(const umoe_gemm_args* a, umoe_stream_t stream) 
     UMOE_REQUIRE((a->lda & 7) == 0, "umoe_grouped_gemm: lda must be a multiple of 8 (16-byte rows)");
     UMOE_REQUIRE(a->ksplit <= 1 || (a->epilogue == UMOE_EPI_F32_RAW && a->prologue == UMOE_PRO_PLAIN && a->ksplit <= 4),
                  "umoe_grouped_gemm: ksplit > 1 needs the plain prologue and the raw fp32 partial-slab epilogue");
-    UMOE_REQUIRE(!a->fused_router || (a->epilogue == UMOE_EPI_SWIGLU && a->nt == 14 &&
-                                      (a->prologue == UMOE_PRO_PLAIN || (a->prologue == UMOE_PRO_RMSNORM && !a->rider_pub && a->max_k == 2048))),
-                 "umoe_grouped_gemm: fused_router rides only in the SwiGLU launch with nt = 14 (RMSNorm prologue: K 2048, no rider_pub)");
+    UMOE_REQUIRE(!a->rider_pub, "umoe_grouped_gemm: rider_pub (rows handed over inside the launch) is read by the flat expert launch only");
+    UMOE_REQUIRE(!a->fused_router || (a->epilogue == UMOE_EPI_SWIGLU && a->nt == 14 && a->prologue == UMOE_PRO_PLAIN),
+                 "umoe_grouped_gemm: fused_router rides only in the plain-prologue SwiGLU launch with nt = 14");
     hipStream_t s = (hipStream_t)stream;
     const int pro = a->prologue, epi = a->epilogue;
     if (pro == UMOE_PRO_RMSNORM) {
@@ -918,7 +710,6 @@ extern "C" int umoe_grouped_gemm(const umoe_gemm_args* a, umoe_stream_t stream) 
                                      a->groups_host && a->num_groups <= UMOE_GROUPS_INLINE,
                                  "umoe_grouped_gemm: fused_router needs <= 16 rows, n_dyn 9 / n_fix 2, D 2048 / 4096, S <= %d workgroups of the launch",
                                  ceil_div(a->max_n_blocks, 14));
-                    if (a->rider_pub) return launch_gemm<14, 1, UMOE_PRO_PLAIN, UMOE_EPI_SWIGLU, 8, true, true>(a, s);
                     return launch_gemm<14, 1, UMOE_PRO_PLAIN, UMOE_EPI_SWIGLU, 8, true>(a, s);
                 }
                 return launch_gemm<14, 1, UMOE_PRO_PLAIN, UMOE_EPI_SWIGLU, 8>(a, s);

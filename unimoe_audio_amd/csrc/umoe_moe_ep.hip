@@ -23,7 +23,7 @@
 // return slab: every phase C workgroup adds 1 on every destination; the reader waits for rounds x workgroups).  Every poll is bounded
 // and keeps the first error cause in the sticky word (1 a peer's rows / counters, 3 the shared experts' rows, 4 the operand-order tiles, 5 a
 // local expert's h tiles did not arrive).  Bit-identical to ep_size 1: every (expert, row tile, 16-feature block) product
-// keeps the K split over 8 waves and the fixed-order reduction of moe_flat_kernel / moe_fused_kernel.
+// keeps the K split over 8 waves and the fixed-order reduction of moe_flat_kernel (= wstream_body<14, 1, PLAIN, SWIGLU, 8> / <6, 2, PLAIN, BF16, 8>, umoe_gemm.hip).
 #include <stdlib.h>
 #include <string.h>
 
@@ -320,8 +320,8 @@ __global__ __launch_bounds__(512, 1) void moe_ep_kernel(const epf_args P, const 
 #ifdef UMOE_TIMELINE
                 TL_ENTER(5);
 #endif
-                if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, first, tid, rl TL_PASS, nullptr, 0u, nullptr);
-                else router4_body<9, 2, 0, false>(ra, first, tid, rl TL_PASS, nullptr, 0u, nullptr);
+                if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, first, tid, rl TL_PASS);
+                else router4_body<9, 2, 0, false>(ra, first, tid, rl TL_PASS);
             } else {
                 __syncthreads();
                 __syncthreads();

@@ -1,11 +1,12 @@
 // The two expert GEMMs of a dense decode layer (8 routed + 2 shared experts, <= 16 rows) in ONE launch of ONE workgroup per CU, with a
 // STATIC SCHEDULE that balances the bytes every CU takes in (decode engine only; replaces core.py:406-416,34-49,344-351 for the
-// decode shape, like moe_fused_kernel of umoe_gemm.hip whose tiles, K split and reduction order it keeps: bit-identical outputs).
+// decode shape; tiles, K split and reduction order are those of the two launches wstream_body<14, 1, PLAIN, SWIGLU, 8> and
+// <6, 2, PLAIN, BF16, 8> of umoe_gemm.hip: bit-identical outputs).
 //
 // Why.  A weight-streaming workgroup takes in ~26 GB/s (~10.5 B/clk/CU: MI355X_MICROARCH.md "global_load_dwordx4 (HBM-bound)"), so a
 // launch of one 8-wave workgroup per CU ends when its HEAVIEST CU has taken in its bytes: every timing of round 1/2 fits bytes-per-CU /
 // 26 GB/s (7 pairs = 896 KiB -> 35-37 us; 8 pairs -> 43 us; two 512 KiB workgroups on one CU -> 39 us; 7 pairs + 6 down blocks =
-// 1412 KiB -> 57 us).  The box grid of moe_fused_kernel gives 226 of the 256 CUs 7 gate/up pairs + 6 down blocks and leaves 30 idle;
+// 1412 KiB -> 57 us).  A box grid over the experts (7 pairs per workgroup) gives 226 of the 256 CUs 7 gate/up pairs + 6 down blocks and leaves 30 idle;
 // spread evenly the layer's 304 MB are 1161 KiB per CU.  Here every CU gets a slice of the FLAT list of gate/up pairs (5-7 pairs,
 // possibly straddling two experts) and, behind it, a slice of ONE expert's down projection (1-6 blocks), both from a table the host
 // computes once (flat_plan): the slices are sized so that every workgroup ends at the same time under a small timing model that knows
@@ -14,7 +15,7 @@
 // they route their row, then take a (lighter) slice like everybody else -- no extra workgroups, all n_wg are resident at once.  Nobody
 // waits for them: every workgroup normalises the 16 rows itself while its first weight chunk is in flight (flat_gateup).
 //
-// Hand-offs as in moe_fused_kernel (cdna_hip_programming.md Guideline 16 R1): write-through payload, every storing wave drains, one
+// Hand-offs (cdna_hip_programming.md Guideline 16 R1): write-through payload, every storing wave drains, one
 // flag per part, relaxed agent-scope poll (bounded, sticky error word), every load of handed-over bytes an sc1 load.
 #include <stdlib.h>
 #include <string.h>
@@ -53,8 +54,8 @@ __device__ __forceinline__ void moe_flat_body(const flat_args& A, const umoe_rou
 #ifdef UMOE_TIMELINE
             TL_ENTER(5);
 #endif
-            if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, token, threadIdx.x, rl TL_PASS, nullptr, 0u, nullptr);
-            else router4_body<9, 2, 0, false>(ra, token, threadIdx.x, rl TL_PASS, nullptr, 0u, nullptr);
+            if (ra.logits_bf16) router4_body<9, 2, 1, false>(ra, token, threadIdx.x, rl TL_PASS);
+            else router4_body<9, 2, 0, false>(ra, token, threadIdx.x, rl TL_PASS);
         } else {
             __syncthreads();
             __syncthreads();

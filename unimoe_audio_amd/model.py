@@ -749,7 +749,7 @@ class DecodeEngine:
         done = bool(int(self.state[4 * self.batch + 2].item()))
         code = self.handoff_error()            # (the host is synchronised here anyway: fail loudly instead of decoding on stale rows)
         if code and not (self.ep is not None and code == 1):     # (an EP receive timeout is the caller's to handle: ep_error())
-            raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_RIDER_PUB=0 selects the launch-per-kernel path")
+            raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 selects the launch-per-kernel path")
         if self.ep is not None and self.ep.size > 1 and self.ep.mode != "loopback" and self.ep.group is not False:
             # expert parallel: every rank keeps stepping until ALL are done (a rank that stopped would starve its peers' receives)
             import torch.distributed as dist
@@ -942,7 +942,7 @@ class DecodeEngine:
         st = self.state.cpu()
         code = self.handoff_error()
         if code:
-            raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_RIDER_PUB=0 selects the launch-per-kernel path")
+            raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 selects the launch-per-kernel path")
         return st
 
     def row_done(self, state_cpu: torch.Tensor, b: int) -> bool:
@@ -978,8 +978,9 @@ class DecodeEngine:
         return out
 
     def info(self, key: str) -> int:
-        """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 1 box-grid fused, 2 flat), "n_cu",
-        "expert_fp8" (1: the last dense decode layer ran the fp8 flat launch)."""
+        """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 2 flat, 3 the one-launch
+        expert-parallel MoE half; 1 was the removed box-grid launch and is never returned), "n_cu", "expert_fp8" (1: the last dense decode
+        layer ran the fp8 flat launch)."""
         return int(L.lib().umoe_engine_info(self.h, key.encode()))
 
     def write_buffer(self, name: str, src: torch.Tensor, offset_bytes: int = 0) -> None:
