@@ -83,7 +83,8 @@ def drop_keep_mask(logits: torch.Tensor, expert_mask: torch.Tensor, n_dyn: int, 
             continue
         v = logits[sel, e].float()
         order = sorted(range(sel.numel()), key=lambda i: (-float(v[i]), int(sel[i])))
-        keep[sel[torch.tensor(order[:cap])], e] = 1
+        # int64: the empty list of capacity 0 would otherwise make a float index
+        keep[sel[torch.tensor(order[:cap], dtype=torch.int64)], e] = 1
     return torch.logical_and(expert_mask, keep).to(dt)
 
 

@@ -294,11 +294,14 @@ extern "C" int umoe_permute_fwd(const uint16_t* x, int D, const int32_t* slot_to
 // arithmetic.  torch.topk leaves the order among EQUAL values unspecified; here ties at the capacity boundary keep the lowest
 // token indices (identical to the reference whenever the capacity-th and the next logit of a column differ).
 __device__ __forceinline__ uint32_t drop_key(const void* logits, int is_bf16, size_t idx) {
+    // -0.0 takes the key of +0.0: the two compare equal as floats, so the token index decides between them like any other tie
     if (is_bf16) {
-        const uint32_t u = reinterpret_cast<const uint16_t*>(logits)[idx];
+        uint32_t u = reinterpret_cast<const uint16_t*>(logits)[idx];
+        if (u == 0x8000u) u = 0u;
         return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);          // 16-bit key, larger logit = larger key
     }
-    const uint32_t u = __float_as_uint(reinterpret_cast<const float*>(logits)[idx]);
+    uint32_t u = __float_as_uint(reinterpret_cast<const float*>(logits)[idx]);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

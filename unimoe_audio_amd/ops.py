@@ -622,7 +622,8 @@ def transpose(src: torch.Tensor) -> torch.Tensor:
 
 
 def swiglu_bwd(dh: torch.Tensor, gu: torch.Tensor, I: int, dgu: torch.Tensor, *, total_rows: Optional[torch.Tensor], max_rows: int):
-    L.check(L.lib().umoe_swiglu_bwd(_p(dh), dh.stride(0), _p(gu), gu.stride(0), I, _p(total_rows), max_rows, _p(dgu), dgu.stride(0),
+    """dh [rows][I], gu / dgu [rows][2I] may be column views of wider buffers (row strides that are multiples of 8)."""
+    L.check(L.lib().umoe_swiglu_bwd(_pv(dh), dh.stride(0), _pv(gu), gu.stride(0), I, _p(total_rows), max_rows, _pv(dgu), dgu.stride(0),
                                     _stream()), "umoe_swiglu_bwd")
     return dgu
 
