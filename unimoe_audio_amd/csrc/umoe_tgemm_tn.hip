@@ -320,7 +320,10 @@ __global__ __launch_bounds__(512, 2) void tgemm_nn_kernel(const umoe_tgemm_args 
         tinc[q] = tdel[q] ? 64 : 0;
         winc[q] = wdel[q] ? wstep : 0;
         tptr[q] = zero + tdel[q] + AH * tinc[q];
-        wptr[q] = zero + wdel[q] + AH * winc[q];          // (re-based at the switch to w2, below)
+        // the steady loop starts at tile AH (the prologue stages tiles 0..AH-1).  sw >= AH: it starts in w and run_w re-bases the pointer
+        // when it reaches tile sw; sw < AH (k_w1 < 32 AH): the prologue already crossed into w2 and the loop never meets tile sw, so it
+        // starts AH - sw tiles into w2
+        wptr[q] = sw < AH ? zero + wdel2[q] + (AH - sw) * winc[q] : zero + wdel[q] + AH * winc[q];
     }
     auto run_w = [&](const int tile, const int slot_off) {
         if (tile == sw) {
