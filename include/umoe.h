@@ -191,7 +191,10 @@ typedef struct {
     int prologue, epilogue;
     int nt;                   /* n-blocks per workgroup: 0 = auto, else 1/2/4/5/6/8, SwiGLU also 14 (tuning knob) */
     int waves;                /* waves per workgroup: 0 = auto, 4, 8 (8 only with nt = 8; tuning knob) */
-    int ksplit;               /* >1: K split over workgroups; needs UMOE_EPI_F32_RAW: slab s at out + s*part_stride */
+    int ksplit;               /* >1 (<= 4): K split over workgroups; needs UMOE_EPI_F32_RAW: slab s at out + s*part_stride holds the
+                               * product over k-steps [KB*s/ksplit, KB*(s+1)/ksplit) of every K quarter (KB = K/32; a slice of no
+                               * steps stores exact zeros).  A group's bias is added in slab 0 ONLY, so the sum of the slabs is
+                               * acc + bias */
     long part_stride;         /* elements between fp32 partial slabs */
     const umoe_group_t* groups_host; /* optional HOST copy of `groups`: with num_groups <= UMOE_GROUPS_INLINE the
                                * descriptors travel in the kernel arguments (one dependent HBM round trip less per launch) */

@@ -112,13 +112,15 @@ def dev():
 
 class Stats(_Stats):
     """the dict holds error / bound ratios only; the "off" shares are kept apart in .shares"""
+    prefix = "GEMM FP64"
+
     def share(self, name, v):
         self.__dict__.setdefault("shares", {})
         self.shares[name] = max(self.shares.get(name, 0.0), float(v))
 
     def show(self, title):
         shares = self.__dict__.get("shares", {})
-        print(f"\nGEMM FP64 {title}: " + ", ".join(f"{k} {v:.3g}" for k, v in self.items()) +
+        print(f"\n{self.prefix} {title}: " + ", ".join(f"{k} {v:.3g}" for k, v in self.items()) +
               (" | off: " + ", ".join(f"{k} {v:.3g}" for k, v in shares.items()) if shares else ""))
 
 

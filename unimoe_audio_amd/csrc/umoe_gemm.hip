@@ -354,7 +354,9 @@ __device__ __forceinline__ void wstream_body(const umoe_gemm_args& p, const umoe
     const int hq = lane >> 4, mq = lane & 15;
     float4 bias_r[TPW];
     uint2 resid_r[TPW];
-    const bool bias_vec = g.bias && ((size_t)g.bias & 15) == 0;
+    // K-split partial slabs (F32_RAW) are summed by their reader: the bias belongs to slab 0 only
+    const float* const gbias = ks == 0 ? g.bias : nullptr;
+    const bool bias_vec = gbias && ((size_t)gbias & 15) == 0;
     if (EPI != UMOE_EPI_SWIGLU) {
         const long orow_q = (long)g.out_row_base + roff + row0 + mq;
 #pragma unroll
@@ -364,7 +366,7 @@ __device__ __forceinline__ void wstream_body(const umoe_gemm_args& p, const umoe
             bias_r[q] = make_float4(0.f, 0.f, 0.f, 0.f);
             resid_r[q] = make_uint2(0, 0);
             const bool live = t < NT && nb0 + t < g.n_blocks && row0 + mq < count && n + 3 < p.n_valid;
-            if (live && bias_vec) bias_r[q] = *reinterpret_cast<const float4*>(g.bias + n);
+            if (live && bias_vec) bias_r[q] = *reinterpret_cast<const float4*>(gbias + n);
             if (EPI == UMOE_EPI_BF16_RESID && live && (p.ldo & 3) == 0)
                 resid_r[q] = *reinterpret_cast<const uint2*>(p.resid + orow_q * p.ldo + n);
         }
@@ -465,7 +467,7 @@ __device__ __forceinline__ void wstream_body(const umoe_gemm_args& p, const umoe
         const float bq[4] = {bias_r[q].x, bias_r[q].y, bias_r[q].z, bias_r[q].w};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            v[j] = a4[j] + ((fast && (bias_vec || !g.bias)) ? bq[j] : ((g.bias && n + j < p.n_valid) ? g.bias[n + j] : 0.f));
+            v[j] = a4[j] + ((fast && (bias_vec || !gbias)) ? bq[j] : ((gbias && n + j < p.n_valid) ? gbias[n + j] : 0.f));
         if (EPI == UMOE_EPI_F32 || EPI == UMOE_EPI_F32_RAW) {
             float* o = reinterpret_cast<float*>(p.out) + (size_t)ks * p.part_stride + orow * p.ldo + n;
 #pragma unroll
@@ -615,6 +617,8 @@ int umoe_gemm_riders(const umoe_gemm_args* a, int kind, const umoe_rider2* r2, c
 }
 
 // 8 waves per workgroup when the staging tile leaves room for only one workgroup per CU (measured: +6 % on K=2752)
+// (use8, launch_gemm_nt, the SwiGLU switch of umoe_grouped_gemm and the BV predicate of launch_gemm are restated by kernel_of in
+//  tests/test_gpu_wstream_fp64.py, which asserts that its cases reach every instantiation: change the two together)
 static bool use8(const umoe_gemm_args* a, int nt) {
     if (a->waves) return a->waves == 8;
     return gemm_lds_bytes(a->max_k, nt, 4, a->ksplit > 1 ? a->ksplit : 1) > 80 * 1024;
