@@ -116,7 +116,7 @@ def main():
     ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
     ap.add_argument("--serve", action="store_true", help="with --requests: serve the list as a queue (UniMoEAudio.serve): --slots rows decode "
                                                          "together and a request is admitted as soon as a row is free; any number of requests")
-    ap.add_argument("--slots", type=int, default=8, help="rows of the serving batch (1..8)")
+    ap.add_argument("--slots", type=int, default=8, help="rows of the serving batch (1..32)")
     a = ap.parse_args()
     if a.requests:
         if a.serve and a.stream:

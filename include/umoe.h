@@ -214,6 +214,30 @@ typedef struct {
 int umoe_prefetch(const void* p, size_t bytes, int wgs, umoe_stream_t stream);
 int umoe_grouped_gemm(const umoe_gemm_args* a, umoe_stream_t stream);
 
+/* ------------------------------------------------------------------ wide decode GEMM (17..64 rows, every weight streamed once)
+ * Y[tile t][16, N(g)] = epilogue(A[tile t][16, K(g)] * W_g^T) for tiles = ceil(rows / 16) in {2, 3, 4}: one pass over the WP16 weights of
+ * every group serves all row tiles (umoe_grouped_gemm re-reads a weight per 16-row tile).  The activations come as operand-order tiles
+ * (umoe_pack_rows; WP16 of a [16][K] matrix, tile t of group g at host_b[g] + t * 16 * K(g), pad rows zero).  The K split over the
+ * `waves` waves of a workgroup and the reduction order are those of the 16-row kernel with `u`-step chunks, so a (row, feature) product
+ * is bit-identical to the one umoe_grouped_gemm computes for a 16-row tile with the same (waves, u).  One (epilogue, waves, u) triple per
+ * GEMM of the decode step; anything else is refused:
+ *   UMOE_EPI_BF16 (+ host_bias), 4, 16      QKV          UMOE_EPI_BF16_RESID (+ host_resid), 4, 16    o_proj
+ *   UMOE_EPI_SWIGLU, 8, 1                   gate/up      UMOE_EPI_BF16, 8, 2                          down
+ *   UMOE_EPI_F32, 4, 16 | 8 | 2             codec head (the 16-row launch's split by block count: < 512, < 1024, more)
+ * host_* are HOST arrays of num_groups (<= 12) entries; groups may differ in n_blocks and K.  Row-major outputs: host_out[g] is
+ * [rows][ldo] (bf16, fp32 for UMOE_EPI_F32), columns >= min(n_valid, 16 n_blocks(g)) and pad rows are not stored, ldo % 4 == 0.  UMOE_EPI_SWIGLU: host_out[g]
+ * receives the tiles of silu(g) * u in operand order, [tiles][16 * I(g)], I = 8 * n_blocks (n_blocks % 4 == 0), pad rows included (zero
+ * rows in, zero rows out): the input of the down projection.  host_bias / host_resid may be NULL, or hold NULL entries (bias).  Weights, input tiles, outputs and
+ * residuals are 16-byte aligned. */
+int umoe_gemm_wide(const uint16_t* const* host_w, const int* host_n_blocks, const int* host_k, int num_groups, int rows,
+                   const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid, const float* const* host_bias,
+                   const uint16_t* const* host_resid, int epilogue, int waves, int u, umoe_stream_t stream);
+/* rows [rows][lda] (row-major, the first k columns) -> operand-order tiles for umoe_gemm_wide: packed holds ceil(rows / 16) * 16 * k
+ * elements, pad rows of the last tile are written as zeros and their source is not read.  norm_w != NULL (k 2048 / 4096): RMSNorm in
+ * front, values bit-identical to umoe_router_fwd(norm_only).  x, packed and norm_w are 16-byte aligned, lda % 8 == 0. */
+int umoe_pack_rows(const uint16_t* x, int lda, int rows, int k, const uint16_t* norm_w, float rms_eps, uint16_t* packed,
+                   umoe_stream_t stream);
+
 /* ------------------------------------------------------------------ tiled MFMA GEMM (prefill / training shapes)
  * Y[rows(g), N(g)] = epilogue( A[rows(g), K] * W_g^T ) with W_g ROW-MAJOR [N][K] bf16 (the reference's nn.Linear layout,
  * core.py:21-28,39-46; no packing: training updates these tensors every step).  Compute-bound counterpart of

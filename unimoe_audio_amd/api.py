@@ -369,14 +369,14 @@ class UniMoEAudio:
               max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None):
         """Continuous batching: a generator that takes SpeechRequest / MusicRequest objects from any iterable (read lazily) and yields
         (index, wav path) as each request ends -- index = the request's position in `requests`, the file is
-        `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows decode together;
-        a request is admitted into a row as soon as one is free (first in, first out, checked every `poll_every` steps), while the other
+        `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows (1..32) decode together,
+        above 8 in the wide decode step (every weight streamed once for all rows); a request is admitted into a row as soon as one is free (first in, first out, checked every `poll_every` steps), while the other
         rows keep decoding (DecodeEngine.admit, unimoe_audio_amd/serve.py).  Each request's prompt pair is built as generate_batch builds it
         and keeps its own length.  The engine is sized once: max_prompt_tokens per prompt, max_audio_seconds per request; a request beyond
         either is refused when its turn comes.  Not for expert-parallel engines, video prompts or streamed chunks."""
-        from .serve import MAX_SLOTS, Scheduler
-        if not 1 <= slots <= MAX_SLOTS:
-            raise ValueError(f"serve: slots must be 1..{MAX_SLOTS} (got {slots})")
+        from .serve import MAX_SLOTS_WIDE, Scheduler
+        if not 1 <= slots <= MAX_SLOTS_WIDE:
+            raise ValueError(f"serve: slots must be 1..{MAX_SLOTS_WIDE} (got {slots})")
         cfg = self.model.config
         eng = self.model.engine(slots, int(max_prompt_tokens), 50 * int(max_audio_seconds), expert_weights=expert_weights)
         eng.start_serving(int(max_prompt_tokens))
@@ -419,7 +419,7 @@ class UniMoEAudio:
                 codes, length = eng.take(row)
                 return self.held.pop(row), codes, length
 
-        sched = Scheduler(Rows(), slots, poll_every)
+        sched = Scheduler(Rows(), slots, poll_every, max_slots=MAX_SLOTS_WIDE)
         self.served_rows = {}                              # request index -> the row it decoded in (of the last / the running serve())
         for index, (r, codes, length) in sched.run(requests):
             self.served_rows.update({i: row for i, row, _ in sched.admitted})

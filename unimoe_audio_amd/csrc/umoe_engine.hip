@@ -117,6 +117,10 @@ struct umoe_engine {
     uint32_t* ep_words = nullptr;         // [0] decode steps taken (epoch base), [1] sticky error word; own allocation: survives workspace growth
     uint16_t* xg = nullptr;               // RCCL mode: [ep][rows][D] normalised rows of every rank (tile ep_rank is written locally)
     uint16_t *xgp = nullptr, *hpk = nullptr;   // peer modes: operand-order tiles (see carve)
+    // wide decode (17..64 rows on one GPU, umoe_gemm_wide.hip): operand-order tiles of the row-major GEMM inputs and of silu(g)*u
+    uint16_t *wide_in = nullptr, *wide_h = nullptr;
+    int row_tiles = 1;                    // 16-row tiles per weight pass of the last decode step (umoe_engine_info "row_tiles")
+    bool in_decode_step = false;          // set while enqueue_step runs: a prefill of one-token prompts has n_tok == rows too and is no decode step
     // the MoE half of an expert-parallel decode layer as ONE launch with the exchange inside (umoe_moe_ep.hip); prepared at connect time
     bool ep_flat = true;                  // UMOE_EP_FLAT=0: the launch-per-kernel exchange below (also taken when the shape has no plan)
     bool epf_ready = false;
@@ -150,6 +154,12 @@ static size_t carve(umoe_engine* e, int n_tok, char* base) {
     // peer modes: 16-row tiles in MFMA operand order -- the gathered rows [ep][16*D] and silu(g)*u of every (local expert, rank) [n_real][16*I]
     e->xgp = k.take<uint16_t>(c.ep_size > 1 ? (size_t)c.ep_size * 16 * D : 0);
     e->hpk = k.take<uint16_t>(c.ep_size > 1 ? (size_t)c.n_real * 16 * c.inter_dyn : 0);
+    // wide decode: [tiles][16 * max(D, HD)] for hin / attn_out / the post-attention norm rows, [G][tiles][16 * Imax] for silu(g)*u.
+    // Sized by the engine's rows, not by n_tok.  Like every buffer carved here they move when the workspace grows: umoe_engine_reserve is what
+    // keeps them (and a captured step graph) fixed across admissions
+    const int wt = (c.ep_size == 1 && c.rows > 16 && c.rows <= 64) ? ceil_div(c.rows, 16) : 0;
+    e->wide_in = k.take<uint16_t>((size_t)wt * 16 * (D > HD ? D : HD));
+    e->wide_h = k.take<uint16_t>((size_t)wt * 16 * Imax * G);
     e->part_o = k.take<float>((size_t)n_tok * c.heads * splits * c.head_dim);
     e->part_ml = k.take<float>((size_t)n_tok * c.heads * splits * 2);
     e->logits = k.take<float>((size_t)c.rows * c.codec_channels * c.codec_vocab);
@@ -200,6 +210,31 @@ static bool dense_mode(const umoe_engine* e, int n_tok) {
     return n_tok == e->c.rows && n_tok <= 16 && n_tok >= e->dense_min_rows;
 }
 
+// UMOE_WIDE_DECODE=0: decode steps of more than 16 rows take the ragged path (router + dispatch tables, a weight pass per 16 rows); =1: the
+// wide form at every size its shapes allow; unset: the wide form at the sizes where it was MEASURED faster than the ragged path of the same
+// process by more than the run-to-run spread (profiles/wide_decode.json).  Read per enqueue like UMOE_FLAT_MOE.
+static bool wide_measured_faster(int rows) {
+    // measured (ms/step ragged | wide, 36 layers): batch 9 4.554 | 4.553 and 12 4.625 | 4.619 inside the spread -> ragged; 16 5.072 | 4.661,
+    // 24 6.099 | 5.544, 32 8.122 | 5.929 -> wide.  Between the measured sizes only what the figures bound: 4 tiles (batch 25..32) cost at most
+    // the 5.929 of 32 and the ragged path at least the 6.099 of 24; batch 13..15 and 17..23 have no such bound and stay ragged
+    return rows == 32 || (rows >= 48 && rows <= 64);
+}
+static bool wide_on(int rows) {
+    const char* v = getenv("UMOE_WIDE_DECODE");
+    if (!v) return wide_measured_faster(rows);
+    return atoi(v) != 0;
+}
+// A decode step (enqueue_step: T == 1; never a prefill, whatever its token count) of 17..64 rows (batch 9..32) in the dense layout with every weight streamed ONCE for all row tiles (umoe_gemm_wide.hip): QKV,
+// o_proj, gate/up, down and the codec head.  One GPU, bf16 weights, the router shapes of the 16-row step; an admission prefill is a prefill.
+// Takes precedence over the tiled kernels at 64 rows.  fp8 engines and expert-parallel engines never take it (fp8 above 8 requests: the
+// ragged bf16 path, as before).
+static bool wide_mode(const umoe_engine* e, int n_tok) {
+    const umoe_engine_cfg& c = e->c;
+    return e->in_decode_step && e->adm_row0 < 0 && n_tok == c.rows && n_tok > 16 && n_tok <= 64 && c.ep_size == 1 && !e->fp8 && c.n_dyn == 9 &&
+           c.n_fix == 2 && c.hidden == 2048 && c.n_real + c.n_fix <= 12 && wide_on(n_tok);
+}
+
+// (the wide form reads no group table: its launches take the layers' weight pointers; the table built here serves UMOE_WIDE_DECODE=0)
 static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
     if (e->groups_for_tok == n_tok) return 0;
     const umoe_engine_cfg& c = e->c;
@@ -785,6 +820,7 @@ enum MoeForm {
     MOE_FLAT,      // dense decode, ONE launch: router riders, RMSNorm, gate/up and down, one workgroup per CU (umoe_moe_flat.hip)
     MOE_RIDERS,    // dense decode, launch per kernel: RMSNorm | gate/up with the router riding in it | down
     MOE_ROUTER,    // dense decode, launch per kernel: router | gate/up | down
+    MOE_WIDE,      // dense decode of 17..64 rows: router | RMSNorm + re-lay | gate/up | down, each weight streamed once for all row tiles
 };
 
 // UMOE_FLAT_MOE=0: never the flat expert launch.  Read per enqueue: the step graph captures the choice, A/B scripts toggle it on a live engine.
@@ -799,6 +835,7 @@ static int flat_wgs(const umoe_engine* e) { return e->n_cu < 256 ? e->n_cu : 256
 
 static MoeForm moe_form(const umoe_engine* e, const LayerDev& L, int n_tok) {
     const umoe_engine_cfg& c = e->c;
+    if (wide_mode(e, n_tok)) return MOE_WIDE;
     if (!dense_mode(e, n_tok)) return (L.has_rm && n_tok >= 64 && e->tiled_prefill && c.n_real + c.n_fix <= 12) ? MOE_TILED : MOE_RAGGED;
     // the shapes the router riders are written for (router4_body<9, 2>; dense_mode: <= 16 rows)
     if (!(e->fuse_router && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096))) return MOE_ROUTER;
@@ -855,6 +892,49 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------ wide decode launches
+// one group, row-major input `a` [n_tok][K] re-laid into wide_in, then one pass over `w`: (waves, u) = the K split of the 16-row launch
+static int wide_dense(umoe_engine* e, const uint16_t* a, int K, const uint16_t* w, int n_blocks, const float* bias, const uint16_t* resid, void* out,
+                      int ldo, int n_valid, int epilogue, int u, int n_tok, hipStream_t s) {
+    int rc;
+    if ((rc = umoe_pack_rows(a, K, n_tok, K, nullptr, 0.f, e->wide_in, s))) return rc;
+    PROF(K_DISPATCH);
+    const uint16_t* b = e->wide_in;
+    if ((rc = umoe_gemm_wide(&w, &n_blocks, &K, 1, n_tok, &b, &out, ldo, n_valid, bias ? &bias : nullptr, resid ? &resid : nullptr, epilogue, 4, u, s)))
+        return rc;
+    return 0;      // (the caller books the GEMM under its class)
+}
+
+// post-attention RMSNorm + re-lay, gate/up over all routed and shared experts, down: three launches, every expert computes every row
+static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_t s) {
+    const umoe_engine_cfg& c = e->c;
+    const int D = c.hidden, G = c.n_real + c.n_fix, Imax = c.inter_dyn > c.inter_shared ? c.inter_dyn : c.inter_shared;
+    const int tiles = ceil_div(n_tok, 16);
+    int rc;
+    if ((rc = umoe_pack_rows(e->x1, D, n_tok, D, L.w.post_norm, c.rms_eps, e->wide_in, s))) return rc;
+    PROF(K_DISPATCH);
+    const uint16_t *wgu[12], *wdn[12], *bx[12], *bh[12];
+    void *oh[12], *oy[12];
+    int nb_gu[12], nb_dn[12], k_gu[12], k_dn[12];
+    for (int x = 0; x < G; ++x) {
+        const bool sh = x >= c.n_real;
+        const int I = sh ? c.inter_shared : c.inter_dyn;
+        wgu[x] = sh ? L.sh_gu[x - c.n_real] : L.exp_gu[x];
+        wdn[x] = sh ? L.sh_dn[x - c.n_real] : L.exp_dn[x];
+        bx[x] = e->wide_in;
+        oh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;      // [tiles][16 * I] in operand order
+        bh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;
+        oy[x] = e->ybuf + (size_t)x * n_tok * D;                // dense layout: expert x owns rows [x * n_tok, (x + 1) * n_tok)
+        nb_gu[x] = 2 * I / 16; k_gu[x] = D;
+        nb_dn[x] = D / 16; k_dn[x] = I;
+    }
+    if ((rc = umoe_gemm_wide(wgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, nullptr, nullptr, UMOE_EPI_SWIGLU, 8, 1, s))) return rc;
+    PROF(K_GATEUP);
+    if ((rc = umoe_gemm_wide(wdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, nullptr, nullptr, UMOE_EPI_BF16, 8, 2, s))) return rc;
+    PROF(K_DOWN);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------ one layer
 static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStream_t s) {
     const umoe_engine_cfg& c = e->c;
@@ -874,8 +954,11 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     a.prologue = UMOE_PRO_PLAIN; a.epilogue = UMOE_EPI_BF16;
     PROF(-1);
     // many rows (prefill): the compute-bound tiled MFMA kernel on the row-major weights; decode: weight streaming
-    const bool tiled = L.has_rm && n_tok >= 64 && e->tiled_prefill;
-    if (tiled) {
+    const bool wide = wide_mode(e, n_tok);
+    const bool tiled = !wide && L.has_rm && n_tok >= 64 && e->tiled_prefill;
+    if (wide) {
+        rc = wide_dense(e, e->hin, D, L.w.qkv_w, QKV / 16, L.w.qkv_b, nullptr, e->qkv, QKV, QKV, UMOE_EPI_BF16, 16, n_tok, s);
+    } else if (tiled) {
         umoe_tgroup_t tg{};
         tg.w = L.w.rm_qkv; tg.bias = L.w.qkv_b; tg.static_count = n_tok; tg.n = QKV; tg.k = D; tg.ldw = D;
         umoe_tgemm_args ta{};
@@ -940,7 +1023,9 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     o.groups = g + 1; o.groups_host = gh + 1; o.num_groups = 1; o.max_rows = n_tok; o.max_n_blocks = D / 16; o.max_k = HD;
     o.a = e->attn_out; o.lda = HD; o.resid = e->x; o.out = e->x1; o.ldo = D; o.n_valid = D;
     o.prologue = UMOE_PRO_PLAIN; o.epilogue = UMOE_EPI_BF16_RESID;
-    if (tiled) {
+    if (wide) {
+        rc = wide_dense(e, e->attn_out, HD, L.w.o_w, D / 16, nullptr, e->x, e->x1, D, D, UMOE_EPI_BF16_RESID, 16, n_tok, s);
+    } else if (tiled) {
         umoe_tgroup_t tg{};
         tg.w = L.w.rm_o; tg.static_count = n_tok; tg.n = D; tg.k = HD; tg.ldw = HD;
         umoe_tgemm_args ta{};
@@ -957,7 +1042,11 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     if (e->ep_decode(n_tok)) return run_moe_ep(e, l, n_tok, s);
     // 5.-8. RMSNorm + router, experts                             model.py:240, core.py:246-291,406-416,344-351
     const MoeForm form = moe_form(e, L, n_tok);
-    const bool dense = form == MOE_FLAT || form == MOE_RIDERS || form == MOE_ROUTER;
+    const bool dense = form == MOE_FLAT || form == MOE_RIDERS || form == MOE_ROUTER || form == MOE_WIDE;
+    if (form != MOE_WIDE && n_tok == c.rows && n_tok > 16 && !adm) {     // a decode step the wide form did not take
+        e->expert_launch = 0;
+        e->row_tiles = 1;
+    }
     UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
     umoe_router_args ra{};
     ra.x = e->x1; ra.gate_w = L.w.gate_w; ra.norm_w = L.w.post_norm; ra.h_out = e->h2; ra.S = n_tok; ra.D = D;
@@ -1048,6 +1137,15 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             if ((rc = experts_two_launches(e, &gu, &dn, s))) return rc;
             e->expert_launch = 0;
             e->expert_fp8 = 0;
+            break;
+        case MOE_WIDE:
+            ra.h_out = nullptr;      // (the experts read the operand-order tiles of the RMSNorm + re-lay launch)
+            if ((rc = umoe_router_fwd(&ra, s))) return rc;      // all rows, no dispatch tables: the combine reads the mask
+            PROF(K_ROUTER);
+            if ((rc = experts_wide(e, L, n_tok, s))) return rc;
+            e->expert_launch = 4;
+            e->expert_fp8 = 0;
+            e->row_tiles = ceil_div(n_tok, 16);
             break;
     }
     // 9. combine + residual -> next layer input                   core.py:488,342-351; model.py:242
@@ -1212,6 +1310,11 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     const umoe_engine_cfg& c = e->c;
     const int B = c.rows / 2, C = c.codec_channels, V = c.codec_vocab;
     int rc;
+    struct StepFlag {
+        bool& f;
+        explicit StepFlag(bool& b) : f(b) { f = true; }
+        ~StepFlag() { f = false; }
+    } in_step(e->in_decode_step);
     PROF(-1);
     step_prep_kernel<<<dim3((unsigned)c.rows), 64, 0, s>>>(io->tokens, io->state, B, C, c.Tmax, e->T_prompt, c.Lmax,
                                                            e->valid_count, e->tok_in, e->pos3, e->kv_pos, e->q_pos0, e->ep_words,
@@ -1240,7 +1343,13 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     h.max_n_blocks = ceil_div(C * V, 16); h.max_k = c.hidden; h.a = e->hin; h.lda = c.hidden;   // hin = final norm(x)
     h.out = e->logits; h.ldo = C * V; h.n_valid = C * V;
     h.prologue = UMOE_PRO_PLAIN; h.epilogue = UMOE_EPI_F32;
-    if ((rc = umoe_grouped_gemm(&h, s))) return rc;
+    if (wide_mode(e, c.rows)) {
+        // the K split the 16-row head launch takes (auto_nt / launch_gemm_nt in umoe_gemm.hip at hidden 2048: blocks per workgroup 8 / 2 / 1)
+        const int nb = ceil_div(C * V, 16), u = nb >= 1024 ? 2 : (nb >= 512 ? 8 : 16);
+        if ((rc = wide_dense(e, e->hin, c.hidden, e->codec_head_w, nb, nullptr, nullptr, e->logits, C * V, C * V, UMOE_EPI_F32, u, c.rows, s))) return rc;
+    } else {
+        if ((rc = umoe_grouped_gemm(&h, s))) return rc;
+    }
     PROF(K_HEAD);
     umoe_sample_args sa{};
     sa.logits = e->logits; sa.B = B; sa.C = C; sa.V = V; sa.cfg_scale = io->cfg_scale; sa.temperature = io->temperature;
@@ -1471,6 +1580,7 @@ extern "C" int umoe_engine_replay(umoe_engine* e, umoe_stream_t stream) {
 extern "C" int umoe_engine_info(umoe_engine* e, const char* key) {
     if (!e || !key) return -1;
     if (!strcmp(key, "expert_launch")) return e->expert_launch;
+    if (!strcmp(key, "row_tiles")) return e->expert_launch == 4 ? e->row_tiles : 1;
     if (!strcmp(key, "expert_fp8")) return e->expert_fp8;
     if (!strcmp(key, "n_cu")) return e->n_cu;
     return -1;

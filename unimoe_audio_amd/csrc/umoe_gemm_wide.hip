@@ -1,0 +1,341 @@
+// Weight-streaming GEMM for a decode step of 17 to 64 rows on ONE GPU: 2, 3 or 4 sixteen-row tiles per pass over a weight.
+//
+//   Y[tile t][16, N(g)] = epilogue( A[tile t][16, K(g)] * W_g^T )   tile t = rows [16 t, min(16 t + 16, rows)), weights read ONCE
+//
+// Design (MI355X / gfx950), relative to wstream_gemm (umoe_gemm.hip) and wstream_mt (umoe_gemm_mt.hip):
+//  * the WP16 weight stream goes straight into VGPRs (non-temporal 1 KiB wave-loads); there is NO grid dimension over row tiles, every
+//    workgroup serves all tiles of the launch with the weight fragments it holds;
+//  * the activation tiles arrive in MFMA operand order (pack_rows below re-lays row-major rows, the SwiGLU epilogue writes operand
+//    order for the down projection), so a B fragment is one contiguous 1 KiB wave-load from L2: 64 rows at K 2752 are 344 KiB, more
+//    than the LDS holds, and no staging pass or barrier stands in front of the stream;
+//  * the K split over the WV waves of a workgroup and the fixed-order LDS reduction (wave 0 first) are those of
+//    wstream_gemm<.., U, .., WV>: a wave runs its k-steps in ascending order into one accumulator per (tile, block), so every
+//    (row, feature) product is BIT-IDENTICAL to the one the 16-row launch with the same (WV, U) computes (tests/test_gpu_wide_gemm.py);
+//  * at most 16 (tile, block) accumulators per wave.  Three tiles run the four-tile instantiation: the fourth tile re-reads the third
+//    one's fragments from L2 and is never stored (an MT = 3 loop would need block counts per workgroup of its own);
+//  * every guard around an MFMA is a scalar branch (wave and slice bounds pinned into SGPRs; tests/test_wide_cpu.py scans the assembly);
+//  * groups carry their own n_blocks and K (routed and shared experts in one launch): the grid is a box over the widest group.
+// Pad rows of a partial last tile are zero on input (pack_rows, and silu(0) * 0 = 0 behind it) and are never stored row-major.
+// Roofline: HBM.  Algorithmic bytes per launch = sum over groups of N*K*2.
+#include "umoe_common.h"
+#include <string.h>
+
+#define UMOE_WIDE_MAXG 12
+struct wide_args {
+    const uint16_t* w[UMOE_WIDE_MAXG];      // WP16 weights of group g (gate/up blocks interleaved for SwiGLU)
+    const uint16_t* b[UMOE_WIDE_MAXG];      // operand-order tiles of group g: tile t at b[g] + t * 16 * k[g]
+    void* out[UMOE_WIDE_MAXG];              // row-major [rows][ldo] (bf16 / fp32), or operand-order tiles [tiles][16 * I] (SwiGLU)
+    const float* bias[UMOE_WIDE_MAXG];      // optional [N] fp32
+    const uint16_t* resid[UMOE_WIDE_MAXG];  // UMOE_EPI_BF16_RESID: [rows][ldo]
+    int n_blocks[UMOE_WIDE_MAXG], k[UMOE_WIDE_MAXG];
+    int num_groups, rows, tiles, ldo, n_valid;
+};
+
+template <int NT, int MT, int U, int WV, int EPI, int RW, int RB, bool WREFILL>
+__global__ __launch_bounds__(WV * 64, 1) void wstream_wide(const wide_args p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const int g = blockIdx.z, nb0 = blockIdx.x * NT;
+    const int n_blocks = p.n_blocks[g];
+    if (nb0 >= n_blocks) return;
+    const int K = p.k[g], KB = K >> 5;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: every guard around an MFMA must be a scalar branch
+    // K split of wstream_gemm<.., U, .., WV>: whole U-step chunks per wave when they divide, single steps otherwise
+    int i0, i1;
+    if (KB % U == 0) {
+        const int units = KB / U;
+        i0 = U * ((units * wave) / WV);
+        i1 = U * ((units * (wave + 1)) / WV);
+    } else {
+        i0 = (KB * wave) / WV;
+        i1 = (KB * (wave + 1)) / WV;
+    }
+    i0 = __builtin_amdgcn_readfirstlane(i0);
+    i1 = __builtin_amdgcn_readfirstlane(i1);
+    const u32x4_t* wp[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int nb = min(nb0 + t, n_blocks - 1);   // tail blocks re-read the last one; never stored
+        wp[t] = reinterpret_cast<const u32x4_t*>(p.w[g]) + ((size_t)nb * KB) * 64 + lane;
+    }
+    const u32x4_t* bp[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int mm = min(m, p.tiles - 1);          // (three tiles: the fourth re-reads the third; never stored)
+        bp[m] = reinterpret_cast<const u32x4_t*>(p.b[g]) + ((size_t)mm * KB) * 64 + lane;
+    }
+    f32x4_t acc[MT][NT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[m][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // register rings as in wstream_mt: RW k-steps of weights (HBM) and RB k-steps of fragments (L2) in flight, the fragment refill
+    // issued before the weight refill; every load is unconditional with its index clamped into the wave's slice (a wave without
+    // k-steps reads step 0 and runs no MFMA)
+    u32x4_t wr[RW][NT], br[RB][MT];
+    auto load_w = [&](u32x4_t (&d)[NT], int ii) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) d[t] = __builtin_nontemporal_load(wp[t] + (size_t)ii * 64);
+    };
+    auto load_b = [&](u32x4_t (&d)[MT], int ii) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) d[m] = bp[m][(size_t)ii * 64];
+    };
+    const int il = max(i1 - 1, 0);
+#pragma unroll
+    for (int r = 0; r < RB; ++r) load_b(br[r], min(i0 + r, il));
+#pragma unroll
+    for (int r = 0; r < RW; ++r) load_w(wr[r], min(i0 + r, il));
+    __builtin_amdgcn_sched_barrier(0);
+    for (int base = i0; base < i1; base += RW) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            const int ii = base + r;
+            if (ii < i1) {
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, br[r % RB][m]);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wr[r][t]), bfrag, acc[m][t], 0, 0, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            load_b(br[r % RB], min(ii + RB, il));
+            if constexpr (WREFILL) load_w(wr[r], min(ii + RW, il));   // (WREFILL false: the whole K slice of a wave fits the ring)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // ---- fixed-order cross-wave reduction (wave 0 first, as in wstream_gemm) --------------------------------------------
+    f32x4_t* red = reinterpret_cast<f32x4_t*>(smem);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) red[((wave * MT + m) * NT + t) * 64 + lane] = acc[m][t];
+    __syncthreads();
+    auto reduced = [&](int m, int t) -> f32x4_t {
+        f32x4_t s = red[(m * NT + t) * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < WV; ++w) {
+            const f32x4_t v = red[((w * MT + m) * NT + t) * 64 + lane];
+            s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
+        }
+        return s;
+    };
+    const int h = lane >> 4, mm = lane & 15;   // lane (h, mm) owns features 4h..4h+3 of token row mm of every tile
+    if constexpr (EPI == UMOE_EPI_SWIGLU) {
+        const int I = n_blocks * 8, Q = I >> 2;             // intermediate size and its K-quarter for the down projection
+        for (int q = wave; q < MT * (NT / 2); q += WV) {
+            const int m = q / (NT / 2), pq = q % (NT / 2);
+            if (m >= p.tiles || nb0 + 2 * pq >= n_blocks) continue;
+            const f32x4_t ga = reduced(m, 2 * pq), ua = reduced(m, 2 * pq + 1);
+            uint16_t y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gt = rbf(ga[j]);
+                const float up = rbf(ua[j]);
+                const float si = rbf(gt / (1.0f + expf(-gt)));
+                y[j] = f2bf(si * up);
+            }
+            // feature f..f+3 of row mm -> operand order of the [16][I] tile: fragment (k-step i, lane = quarter*16 + row), element j
+            // (pad rows of the last tile are written too: zero rows in give silu(0) * 0 = 0, the down projection reads zeros)
+            const int f = (nb0 / 2 + pq) * 16 + 4 * h;
+            const int qq = f / Q, r = f % Q;
+            uint16_t* o = reinterpret_cast<uint16_t*>(p.out[g]) + (size_t)m * 16 * I + ((size_t)(r >> 3) * 64 + qq * 16 + mm) * 8 + (r & 7);
+            *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16));
+        }
+        return;
+    } else {
+        const float* gbias = p.bias[g];
+        for (int q = wave; q < MT * NT; q += WV) {
+            const int m = q / NT, t = q % NT;
+            const int row = m * 16 + mm;
+            if (m >= p.tiles || nb0 + t >= n_blocks || row >= p.rows) continue;      // pad rows are never stored
+            const f32x4_t a4 = reduced(m, t);
+            const int n = (nb0 + t) * 16 + 4 * h;
+            if (n >= p.n_valid) continue;
+            const bool fast = n + 3 < p.n_valid;
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = a4[j] + ((gbias && n + j < p.n_valid) ? gbias[n + j] : 0.f);   // (the 16-row kernel adds 0.f too)
+            const size_t off = (size_t)row * p.ldo + n;
+            if constexpr (EPI == UMOE_EPI_F32) {
+                float* o = reinterpret_cast<float*>(p.out[g]) + off;
+                if (fast) {
+                    *reinterpret_cast<float4*>(o) = make_float4(rbf(v[0]), rbf(v[1]), rbf(v[2]), rbf(v[3]));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (n + j < p.n_valid) o[j] = rbf(v[j]);
+                }
+            } else {
+                uint16_t* o = reinterpret_cast<uint16_t*>(p.out[g]) + off;
+                uint16_t y[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float x = rbf(v[j]);
+                    if (EPI == UMOE_EPI_BF16_RESID && n + j < p.n_valid) x = bf2f(p.resid[g][off + j]) + x;
+                    y[j] = f2bf(x);
+                }
+                if (fast) {
+                    *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (n + j < p.n_valid) o[j] = y[j];
+                }
+            }
+        }
+    }
+}
+
+template <int NT, int MT, int U, int WV, int EPI, int RW, int RB, bool WREFILL>
+static int launch_wide_v(const wide_args& a, int max_nb, hipStream_t s) {
+    const size_t lds = (size_t)WV * MT * NT * 64 * 16;
+    static bool configured = false;
+    if (!configured) {
+        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wstream_wide<NT, MT, U, WV, EPI, RW, RB, WREFILL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        configured = true;
+    }
+    const dim3 grid((unsigned)ceil_div(max_nb, NT), 1, (unsigned)a.num_groups);
+    wstream_wide<NT, MT, U, WV, EPI, RW, RB, WREFILL><<<grid, WV * 64, lds, s>>>(a);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int NT, int MT, int U, int WV, int EPI, int RW, int RB>
+static int launch_wide(const wide_args& a, hipStream_t s) {
+    // k-steps of the longest wave slice over the groups: no weight refill when the ring holds them all
+    int longest = 0, max_nb = 0;
+    for (int g = 0; g < a.num_groups; ++g) {
+        const int KB = a.k[g] >> 5;
+        const int l = (KB % U == 0) ? U * ceil_div(KB / U, WV) : ceil_div(KB, WV);
+        longest = l > longest ? l : longest;
+        max_nb = a.n_blocks[g] > max_nb ? a.n_blocks[g] : max_nb;
+    }
+    if (longest <= RW) return launch_wide_v<NT, MT, U, WV, EPI, RW, RB, false>(a, max_nb, s);
+    return launch_wide_v<NT, MT, U, WV, EPI, RW, RB, true>(a, max_nb, s);
+}
+
+// blocks per workgroup (NT) by epilogue and tiles: the launcher's choice, restated by tests/test_gpu_wide_gemm.py
+extern "C" int umoe_gemm_wide(const uint16_t* const* host_w, const int* host_n_blocks, const int* host_k, int num_groups, int rows,
+                              const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid, const float* const* host_bias,
+                              const uint16_t* const* host_resid, int epilogue, int waves, int u, umoe_stream_t stream) {
+    UMOE_REQUIRE(host_w && host_n_blocks && host_k && host_b && host_out, "umoe_gemm_wide: null argument");
+    UMOE_REQUIRE(num_groups >= 1 && num_groups <= UMOE_WIDE_MAXG, "umoe_gemm_wide: 1..%d groups (got %d)", UMOE_WIDE_MAXG, num_groups);
+    UMOE_REQUIRE(rows > 16 && rows <= 64, "umoe_gemm_wide: 17..64 rows (got %d): 16 rows and fewer are umoe_grouped_gemm's", rows);
+    wide_args a;
+    memset(&a, 0, sizeof(a));
+    a.num_groups = num_groups; a.rows = rows; a.tiles = ceil_div(rows, 16); a.ldo = ldo; a.n_valid = n_valid;
+    const bool swiglu = epilogue == UMOE_EPI_SWIGLU;
+    for (int g = 0; g < num_groups; ++g) {
+        a.w[g] = host_w[g]; a.b[g] = host_b[g]; a.out[g] = host_out[g];
+        a.bias[g] = host_bias ? host_bias[g] : nullptr;
+        a.resid[g] = host_resid ? host_resid[g] : nullptr;
+        a.n_blocks[g] = host_n_blocks[g]; a.k[g] = host_k[g];
+        UMOE_REQUIRE(a.w[g] && a.b[g] && a.out[g], "umoe_gemm_wide: group %d lacks weights, input tiles or an output", g);
+        UMOE_REQUIRE((((uintptr_t)a.w[g] | (uintptr_t)a.b[g] | (uintptr_t)a.out[g] | (uintptr_t)a.resid[g]) & 15) == 0 && ((uintptr_t)a.bias[g] & 3) == 0,
+                     "umoe_gemm_wide: group %d: weights, input tiles, output and residual must be 16-byte aligned (16-byte vector accesses)", g);
+        UMOE_REQUIRE(a.k[g] > 0 && a.k[g] % 32 == 0 && a.n_blocks[g] > 0, "umoe_gemm_wide: group %d: K %% 32 == 0, n_blocks > 0 (K=%d n_blocks=%d)", g,
+                     a.k[g], a.n_blocks[g]);
+        UMOE_REQUIRE(!swiglu || a.n_blocks[g] % 4 == 0, "umoe_gemm_wide: SwiGLU needs gate/up block pairs and I %% 32 == 0 (group %d: %d blocks)", g,
+                     a.n_blocks[g]);
+        UMOE_REQUIRE(epilogue != UMOE_EPI_BF16_RESID || a.resid[g], "umoe_gemm_wide: residual epilogue needs resid (group %d)", g);
+        UMOE_REQUIRE(swiglu || (ldo % 4 == 0 && n_valid > 0 && n_valid <= ldo),
+                     "umoe_gemm_wide: row-major outputs need ldo %% 4 == 0 and 0 < n_valid <= ldo (ldo=%d n_valid=%d)", ldo, n_valid);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool two = a.tiles == 2;
+    // one instantiation per (epilogue, WV, U) of the 16-row decode step (launch_gemm_nt / the SwiGLU switch of umoe_grouped_gemm)
+    if (waves == 4 && u == 16 && epilogue == UMOE_EPI_BF16)         // QKV (+ bias)
+        return two ? launch_wide<1, 2, 16, 4, UMOE_EPI_BF16, 16, 4>(a, s) : launch_wide<1, 4, 16, 4, UMOE_EPI_BF16, 16, 4>(a, s);
+    if (waves == 4 && u == 16 && epilogue == UMOE_EPI_BF16_RESID)   // o_proj (+ residual)
+        return two ? launch_wide<1, 2, 16, 4, UMOE_EPI_BF16_RESID, 16, 4>(a, s) : launch_wide<1, 4, 16, 4, UMOE_EPI_BF16_RESID, 16, 4>(a, s);
+    if (waves == 4 && u == 8 && epilogue == UMOE_EPI_F32)           // codec head (512..1023 blocks in the 16-row launch: 2 per workgroup)
+        return two ? launch_wide<2, 2, 8, 4, UMOE_EPI_F32, 8, 4>(a, s) : launch_wide<2, 4, 8, 4, UMOE_EPI_F32, 8, 4>(a, s);
+    if (waves == 4 && u == 16 && epilogue == UMOE_EPI_F32)          // a small head (< 512 blocks: 1 per workgroup there)
+        return two ? launch_wide<1, 2, 16, 4, UMOE_EPI_F32, 16, 4>(a, s) : launch_wide<1, 4, 16, 4, UMOE_EPI_F32, 16, 4>(a, s);
+    if (waves == 4 && u == 2 && epilogue == UMOE_EPI_F32)           // a large head (>= 1024 blocks: 8 per workgroup there)
+        return two ? launch_wide<2, 2, 2, 4, UMOE_EPI_F32, 8, 4>(a, s) : launch_wide<2, 4, 2, 4, UMOE_EPI_F32, 8, 4>(a, s);
+    if (waves == 8 && u == 1 && swiglu)                             // gate/up
+        return two ? launch_wide<8, 2, 1, 8, UMOE_EPI_SWIGLU, 4, 2>(a, s) : launch_wide<4, 4, 1, 8, UMOE_EPI_SWIGLU, 8, 2>(a, s);
+    if (waves == 8 && u == 2 && epilogue == UMOE_EPI_BF16)          // down
+        return two ? launch_wide<2, 2, 2, 8, UMOE_EPI_BF16, 8, 4>(a, s) : launch_wide<1, 4, 2, 8, UMOE_EPI_BF16, 8, 4>(a, s);
+    UMOE_REQUIRE(false,
+                 "umoe_gemm_wide: (epilogue, waves, u) must be one of the decode step's: (bf16 | bf16+resid, 4, 16), (fp32, 4, 16 | 8 | 2), (SwiGLU, 8, 1), "
+                 "(bf16, 8, 2) (got %d, %d, %d)",
+                 epilogue, waves, u);
+}
+
+// ------------------------------------------------------------------------------------ operand-order producers
+// Rows [rows][K] row-major -> WP16 tiles of [16][K] (include/umoe.h): tile t at packed + t * 16 * K, pad rows of the last tile ZERO (their
+// source is never read).  One workgroup of 256 threads per tile row.  NORM: the RMSNorm of router4_body (umoe_router_dev.h) in front,
+// the same arithmetic bit for bit -- thread (wave, lane) holds the 16-byte chunks (4 n + wave) * 64 + lane, sums their squares in element
+// order, xor-butterfly 32 .. 1, the four wave sums added in order, value = bf16(w * bf16(x * rs)).
+template <bool NORM>
+__global__ __launch_bounds__(256) void pack_rows_kernel(const uint16_t* __restrict__ x, int lda, int rows, int K, const uint16_t* __restrict__ norm_w,
+                                                        float rms_eps, uint16_t* __restrict__ packed) {
+    __shared__ float ss_part[4];
+    const int r = blockIdx.x, t = r >> 4, m = r & 15, tid = threadIdx.x;
+    const int KB = K >> 5;      // 16-byte chunks per K-quarter
+    uint16_t* dst = packed + (size_t)t * 16 * K;
+    auto chunk_dst = [&](int c) { return dst + ((size_t)(c % KB) * 64 + (c / KB) * 16 + m) * 8; };
+    if (r >= rows) {            // (uniform per workgroup)
+        for (int c = tid; c < 4 * KB; c += 256) st16(chunk_dst(c), make_uint4(0, 0, 0, 0));
+        return;
+    }
+    const uint16_t* xr = x + (size_t)r * lda;
+    if constexpr (!NORM) {
+        for (int c = tid; c < 4 * KB; c += 256) st16(chunk_dst(c), ld16(xr + c * 8));
+    } else {
+        const int lane = tid & 63, wave = tid >> 6;
+        const int nch = K >> 11;    // chunks per thread: 1 or 2
+        uint4 xv[2], nw[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+            if (n < nch) {
+                const int c = (n * 4 + wave) * 64 + lane;
+                xv[n] = ld16(xr + c * 8);
+                nw[n] = ld16(norm_w + c * 8);
+            }
+        float ss = 0.f;
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+            if (n < nch) {
+                float f[8];
+                unpack8(xv[n], f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+            }
+        ss = wave_sum(ss);
+        if (lane == 0) ss_part[wave] = ss;
+        __syncthreads();
+        ss = ((ss_part[0] + ss_part[1]) + ss_part[2]) + ss_part[3];
+        const float rs = rsqrtf(ss / (float)K + rms_eps);
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+            if (n < nch) {
+                const int c = (n * 4 + wave) * 64 + lane;
+                float f[8], w[8];
+                unpack8(xv[n], f);
+                unpack8(nw[n], w);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[j] = rbf(w[j] * rbf(f[j] * rs));
+                st16(chunk_dst(c), pack8(f));
+            }
+    }
+}
+
+extern "C" int umoe_pack_rows(const uint16_t* x, int lda, int rows, int k, const uint16_t* norm_w, float rms_eps, uint16_t* packed,
+                              umoe_stream_t stream) {
+    UMOE_REQUIRE(x && packed && rows > 0 && rows <= 65535 * 16 && k > 0 && k % 32 == 0 && lda >= k && lda % 8 == 0,
+                 "umoe_pack_rows: need rows > 0, K %% 32 == 0, lda >= K, lda %% 8 == 0 (rows=%d K=%d lda=%d)", rows, k, lda);
+    UMOE_REQUIRE((((uintptr_t)x | (uintptr_t)packed | (uintptr_t)norm_w) & 15) == 0, "umoe_pack_rows: x, packed and norm_w must be 16-byte aligned");
+    UMOE_REQUIRE(!norm_w || k == 2048 || k == 4096, "umoe_pack_rows: the RMSNorm form needs K 2048 or 4096 (got %d)", k);
+    const dim3 grid((unsigned)(ceil_div(rows, 16) * 16));
+    if (norm_w) pack_rows_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(x, lda, rows, k, norm_w, rms_eps, packed);
+    else pack_rows_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(x, lda, rows, k, nullptr, 0.f, packed);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}

@@ -871,8 +871,8 @@ class DecodeEngine:
         row.  admit() then puts requests into rows; step() decodes whatever rows are live."""
         self._refuse_clock("start_serving")
         B, Cc = self.batch, self.cfg.codec_channels
-        if B > 8:
-            raise L.UmoeError(f"start_serving: at most 8 rows (got {B})")
+        if B > 32:
+            raise L.UmoeError(f"start_serving: at most 32 rows (got {B})")
         if max_prompt < 1 or max_prompt + 2 > self.Lmax:
             raise L.UmoeError(f"start_serving: max_prompt {max_prompt} does not fit Lmax {self.Lmax}")
         L.check(L.lib().umoe_engine_reserve(self.h, 2 * int(max_prompt)), "umoe_engine_reserve")
@@ -979,8 +979,9 @@ class DecodeEngine:
 
     def info(self, key: str) -> int:
         """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 2 flat, 3 the one-launch
-        expert-parallel MoE half; 1 was the removed box-grid launch and is never returned), "n_cu", "expert_fp8" (1: the last dense decode
-        layer ran the fp8 flat launch)."""
+        expert-parallel MoE half, 4 the wide form of 17..64 rows; 1 was the removed box-grid launch and is never returned), "row_tiles"
+        (16-row tiles per weight pass of the wide form, 1 otherwise), "n_cu", "expert_fp8" (1: the last dense decode layer ran the fp8
+        flat launch)."""
         return int(L.lib().umoe_engine_info(self.h, key.encode()))
 
     def write_buffer(self, name: str, src: torch.Tensor, offset_bytes: int = 0) -> None:

@@ -252,6 +252,44 @@ def grouped_gemm(table: GroupTable, a: torch.Tensor, out: torch.Tensor, *, max_r
     return out
 
 
+def pack_rows(x: torch.Tensor, *, norm_w: Optional[torch.Tensor] = None, rms_eps: float = 1e-6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rows [S, K] bf16 (row-strided view allowed) -> operand-order tiles for gemm_wide, flat [ceil(S / 16) * 16 * K]; pad rows zero.
+    norm_w: RMSNorm in front (K 2048 / 4096), bit-identical to router_fwd(norm_only)."""
+    _bf(x)
+    S, K = x.shape
+    if out is None:
+        out = torch.empty(((S + 15) // 16) * 16 * K, dtype=torch.bfloat16, device=x.device)
+    assert out.numel() >= ((S + 15) // 16) * 16 * K
+    L.check(L.lib().umoe_pack_rows(_pv(x), x.stride(0), S, K, _p(norm_w), rms_eps, _p(out), _stream()), "umoe_pack_rows")
+    return out
+
+
+def gemm_wide(w: Sequence[torch.Tensor], n_blocks: Sequence[int], k: Sequence[int], rows: int, b: Sequence[torch.Tensor],
+              out: Sequence[torch.Tensor], *, epilogue: int, waves: int, u: int, bias: Optional[Sequence[Optional[torch.Tensor]]] = None,
+              resid: Optional[Sequence[torch.Tensor]] = None, n_valid: Optional[int] = None):
+    """umoe_gemm_wide: 17..64 rows as 2..4 operand-order tiles per group, every group's WP16 weights streamed once.  One list entry per
+    group; `out[g]` is a [rows, ldo] view (row-major epilogues) or the flat operand-order tile buffer (SwiGLU)."""
+    G = len(w)
+    assert G == len(n_blocks) == len(k) == len(b) == len(out) and G >= 1
+
+    def ptrs(ts, strided=False):
+        if ts is None:
+            return None
+        return (C.c_void_p * G)(*[None if t is None else (_pv(t) if strided else _p(t).value) for t in ts])
+
+    row_major = epilogue != EPI_SWIGLU
+    ldo = out[0].stride(0) if row_major else 0
+    if row_major:
+        assert all(o.dim() == 2 and o.stride(0) == ldo and o.shape[0] >= rows for o in out)
+        assert resid is None or all(r.dim() == 2 and r.stride(0) == ldo for r in resid)
+        if n_valid is None:
+            n_valid = out[0].shape[1]
+    L.check(L.lib().umoe_gemm_wide(ptrs(w), (C.c_int * G)(*[int(v) for v in n_blocks]), (C.c_int * G)(*[int(v) for v in k]), G, rows,
+                                   ptrs(b), ptrs(out, strided=row_major), ldo, n_valid or 0, ptrs(bias), ptrs(resid, strided=True), epilogue,
+                                   waves, u, _stream()), "umoe_gemm_wide")
+    return out
+
+
 def linear(x: torch.Tensor, w_packed: torch.Tensor, N: int, *, bias: Optional[torch.Tensor] = None, norm_w=None,
            rms_eps=1e-6, resid=None, out_f32=False, nt=0) -> torch.Tensor:
     """y = [rmsnorm](x) @ W^T (+bias) (+resid): one dense group."""

@@ -19,13 +19,16 @@ from __future__ import annotations
 from collections import deque
 from typing import Any, Deque, Dict, Iterable, Iterator, List, Tuple
 
-MAX_SLOTS = 8
+MAX_SLOTS = 8          # the default ceiling: the rows of the 16-row decode step
+MAX_SLOTS_WIDE = 32    # the most a caller may raise it to: the rows of the wide decode step
 
 
 class Scheduler:
-    def __init__(self, engine, slots: int, poll_every: int = 16):
-        if not 1 <= slots <= MAX_SLOTS:
-            raise ValueError(f"slots must be 1..{MAX_SLOTS} (got {slots})")
+    def __init__(self, engine, slots: int, poll_every: int = 16, max_slots: int = MAX_SLOTS):
+        if not 1 <= max_slots <= MAX_SLOTS_WIDE:
+            raise ValueError(f"max_slots must be 1..{MAX_SLOTS_WIDE} (got {max_slots})")
+        if not 1 <= slots <= max_slots:
+            raise ValueError(f"slots must be 1..{max_slots} (got {slots})")
         if poll_every < 1:
             raise ValueError("poll_every must be >= 1")
         self.engine, self.slots, self.poll_every = engine, int(slots), int(poll_every)
@@ -68,10 +71,10 @@ class Scheduler:
                     yield index, result
 
 
-def makespan_steps(lengths: Iterable[int], slots: int, poll_every: int) -> int:
+def makespan_steps(lengths: Iterable[int], slots: int, poll_every: int, max_slots: int = MAX_SLOTS) -> int:
     """Decode steps Scheduler.run takes for requests that need `lengths` steps each, in queue order: a request admitted at step a
     is seen ended at the first poll at or after a + length."""
-    sched = Scheduler(_Lengths(), slots, poll_every)
+    sched = Scheduler(_Lengths(), slots, poll_every, max_slots)
     for _ in sched.run(list(lengths)):
         pass
     return sched.steps_run
