@@ -678,7 +678,8 @@ int umoe_rvq_nearest(const float* z, const float* codebooks, const float* in_w, 
  * The Snake activation of the PRECEDING layer (x + sin(alpha x)^2 / (alpha + 1e-9), per input channel) is fused into the input
  * load when snake_alpha != NULL; bias, the residual add of a ResidualUnit (resid, same shape as y) and the decoder's final tanh
  * (act = 1) into the store.  Weights are the weight-normalised tensors already folded (g * v / |v|, done once at load time).
- *   umoe_dac_conv1d:            w [Cout][Cin][K], Lout = (L + 2 pad - dilation (K - 1) - 1) / stride + 1
+ *   umoe_dac_conv1d:            w [Cout][Cin][K], Lout = floor((L + 2 pad - dilation (K - 1) - 1) / stride) + 1; a receptive
+ *                               field wider than the padded input (negative numerator) is an empty output and is refused
  *   umoe_dac_conv_transpose1d:  w [Cin][Cout][K], Lout = (L - 1) stride - 2 pad + K + out_pad */
 int umoe_dac_conv1d(const float* x, const float* w, const float* bias, const float* snake_alpha, const float* resid, int B, int Cin,
                     int L, int Cout, int K, int stride, int dilation, int pad, int act, float* y, int* Lout_out, umoe_stream_t stream);

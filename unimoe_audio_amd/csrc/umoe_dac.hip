@@ -183,6 +183,13 @@ __global__ __launch_bounds__(256) void dac_resample_kernel(const float* __restri
     }
     y[(size_t)b * Lout + j] = acc;
 }
+
+// floor((L + 2 pad - dilation (K - 1) - 1) / stride) + 1, and 0 where the receptive field is wider than the padded input: C division
+// truncates toward zero, which turned a numerator in (-stride, 0) into one output position that does not exist
+long long dac_conv_out_len(int L, int K, int stride, int dilation, int pad) {
+    const long long num = (long long)L + 2LL * pad - (long long)dilation * (K - 1) - 1;
+    return num < 0 ? 0 : num / stride + 1;
+}
 }  // namespace
 
 extern "C" int umoe_dac_resample(const float* x, const float* kern, int B, int L, int o, int n, int width, int Lout, float* y,
@@ -196,10 +203,11 @@ extern "C" int umoe_dac_resample(const float* x, const float* kern, int B, int L
 extern "C" int umoe_dac_conv1d(const float* x, const float* w, const float* bias, const float* snake_alpha, const float* resid, int B,
                                int Cin, int L, int Cout, int K, int stride, int dilation, int pad, int act, float* y, int* Lout_out,
                                umoe_stream_t stream) {
-    UMOE_REQUIRE(x && w && y && B > 0 && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && dilation > 0 && pad >= 0 && L > 0,
+    UMOE_REQUIRE(x && w && B > 0 && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && dilation > 0 && pad >= 0 && L > 0,
                  "umoe_dac_conv1d: bad argument");
-    const int Lout = (L + 2 * pad - dilation * (K - 1) - 1) / stride + 1;
-    UMOE_REQUIRE(Lout > 0, "umoe_dac_conv1d: empty output (L=%d K=%d dilation=%d pad=%d)", L, K, dilation, pad);
+    const int Lout = (int)dac_conv_out_len(L, K, stride, dilation, pad);
+    UMOE_REQUIRE(Lout > 0, "umoe_dac_conv1d: empty output (L=%d K=%d stride=%d dilation=%d pad=%d)", L, K, stride, dilation, pad);
+    UMOE_REQUIRE(y, "umoe_dac_conv1d: bad argument");
     if (Lout_out) *Lout_out = Lout;
     const int XW = (TP - 1) * stride + (K - 1) * dilation + 1;
     const size_t lds = ((size_t)CC * XW + (size_t)CC * K * TO) * sizeof(float);
@@ -244,7 +252,8 @@ extern "C" int umoe_dac_conv1d_win(const float* x, int x_off, int Lx, const floa
                                    int dilation, int pad, int act, int t_begin, int n, float* y, int y_off, int Ly, umoe_stream_t stream) {
     UMOE_REQUIRE(x && w && y && B > 0 && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && dilation > 0 && pad >= 0 && L > 0 && Lx > 0 &&
                  Ly > 0 && t_begin >= 0 && n > 0, "umoe_dac_conv1d_win: bad argument");
-    const long long Lout = ((long long)L + 2 * pad - (long long)dilation * (K - 1) - 1) / stride + 1;
+    const long long Lout = dac_conv_out_len(L, K, stride, dilation, pad);
+    UMOE_REQUIRE(Lout > 0, "umoe_dac_conv1d_win: empty output (L=%d K=%d stride=%d dilation=%d pad=%d)", L, K, stride, dilation, pad);
     UMOE_REQUIRE((long long)t_begin + n <= Lout, "umoe_dac_conv1d_win: outputs [%d, %d) past the sequence's %lld", t_begin, t_begin + n, Lout);
     long long a, b;
     if (dac_needed((long long)t_begin * stride - pad, (long long)(t_begin + n - 1) * stride - pad + (long long)(K - 1) * dilation, L, &a, &b))

@@ -45,7 +45,7 @@ def conv1d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, st
     Cout, Cin2, K = w.shape
     assert Cin2 == Cin
     Lout = (Lx + 2 * padding - dilation * (K - 1) - 1) // stride + 1
-    y = torch.empty((B, Cout, Lout), dtype=torch.float32, device=x.device)
+    y = torch.empty((B, Cout, max(Lout, 0)), dtype=torch.float32, device=x.device)      # (an empty output: the library refuses it)
     if resid is not None:
         assert tuple(resid.shape) == tuple(y.shape)
     lo = C.c_int()
@@ -310,11 +310,8 @@ class DacModel(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------- resampler / wav io
-def resample(wave_BxL: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
-    """torchaudio.transforms.Resample's default algorithm (windowed sinc, Hann window), restated: a bank of `new/gcd` filters applied
-    with stride `orig/gcd` (umoe_dac_resample)."""
-    if orig_freq == new_freq:
-        return wave_BxL
+def resample_filter(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """The filter bank of resample(): (kern [n, 2 * width + o] float32 on the CPU, o, n, width) with o / n = orig / new over their gcd."""
     g = math.gcd(int(orig_freq), int(new_freq))
     o, n = int(orig_freq) // g, int(new_freq) // g
     base = min(o, n) * rolloff
@@ -325,10 +322,19 @@ def resample(wave_BxL: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filt
     window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
     t = t * math.pi
     kern = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base / o)                 # [n, 1, 2*width + o]
+    return kern[:, 0].float().contiguous(), o, n, width
+
+
+def resample(wave_BxL: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """torchaudio.transforms.Resample's default algorithm (windowed sinc, Hann window), restated: a bank of `new/gcd` filters applied
+    with stride `orig/gcd` (umoe_dac_resample)."""
+    if orig_freq == new_freq:
+        return wave_BxL
+    kern, o, n, width = resample_filter(orig_freq, new_freq, lowpass_filter_width, rolloff)
     B, Lx = wave_BxL.shape
     Lout = math.ceil(n * Lx / o)
     x = wave_BxL.float().contiguous()
-    kd = kern[:, 0].float().to(x.device).contiguous()                                                     # [n, 2*width + o]
+    kd = kern.to(x.device).contiguous()                                                                   # [n, 2*width + o]
     y = torch.empty((B, Lout), dtype=torch.float32, device=x.device)
     L.check(L.lib().umoe_dac_resample(_dev_f32(x), _dev_f32(kd), B, Lx, o, n, width, Lout, _dev_f32(y), _stream()), "umoe_dac_resample")
     return y
