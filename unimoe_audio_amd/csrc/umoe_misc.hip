@@ -164,7 +164,14 @@ __global__ __launch_bounds__(256) void combine_kernel(const umoe_combine_args a,
         __syncthreads();
     }
     TL_MARK(9, 5);
-    for (int c = threadIdx.x; c < (a.D >> 3); c += 256) {
+    // WHOLE waves enter the row loop: the dense form broadcasts its tables in here from lanes 0 .. n_real - 1 (and the compiler moves the
+    // table loads in here with them), so those lanes must be active whenever any lane of the wave is -- with a per-lane bound a row of
+    // D / 8 % 64 < n_real chunks (D = 8, D = 536) broadcast registers no lane had written.  A lane past the row's end redoes the row's
+    // last chunk: the same values to the same address.
+    const int n_chunks = a.D >> 3;
+    for (int c0 = threadIdx.x; (c0 & ~63) < n_chunks; c0 += 256) {
+        const bool live = c0 < n_chunks;
+        const int c = live ? c0 : n_chunks - 1;
         float acc[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = 0.f;
@@ -249,7 +256,7 @@ __global__ __launch_bounds__(256) void combine_kernel(const umoe_combine_args a,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             acc[j] = rbf(acc[j]);
-            ss += acc[j] * acc[j];
+            if (live) ss += acc[j] * acc[j];
         }
         TL_MARK(9, 7);
         st16(a.out + (size_t)s * a.D + c * 8, pack8(acc));

@@ -302,10 +302,12 @@ def linear(x: torch.Tensor, w_packed: torch.Tensor, N: int, *, bias: Optional[to
 
 
 def combine(y_slots, slot_of, moe_w, y_shared, global_w, resid, n_dyn: int, n_fix: int, norm_w=None, rms_eps=1e-6,
-            y_parts=None, shared_row0=-1):
+            y_parts=None, shared_row0=-1, expert_mask=None, mask_ld=0, dense_rows=0):
     """y_parts: optional fp32 [n_parts, rows, D] partial slabs of a K-split down GEMM (then y_slots may be None and the
-    shared experts' rows start at `shared_row0` of the same slabs)."""
-    S, n_real = slot_of.shape
+    shared experts' rows start at `shared_row0` of the same slabs).
+    expert_mask: the dense layout of the decode engine instead of a slot table (then slot_of is None): int32 [S, mask_ld], the row of
+    expert e for token s is e * dense_rows + s (dense_rows >= S) and the mask only says which of them are added."""
+    S, n_real = slot_of.shape if slot_of is not None else moe_w.shape
     ref_t = y_slots if y_slots is not None else y_parts
     D = ref_t.shape[-1]
     out = torch.empty((S, D), dtype=torch.bfloat16, device=ref_t.device)
@@ -314,7 +316,7 @@ def combine(y_slots, slot_of, moe_w, y_shared, global_w, resid, n_dyn: int, n_fi
                       resid=_p(resid), out=_p(out), S=S, D=D, n_real=n_real, n_dyn=n_dyn, n_fix=n_fix, y_parts=_p(y_parts),
                       n_parts=0 if y_parts is None else y_parts.shape[0], part_stride=0 if y_parts is None else y_parts.stride(0),
                       shared_row0=shared_row0, norm_w=_p(norm_w),
-                      norm_out=_p(hn), rms_eps=rms_eps)
+                      norm_out=_p(hn), rms_eps=rms_eps, expert_mask=_p(expert_mask), mask_ld=mask_ld, dense_rows=dense_rows)
     L.check(L.lib().umoe_unpermute_combine_fwd(C.byref(a), _stream()), "umoe_unpermute_combine_fwd")
     return (out, hn) if norm_w is not None else out
 
@@ -376,6 +378,27 @@ def attention(q, k_cache, v_cache, kv_start, q_pos0, nq, H, splits=1, qkv_raw=No
     else:
         L.check(L.lib().umoe_attn_decode(C.byref(a), _stream()), "umoe_attn_decode")
     return out
+
+
+# ----------------------------------------------------------------------------- vision tower pieces (csrc/umoe_vision.hip)
+def vision_rope(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, S: int, H: int, hd: int):
+    """in place on the q and k thirds of qkv [S][3][H][hd] bf16; cos / sin [S][hd] fp32"""
+    L.check(L.lib().umoe_vision_rope(_p(_bf(qkv)), _p(cos), _p(sin), S, H, hd, _stream()), "umoe_vision_rope")
+
+
+def vision_attn(qkv: torch.Tensor, seg_lo: torch.Tensor, seg_hi: torch.Tensor, S: int, H: int, hd: int, scale: float, out: torch.Tensor):
+    """non-causal attention of token s over the keys [seg_lo[s], seg_hi[s]) into out [S][H * hd] bf16"""
+    L.check(L.lib().umoe_vision_attn(_p(_bf(qkv)), _p(seg_lo), _p(seg_hi), S, H, hd, scale, _p(_bf(out)), _stream()), "umoe_vision_attn")
+
+
+def swiglu_pair(gu: torch.Tensor, S: int, I: int, ldh: int, h: torch.Tensor):
+    """gu [S][2 I] (gate | up) -> h [S][ldh] = bf16(bf16(silu(g)) * u), columns [I, ldh) zeroed"""
+    L.check(L.lib().umoe_swiglu_pair(_p(_bf(gu)), S, I, ldh, _p(_bf(h)), _stream()), "umoe_swiglu_pair")
+
+
+def gelu(x: torch.Tensor, n: Optional[int] = None):
+    """exact (erf) GELU in place on the first n elements of x (all of them by default)"""
+    L.check(L.lib().umoe_gelu(_p(_bf(x)), x.numel() if n is None else n, _stream()), "umoe_gelu")
 
 
 # ----------------------------------------------------------------------------- codec side
