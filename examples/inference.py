@@ -112,7 +112,7 @@ def main():
     ap.add_argument("--device", "-d", type=int, default=0)
     ap.add_argument("--no-reuse", action="store_true")
     ap.add_argument("--expert-weights", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step)")
+                    help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step; with --serve at every --slots 1..32)")
     ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
     ap.add_argument("--serve", action="store_true", help="with --requests: serve the list as a queue (UniMoEAudio.serve): --slots rows decode "
                                                          "together and a request is admitted as soon as a row is free; any number of requests")

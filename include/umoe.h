@@ -232,6 +232,16 @@ int umoe_grouped_gemm(const umoe_gemm_args* a, umoe_stream_t stream);
 int umoe_gemm_wide(const uint16_t* const* host_w, const int* host_n_blocks, const int* host_k, int num_groups, int rows,
                    const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid, const float* const* host_bias,
                    const uint16_t* const* host_resid, int epilogue, int waves, int u, umoe_stream_t stream);
+/* The gate/up and the down launch of the wide step on WP8 weights (above): host_w8[g] holds the WP8 blocks of group g, host_exps[g] their
+ * row exponents (16 per block), everything else is umoe_gemm_wide's -- tiles, K split, reduction order, epilogue, operand-order tiles in
+ * and (SwiGLU) out.  The e4m3 bytes are converted to the bf16 MFMA operand with the row's 2^e right in front of the MFMAs, so every output
+ * is bit-identical to umoe_gemm_wide on the dequantized weights q * 2^e.  Accepts exactly (UMOE_EPI_SWIGLU, 8, 1) and (UMOE_EPI_BF16, 8, 2);
+ * no bias, no residual.  A group with an even K / 32 streams 16-byte lane loads of two k-steps, one with an odd K / 32 (u = 2 only) one
+ * 8-byte load per k-step; groups of both kinds may share a launch.  The gate/up launch (u = 1) needs K % 512 == 0, the K at which its
+ * wave slices are whole 16-byte chunks: no padded k-step is ever computed.  Weights, input tiles and outputs are 16-byte aligned. */
+int umoe_gemm_wide_fp8(const uint8_t* const* host_w8, const int8_t* const* host_exps, const int* host_n_blocks, const int* host_k,
+                       int num_groups, int rows, const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid,
+                       int epilogue, int waves, int u, umoe_stream_t stream);
 /* rows [rows][lda] (row-major, the first k columns) -> operand-order tiles for umoe_gemm_wide: packed holds ceil(rows / 16) * 16 * k
  * elements, pad rows of the last tile are written as zeros and their source is not read.  norm_w != NULL (k 2048 / 4096): RMSNorm in
  * front, values bit-identical to umoe_router_fwd(norm_only).  x, packed and norm_w are 16-byte aligned, lda % 8 == 0. */
@@ -763,11 +773,17 @@ void umoe_engine_destroy(umoe_engine* e);
 int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer_weights* w);
 /* fp8 expert weights of one layer (after umoe_engine_set_layer): host arrays [n_real + n_fix] (routed experts, then shared) of device
  * pointers to WP8 gate/up pairs, their exponents, WP8 down blocks and theirs.  An engine with fp8 weights runs every dense decode layer's
- * experts through the fp8 flat launch and nothing else: a decode step it cannot run that way (the launch-per-kernel form UMOE_FLAT_MOE=0
+ * experts through the fp8 flat launch (or, above 16 rows with umoe_engine_set_fp8_wide, the wide form on WP8) and nothing else: a decode step it cannot run that way (the launch-per-kernel form UMOE_FLAT_MOE=0
  * UMOE_FUSE_CQ=0, UMOE_FUSE_ROUTER=0, too few compute units for a schedule) is refused before anything is enqueued; expert parallel engines (ep_size > 1) are refused here.
  * umoe_engine_info(e, "expert_fp8") = 1 when the last dense decode layer ran the fp8 launch.  Prefill keeps the bf16 weights. */
 int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* gu8, const int8_t* const* gu_e, const uint8_t* const* dn8,
                               const int8_t* const* dn_e);
+/* on != 0: a decode step of 17..64 rows of an fp8 engine takes the wide form with umoe_gemm_wide_fp8 for gate/up and down (QKV, o_proj,
+ * router, re-lay, combine and head are the bf16 wide launches) at EVERY such size -- the engine has no other path there, so the table of
+ * sizes at which the bf16 wide form was measured faster does not apply; UMOE_WIDE_DECODE=0 makes the step refuse as with the switch off.
+ * umoe_engine_info then gives "expert_launch" 4, "expert_fp8" 1, "row_tiles" = tiles.  Steps of 16 rows or fewer take the fp8 flat launch
+ * either way.  Default off: a directly constructed fp8 engine of more than 16 rows refuses its decode step as before. */
+int umoe_engine_set_fp8_wide(umoe_engine* e, int on);
 /* test hook: the fp8 launch's conversion path over a row-major e4m3 matrix q [N][K] (K % 8 == 0) with one exponent per row:
  * out[r][k] = bf16 bits of q[r][k] * 2^e[r] */
 int umoe_fp8_convert_probe(const uint8_t* q, const int8_t* e, int N, int K, uint16_t* out, umoe_stream_t stream);

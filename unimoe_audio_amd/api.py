@@ -88,7 +88,8 @@ class UniMoEAudio:
     def __init__(self, model_path: Optional[str], device_id: int = 0, config: Optional[UniMoEAudioConfig] = None,
                  model: Optional[UniAudioRVQQwen2_5VLMoEForConditionalGeneration] = None, expert_weights: str = "bf16"):
         """expert_weights "fp8": weight-only fp8 (e4m3, one power-of-two scale per row) of the routed and shared experts
-        (model.quantize_experts_): decode streams half the expert bytes; the whole model then computes with the dequantized weights."""
+        (model.quantize_experts_): decode streams half the expert bytes, at every batch size from 1 to 32 requests; the whole model then
+        computes with the dequantized weights."""
         if expert_weights not in ("bf16", "fp8"):
             raise ValueError(f"expert_weights must be 'bf16' or 'fp8' (got {expert_weights!r})")
         if not torch.cuda.is_available():
@@ -370,7 +371,8 @@ class UniMoEAudio:
         """Continuous batching: a generator that takes SpeechRequest / MusicRequest objects from any iterable (read lazily) and yields
         (index, wav path) as each request ends -- index = the request's position in `requests`, the file is
         `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows (1..32) decode together,
-        above 8 in the wide decode step (every weight streamed once for all rows); a request is admitted into a row as soon as one is free (first in, first out, checked every `poll_every` steps), while the other
+        above 8 in the wide decode step (every weight streamed once for all rows; with fp8 expert weights its gate/up and down launches
+        stream the fp8 copies); a request is admitted into a row as soon as one is free (first in, first out, checked every `poll_every` steps), while the other
         rows keep decoding (DecodeEngine.admit, unimoe_audio_amd/serve.py).  Each request's prompt pair is built as generate_batch builds it
         and keeps its own length.  The engine is sized once: max_prompt_tokens per prompt, max_audio_seconds per request; a request beyond
         either is refused when its turn comes.  Not for expert-parallel engines, video prompts or streamed chunks."""

@@ -98,7 +98,8 @@ struct umoe_engine {
                                  // expert-parallel MoE half (umoe_engine_info; 1 was the removed box-grid launch)
     bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
-    int expert_fp8 = 0;          // the last dense decode layer ran the fp8 flat launch (umoe_engine_info "expert_fp8")
+    int expert_fp8 = 0;          // the last dense decode layer ran an fp8 launch: the flat one, or the wide form's (umoe_engine_info "expert_fp8")
+    bool fp8_wide = false;       // umoe_engine_set_fp8_wide: decode steps of 17..64 rows of an fp8 engine take the wide form on the WP8 weights
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
     bool tiled_prefill = true;   // UMOE_TILED_PREFILL=0: weight-streaming kernels for every row count (A/B, tests)
     // optional per-kernel-class timing of one eager step (hipEvents on the launch stream)
@@ -226,12 +227,21 @@ static bool wide_on(int rows) {
 }
 // A decode step (enqueue_step: T == 1; never a prefill, whatever its token count) of 17..64 rows (batch 9..32) in the dense layout with every weight streamed ONCE for all row tiles (umoe_gemm_wide.hip): QKV,
 // o_proj, gate/up, down and the codec head.  One GPU, bf16 weights, the router shapes of the 16-row step; an admission prefill is a prefill.
-// Takes precedence over the tiled kernels at 64 rows.  fp8 engines and expert-parallel engines never take it (fp8 above 8 requests: the
-// ragged bf16 path, as before).
-static bool wide_mode(const umoe_engine* e, int n_tok) {
+// Takes precedence over the tiled kernels at 64 rows.  Expert-parallel engines never take it; fp8 engines only with the switch
+// umoe_engine_set_fp8_wide, and then at EVERY size (wide_measured_faster compares two bf16 paths; an fp8 engine has no other path above 16
+// rows, so only UMOE_WIDE_DECODE=0 keeps it from the wide form -- and its step is refused, fp8_step_check).
+static bool wide_shapes(const umoe_engine* e, int n_tok) {
     const umoe_engine_cfg& c = e->c;
-    return e->in_decode_step && e->adm_row0 < 0 && n_tok == c.rows && n_tok > 16 && n_tok <= 64 && c.ep_size == 1 && !e->fp8 && c.n_dyn == 9 &&
-           c.n_fix == 2 && c.hidden == 2048 && c.n_real + c.n_fix <= 12 && wide_on(n_tok);
+    return e->adm_row0 < 0 && n_tok == c.rows && n_tok > 16 && n_tok <= 64 && c.ep_size == 1 && c.n_dyn == 9 && c.n_fix == 2 && c.hidden == 2048 &&
+           c.n_real + c.n_fix <= 12;
+}
+static bool fp8_wide_on() {
+    const char* v = getenv("UMOE_WIDE_DECODE");
+    return !v || atoi(v) != 0;
+}
+static bool wide_mode(const umoe_engine* e, int n_tok) {
+    if (!e->in_decode_step || !wide_shapes(e, n_tok)) return false;
+    return e->fp8 ? e->fp8_wide && fp8_wide_on() : wide_on(n_tok);
 }
 
 // (the wide form reads no group table: its launches take the layers' weight pointers; the table built here serves UMOE_WIDE_DECODE=0)
@@ -449,6 +459,12 @@ extern "C" int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_
     L.f8e_gu.assign(gu_e, gu_e + G); L.f8e_dn.assign(dn_e, dn_e + G);
     L.has_f8 = true;
     e->fp8 = true;
+    return 0;
+}
+
+extern "C" int umoe_engine_set_fp8_wide(umoe_engine* e, int on) {
+    UMOE_REQUIRE(e, "umoe_engine_set_fp8_wide: null engine");
+    e->fp8_wide = on != 0;
     return 0;
 }
 
@@ -913,7 +929,11 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
     int rc;
     if ((rc = umoe_pack_rows(e->x1, D, n_tok, D, L.w.post_norm, c.rms_eps, e->wide_in, s))) return rc;
     PROF(K_DISPATCH);
+    const bool f8 = e->fp8;      // (wide_mode admitted the step: the switch is on and fp8_step_check saw every layer's WP8 weights)
+    UMOE_REQUIRE(!f8 || L.has_f8, "umoe_engine: fp8 expert weights: a layer has none (umoe_engine_set_layer_fp8)");
     const uint16_t *wgu[12], *wdn[12], *bx[12], *bh[12];
+    const uint8_t *wgu8[12], *wdn8[12];
+    const int8_t *egu[12], *edn[12];
     void *oh[12], *oy[12];
     int nb_gu[12], nb_dn[12], k_gu[12], k_dn[12];
     for (int x = 0; x < G; ++x) {
@@ -921,6 +941,10 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
         const int I = sh ? c.inter_shared : c.inter_dyn;
         wgu[x] = sh ? L.sh_gu[x - c.n_real] : L.exp_gu[x];
         wdn[x] = sh ? L.sh_dn[x - c.n_real] : L.exp_dn[x];
+        if (f8) {                // [routed, then shared], as umoe_engine_set_layer_fp8 stored them
+            wgu8[x] = reinterpret_cast<const uint8_t*>(L.f8_gu[x]); egu[x] = L.f8e_gu[x];
+            wdn8[x] = reinterpret_cast<const uint8_t*>(L.f8_dn[x]); edn[x] = L.f8e_dn[x];
+        }
         bx[x] = e->wide_in;
         oh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;      // [tiles][16 * I] in operand order
         bh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;
@@ -928,9 +952,13 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
         nb_gu[x] = 2 * I / 16; k_gu[x] = D;
         nb_dn[x] = D / 16; k_dn[x] = I;
     }
-    if ((rc = umoe_gemm_wide(wgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, nullptr, nullptr, UMOE_EPI_SWIGLU, 8, 1, s))) return rc;
+    if (f8) rc = umoe_gemm_wide_fp8(wgu8, egu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, UMOE_EPI_SWIGLU, 8, 1, s);
+    else rc = umoe_gemm_wide(wgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, nullptr, nullptr, UMOE_EPI_SWIGLU, 8, 1, s);
+    if (rc) return rc;
     PROF(K_GATEUP);
-    if ((rc = umoe_gemm_wide(wdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, nullptr, nullptr, UMOE_EPI_BF16, 8, 2, s))) return rc;
+    if (f8) rc = umoe_gemm_wide_fp8(wdn8, edn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, UMOE_EPI_BF16, 8, 2, s);
+    else rc = umoe_gemm_wide(wdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, nullptr, nullptr, UMOE_EPI_BF16, 8, 2, s);
+    if (rc) return rc;
     PROF(K_DOWN);
     return 0;
 }
@@ -1047,7 +1075,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
         e->expert_launch = 0;
         e->row_tiles = 1;
     }
-    UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
+    UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT && form != MOE_WIDE), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
     umoe_router_args ra{};
     ra.x = e->x1; ra.gate_w = L.w.gate_w; ra.norm_w = L.w.post_norm; ra.h_out = e->h2; ra.S = n_tok; ra.D = D;
     ra.n_dyn = c.n_dyn; ra.n_real = c.n_real; ra.n_fix = c.n_fix; ra.logits_bf16 = 1; ra.top_p = c.top_p;
@@ -1144,7 +1172,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             PROF(K_ROUTER);
             if ((rc = experts_wide(e, L, n_tok, s))) return rc;
             e->expert_launch = 4;
-            e->expert_fp8 = 0;
+            e->expert_fp8 = e->fp8 ? 1 : 0;
             e->row_tiles = ceil_div(n_tok, 16);
             break;
     }
@@ -1500,12 +1528,18 @@ extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* 
     return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, (hipStream_t)stream);
 }
 
-// An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch (moe_form: MOE_FLAT): the
-// launch-per-kernel forms would stream bf16 expert weights it does not run on.  Checked on the host before anything is enqueued.
+// An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch (moe_form: MOE_FLAT) or, with the
+// switch umoe_engine_set_fp8_wide, the wide form on the WP8 weights (17..64 rows): the launch-per-kernel forms would stream bf16 expert
+// weights it does not run on.  Checked on the host before anything is enqueued.
 static int fp8_step_check(umoe_engine* e) {
     if (!e->fp8) return 0;
     const umoe_engine_cfg& c = e->c;
     UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: fp8 expert weights are not supported expert parallel (ep_size %d)", c.ep_size);
+    if (e->fp8_wide && fp8_wide_on() && wide_shapes(e, c.rows)) {      // the step wide_mode will admit
+        for (int l = 0; l < c.layers; ++l)
+            UMOE_REQUIRE(e->layers[l].has_f8, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
+        return 0;
+    }
     UMOE_REQUIRE(flat_moe_on(), "umoe_engine: fp8 expert weights need the flat expert launch (UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 is the bf16 launch-per-kernel form)");
     UMOE_REQUIRE(e->fuse_router, "umoe_engine: fp8 expert weights need the flat expert launch with its router riders (UMOE_FUSE_ROUTER=0 selects a bf16 path)");
     UMOE_REQUIRE(dense_mode(e, c.rows) && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096),

@@ -17,7 +17,14 @@
 //  * groups carry their own n_blocks and K (routed and shared experts in one launch): the grid is a box over the widest group.
 // Pad rows of a partial last tile are zero on input (pack_rows, and silu(0) * 0 = 0 behind it) and are never stored row-major.
 // Roofline: HBM.  Algorithmic bytes per launch = sum over groups of N*K*2.
-#include "umoe_common.h"
+//
+// FP8 form (wstream_wide_f8, umoe_gemm_wide_fp8: the gate/up and down launches of an fp8 engine): the same body on WP8 blocks
+// (include/umoe.h).  Only the weight stream differs: the rings hold e4m3 bytes, converted to the bf16 MFMA operand right in front of the
+// MFMAs with the row's 2^e (flat_f8_frag), so every output is bit-identical to the bf16 form run on the dequantized weights.  A group with
+// an even number of k-steps streams 16-byte lane loads of two k-steps; a group with an odd number (the shared experts' down projection, 43
+// k-steps: wave slices start and end on either half of a chunk) streams one 8-byte load per k-step.  The form is a scalar branch per
+// group, so routed and shared groups share one down launch.  No padded k-step is loaded or computed.
+#include "umoe_flat_dev.h"      // (umoe_common.h; flat_f8_frag / flat_f8_scale)
 #include <string.h>
 
 #define UMOE_WIDE_MAXG 12
@@ -190,22 +197,189 @@ __global__ __launch_bounds__(WV * 64, 1) void wstream_wide(const wide_args p) {
     }
 }
 
+// ---- the fp8 form: prologue, K split, reduction and the two epilogues it runs (SwiGLU, bf16 without bias) are wstream_wide's, restated
+// here so that the bf16 kernels above stay byte for byte what they were; only the weight stream between them is new
+struct wide_f8_args {                       // the fp8 form's own argument block (wide_args stays as it is)
+    const uint8_t* w[UMOE_WIDE_MAXG];       // WP8 weights of group g (gate/up blocks interleaved for SwiGLU)
+    const int8_t* exps[UMOE_WIDE_MAXG];     // row exponents, 16 per weight block
+    const uint16_t* b[UMOE_WIDE_MAXG];      // operand-order tiles, as wide_args
+    void* out[UMOE_WIDE_MAXG];
+    int n_blocks[UMOE_WIDE_MAXG], k[UMOE_WIDE_MAXG];
+    int num_groups, rows, tiles, ldo, n_valid;
+};
+
+// RW: k-steps the weight ring holds (RW / 2 stages of 16 bytes, or RW stages of 8 bytes for an odd number of k-steps)
 template <int NT, int MT, int U, int WV, int EPI, int RW, int RB, bool WREFILL>
-static int launch_wide_v(const wide_args& a, int max_nb, hipStream_t s) {
+__global__ __launch_bounds__(WV * 64, 1) void wstream_wide_f8(const wide_f8_args p) {
+    static_assert(EPI == UMOE_EPI_SWIGLU || EPI == UMOE_EPI_BF16, "the fp8 form runs the gate/up and the down launch");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const int g = blockIdx.z, nb0 = blockIdx.x * NT;
+    const int n_blocks = p.n_blocks[g];
+    if (nb0 >= n_blocks) return;
+    const int K = p.k[g], KB = K >> 5;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int i0, i1;
+    if (KB % U == 0) {
+        const int units = KB / U;
+        i0 = U * ((units * wave) / WV);
+        i1 = U * ((units * (wave + 1)) / WV);
+    } else {
+        i0 = (KB * wave) / WV;
+        i1 = (KB * (wave + 1)) / WV;
+    }
+    i0 = __builtin_amdgcn_readfirstlane(i0);
+    i1 = __builtin_amdgcn_readfirstlane(i1);
+    const u32x4_t* wp[NT];      // the block's first 16-byte chunk (two k-steps)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int nb = min(nb0 + t, n_blocks - 1);   // tail blocks re-read the last one; never stored
+        wp[t] = reinterpret_cast<const u32x4_t*>(p.w[g]) + ((size_t)nb * ((KB + 1) >> 1)) * 64 + lane;
+    }
+    const u32x4_t* bp[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int mm = min(m, p.tiles - 1);
+        bp[m] = reinterpret_cast<const u32x4_t*>(p.b[g]) + ((size_t)mm * KB) * 64 + lane;
+    }
+    f32x4_t acc[MT][NT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[m][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // the rings of wstream_wide with e4m3 bytes in the weight stages: CS k-steps per stage (2: one 16-byte load, 1: one 8-byte load).  The fragment
+    // ring, the refill order and the clamps are the same; the row exponents are requested behind the first weight stages
+    u32x4_t br[RB][MT];
+    auto load_b = [&](u32x4_t (&d)[MT], int ii) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) d[m] = bp[m][(size_t)ii * 64];
+    };
+    const int8_t* ex = p.exps[g] + (lane & 15);
+    auto stream = [&](auto cs) {
+        constexpr int CS = decltype(cs)::value;
+        using WT = std::conditional_t<CS == 2, u32x4_t, flat_u32x2>;
+        WT wr[RW / CS][NT];
+        auto load_w = [&](WT (&d)[NT], int ii) {      // the stage that starts at k-step ii (CS == 2: ii is even)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const WT* c = reinterpret_cast<const WT*>(wp[t]);
+                d[t] = __builtin_nontemporal_load(CS == 2 ? c + (size_t)(ii >> 1) * 64 : c + (size_t)(ii >> 1) * 128 + (ii & 1));
+            }
+        };
+        const int il = max(i1 - 1, 0), ilw = max(i1 - CS, 0);
+#pragma unroll
+        for (int r = 0; r < RB; ++r) load_b(br[r], min(i0 + r, il));
+#pragma unroll
+        for (int r = 0; r < RW / CS; ++r) load_w(wr[r], min(i0 + CS * r, ilw));
+        float sc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) sc[t] = flat_f8_scale(ex[min(nb0 + t, n_blocks - 1) * 16]);
+        __builtin_amdgcn_sched_barrier(0);
+        for (int base = i0; base < i1; base += RW) {
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const int ii = base + r;
+                if (ii < i1) {
+                    bf16x8_t wf[NT];
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) wf[t] = flat_f8_frag(wr[r / CS][t][2 * (r % CS)], wr[r / CS][t][2 * (r % CS) + 1], sc[t]);
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) {
+                        const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, br[r % RB][m]);
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[t], bfrag, acc[m][t], 0, 0, 0);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                load_b(br[r % RB], min(ii + RB, il));
+                if constexpr (WREFILL)
+                    if (r % CS == CS - 1) load_w(wr[r / CS], min(ii - (CS - 1) + RW, ilw));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    // (U == 1: the host admits only K whose wave slices are whole chunks)
+    if (U == 2 && (KB & 1)) stream(std::integral_constant<int, 1>{});
+    else stream(std::integral_constant<int, 2>{});
+    // ---- fixed-order cross-wave reduction (wave 0 first) ----
+    f32x4_t* red = reinterpret_cast<f32x4_t*>(smem);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) red[((wave * MT + m) * NT + t) * 64 + lane] = acc[m][t];
+    __syncthreads();
+    auto reduced = [&](int m, int t) -> f32x4_t {
+        f32x4_t s = red[(m * NT + t) * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < WV; ++w) {
+            const f32x4_t v = red[((w * MT + m) * NT + t) * 64 + lane];
+            s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
+        }
+        return s;
+    };
+    const int h = lane >> 4, mm = lane & 15;
+    if constexpr (EPI == UMOE_EPI_SWIGLU) {
+        const int I = n_blocks * 8, Q = I >> 2;
+        for (int q = wave; q < MT * (NT / 2); q += WV) {
+            const int m = q / (NT / 2), pq = q % (NT / 2);
+            if (m >= p.tiles || nb0 + 2 * pq >= n_blocks) continue;
+            const f32x4_t ga = reduced(m, 2 * pq), ua = reduced(m, 2 * pq + 1);
+            uint16_t y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gt = rbf(ga[j]);
+                const float up = rbf(ua[j]);
+                const float si = rbf(gt / (1.0f + expf(-gt)));
+                y[j] = f2bf(si * up);
+            }
+            const int f = (nb0 / 2 + pq) * 16 + 4 * h;
+            const int qq = f / Q, r = f % Q;
+            uint16_t* o = reinterpret_cast<uint16_t*>(p.out[g]) + (size_t)m * 16 * I + ((size_t)(r >> 3) * 64 + qq * 16 + mm) * 8 + (r & 7);
+            *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16));
+        }
+    } else {
+        for (int q = wave; q < MT * NT; q += WV) {
+            const int m = q / NT, t = q % NT;
+            const int row = m * 16 + mm;
+            if (m >= p.tiles || nb0 + t >= n_blocks || row >= p.rows) continue;      // pad rows are never stored
+            const f32x4_t a4 = reduced(m, t);
+            const int n = (nb0 + t) * 16 + 4 * h;
+            if (n >= p.n_valid) continue;
+            uint16_t* o = reinterpret_cast<uint16_t*>(p.out[g]) + (size_t)row * p.ldo + n;
+            uint16_t y[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = f2bf(rbf(a4[j] + 0.f));      // (+ 0.f: the bias slot of wstream_wide; -0 -> +0 like there)
+            if (n + 3 < p.n_valid) {
+                *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)y[0] | ((uint32_t)y[1] << 16), (uint32_t)y[2] | ((uint32_t)y[3] << 16));
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (n + j < p.n_valid) o[j] = y[j];
+            }
+        }
+    }
+}
+
+template <int NT, int MT, int U, int WV, int EPI, int RW, int RB, bool WREFILL, typename ARGS>
+static int launch_wide_v(const ARGS& a, int max_nb, hipStream_t s) {
     const size_t lds = (size_t)WV * MT * NT * 64 * 16;
+    void (*kernel)(const ARGS);
+    if constexpr (std::is_same_v<ARGS, wide_f8_args>) kernel = &wstream_wide_f8<NT, MT, U, WV, EPI, RW, RB, WREFILL>;
+    else kernel = &wstream_wide<NT, MT, U, WV, EPI, RW, RB, WREFILL>;
     static bool configured = false;
     if (!configured) {
-        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wstream_wide<NT, MT, U, WV, EPI, RW, RB, WREFILL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         configured = true;
     }
     const dim3 grid((unsigned)ceil_div(max_nb, NT), 1, (unsigned)a.num_groups);
-    wstream_wide<NT, MT, U, WV, EPI, RW, RB, WREFILL><<<grid, WV * 64, lds, s>>>(a);
+    kernel<<<grid, WV * 64, lds, s>>>(a);
     UMOE_LAUNCH_CHECK();
     return 0;
 }
 
-template <int NT, int MT, int U, int WV, int EPI, int RW, int RB>
-static int launch_wide(const wide_args& a, hipStream_t s) {
+template <int NT, int MT, int U, int WV, int EPI, int RW, int RB, typename ARGS>
+static int launch_wide(const ARGS& a, hipStream_t s) {
     // k-steps of the longest wave slice over the groups: no weight refill when the ring holds them all
     int longest = 0, max_nb = 0;
     for (int g = 0; g < a.num_groups; ++g) {
@@ -266,6 +440,45 @@ extern "C" int umoe_gemm_wide(const uint16_t* const* host_w, const int* host_n_b
                  "umoe_gemm_wide: (epilogue, waves, u) must be one of the decode step's: (bf16 | bf16+resid, 4, 16), (fp32, 4, 16 | 8 | 2), (SwiGLU, 8, 1), "
                  "(bf16, 8, 2) (got %d, %d, %d)",
                  epilogue, waves, u);
+}
+
+// The gate/up and down launches of the wide step on WP8 weights: (SwiGLU, 8, 1) and (bf16, 8, 2), tiles and K split as above.  Ring depths
+// (DESIGN 4i): a k-step is half the registers of the bf16 form's, so the rings of down (12 k-steps) and of gate/up at three or four tiles
+// (8) hold a wave's whole K slice of the decode shapes and are never refilled; gate/up at two tiles (8 blocks per workgroup) keeps the
+// bf16 form's 4 k-steps -- 6 and 8 spill.
+extern "C" int umoe_gemm_wide_fp8(const uint8_t* const* host_w8, const int8_t* const* host_exps, const int* host_n_blocks, const int* host_k,
+                                  int num_groups, int rows, const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid,
+                                  int epilogue, int waves, int u, umoe_stream_t stream) {
+    UMOE_REQUIRE(host_w8 && host_exps && host_n_blocks && host_k && host_b && host_out, "umoe_gemm_wide_fp8: null argument");
+    UMOE_REQUIRE(num_groups >= 1 && num_groups <= UMOE_WIDE_MAXG, "umoe_gemm_wide_fp8: 1..%d groups (got %d)", UMOE_WIDE_MAXG, num_groups);
+    UMOE_REQUIRE(rows > 16 && rows <= 64, "umoe_gemm_wide_fp8: 17..64 rows (got %d): 16 rows and fewer are the fp8 flat expert launch's", rows);
+    const bool swiglu = epilogue == UMOE_EPI_SWIGLU && waves == 8 && u == 1, down = epilogue == UMOE_EPI_BF16 && waves == 8 && u == 2;
+    UMOE_REQUIRE(swiglu || down, "umoe_gemm_wide_fp8: (epilogue, waves, u) must be the gate/up or the down launch's: (SwiGLU, 8, 1), (bf16, 8, 2) (got %d, %d, %d)",
+                 epilogue, waves, u);
+    wide_f8_args a;
+    memset(&a, 0, sizeof(a));
+    a.num_groups = num_groups; a.rows = rows; a.tiles = ceil_div(rows, 16); a.ldo = ldo; a.n_valid = n_valid;
+    for (int g = 0; g < num_groups; ++g) {
+        a.w[g] = host_w8[g]; a.exps[g] = host_exps[g]; a.b[g] = host_b[g]; a.out[g] = host_out[g];
+        a.n_blocks[g] = host_n_blocks[g]; a.k[g] = host_k[g];
+        UMOE_REQUIRE(a.w[g] && a.exps[g] && a.b[g] && a.out[g], "umoe_gemm_wide_fp8: group %d lacks weights, exponents, input tiles or an output", g);
+        UMOE_REQUIRE((((uintptr_t)a.w[g] | (uintptr_t)a.b[g] | (uintptr_t)a.out[g]) & 15) == 0,
+                     "umoe_gemm_wide_fp8: group %d: weights, input tiles and output must be 16-byte aligned (16-byte vector accesses)", g);
+        UMOE_REQUIRE(a.k[g] > 0 && a.k[g] % 32 == 0 && a.n_blocks[g] > 0, "umoe_gemm_wide_fp8: group %d: K %% 32 == 0, n_blocks > 0 (K=%d n_blocks=%d)", g,
+                     a.k[g], a.n_blocks[g]);
+        UMOE_REQUIRE(!swiglu || a.n_blocks[g] % 4 == 0, "umoe_gemm_wide_fp8: SwiGLU needs gate/up block pairs and I %% 32 == 0 (group %d: %d blocks)", g,
+                     a.n_blocks[g]);
+        // u = 1 splits K in single steps: only when every wave boundary K / 32 * w / 8 is even is a slice whole 16-byte chunks (u = 2 serves
+        // every K: whole chunks for an even number of k-steps, 8-byte loads for an odd one)
+        UMOE_REQUIRE(!swiglu || a.k[g] % 512 == 0, "umoe_gemm_wide_fp8: the gate/up launch needs K %% 512 == 0 (group %d: K=%d): no padded k-step is computed", g,
+                     a.k[g]);
+        UMOE_REQUIRE(swiglu || (ldo % 4 == 0 && n_valid > 0 && n_valid <= ldo),
+                     "umoe_gemm_wide_fp8: row-major outputs need ldo %% 4 == 0 and 0 < n_valid <= ldo (ldo=%d n_valid=%d)", ldo, n_valid);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool two = a.tiles == 2;
+    if (swiglu) return two ? launch_wide<8, 2, 1, 8, UMOE_EPI_SWIGLU, 4, 2>(a, s) : launch_wide<4, 4, 1, 8, UMOE_EPI_SWIGLU, 8, 2>(a, s);
+    return two ? launch_wide<2, 2, 2, 8, UMOE_EPI_BF16, 12, 4>(a, s) : launch_wide<1, 4, 2, 8, UMOE_EPI_BF16, 12, 4>(a, s);
 }
 
 // ------------------------------------------------------------------------------------ operand-order producers

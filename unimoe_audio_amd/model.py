@@ -358,21 +358,25 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
                expert_weights: Optional[str] = None) -> "DecodeEngine":
         """The decode engine for this shape, rebuilt when the shape, the weights (data pointer / version of any parameter) or the
         expert-parallel link changed.  `ep`: an unimoe_audio_amd.ep.EpLink (every rank of the link calls this together).
-        `expert_weights` "bf16" / "fp8" (None: "fp8" when quantize_experts_('fp8') ran on this model, else "bf16")."""
+        `expert_weights` "bf16" / "fp8" (None: "fp8" when quantize_experts_('fp8') ran on this model, else "bf16").  An fp8 engine built
+        here decodes batches of 9 to 32 requests in the wide form on the fp8 weights (DecodeEngine fp8_wide=True)."""
         need_L = max_prompt + max_tokens + 8
         e = self._engine
         key = self._pack_key()
         fmt = expert_weights or ("fp8" if quant.is_quantized(self) else "bf16")
+        fp8_wide = fmt == "fp8"
         if (e is None or e.batch != batch or e.Lmax < need_L or e.Tmax < max_tokens + 64 or e.pack_key != key or e.ep is not ep
-                or e.expert_weights != fmt):
+                or e.expert_weights != fmt or e.fp8_wide != fp8_wide):
             if e is not None:
                 e.close()
-            self._engine = DecodeEngine(self, batch, Lmax=need_L, Tmax=max_tokens + 64, attn_splits=attn_splits, ep=ep, expert_weights=fmt)
+            self._engine = DecodeEngine(self, batch, Lmax=need_L, Tmax=max_tokens + 64, attn_splits=attn_splits, ep=ep, expert_weights=fmt,
+                                        fp8_wide=fp8_wide)
         return self._engine
 
     def quantize_experts_(self, fmt: str = "fp8"):
         """Weight-only fp8 of the routed and shared experts (unimoe_audio_amd/quant.py): the parameters become their dequantized
-        values W_deq in place; decode engines built afterwards stream the e4m3 copies (half the expert bytes)."""
+        values W_deq in place; decode engines built afterwards stream the e4m3 copies (half the expert bytes): the flat expert launch
+        up to 8 requests, the wide step's gate/up and down launches for 9 to 32."""
         return quant.quantize_experts_(self, fmt)
 
     @torch.no_grad()
@@ -503,7 +507,10 @@ class DecodeEngine:
     """Python face of umoe_engine_*: packs the weights once, owns the C engine and the decode state."""
 
     def __init__(self, model: UniAudioRVQQwen2_5VLMoEForConditionalGeneration, batch: int, Lmax: int, Tmax: int,
-                 attn_splits: int = 8, max_pos: Optional[int] = None, ep=None, ep_connect: bool = True, expert_weights: Optional[str] = None):
+                 attn_splits: int = 8, max_pos: Optional[int] = None, ep=None, ep_connect: bool = True, expert_weights: Optional[str] = None,
+                 fp8_wide: bool = False):
+        """fp8_wide: an fp8 engine of 9 to 32 requests decodes in the wide form with the gate/up and down launches on the fp8 weights
+        (umoe_engine_set_fp8_wide).  False (default): such an engine refuses its decode step, as it always did; model.engine() passes True."""
         cfg = model.config
         fmt = expert_weights or ("fp8" if quant.is_quantized(model) else "bf16")
         if fmt not in ("bf16", "fp8"):
@@ -513,6 +520,7 @@ class DecodeEngine:
                 raise L.UmoeError("fp8 expert weights run on the flat expert launch only: not with expert parallel decode")
             quant.check_quantized(model)      # refuses stale fp8 copies (a weight edited after quantize_experts_)
         self.expert_weights = fmt
+        self.fp8_wide = bool(fp8_wide)
         dev = model.device
         if dev.type != "cuda":
             raise L.UmoeError("DecodeEngine needs the model on a ROCm device; there is no CPU path in the product")
@@ -536,6 +544,8 @@ class DecodeEngine:
         self.h = h
         self.keep: List[torch.Tensor] = []
         self._pack_weights(max_pos)
+        if self.fp8_wide:
+            L.check(L.lib().umoe_engine_set_fp8_wide(self.h, 1), "umoe_engine_set_fp8_wide")
         if ep is not None and ep.size > 1 and ep_connect:
             ep.connect(self.h)
         self.tokens = None
@@ -980,8 +990,8 @@ class DecodeEngine:
     def info(self, key: str) -> int:
         """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 2 flat, 3 the one-launch
         expert-parallel MoE half, 4 the wide form of 17..64 rows; 1 was the removed box-grid launch and is never returned), "row_tiles"
-        (16-row tiles per weight pass of the wide form, 1 otherwise), "n_cu", "expert_fp8" (1: the last dense decode layer ran the fp8
-        flat launch)."""
+        (16-row tiles per weight pass of the wide form, 1 otherwise), "n_cu", "expert_fp8" (1: the last dense decode layer ran an fp8
+        launch: the flat one, or gate/up and down of the wide form)."""
         return int(L.lib().umoe_engine_info(self.h, key.encode()))
 
     def write_buffer(self, name: str, src: torch.Tensor, offset_bytes: int = 0) -> None:

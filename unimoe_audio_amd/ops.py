@@ -290,6 +290,28 @@ def gemm_wide(w: Sequence[torch.Tensor], n_blocks: Sequence[int], k: Sequence[in
     return out
 
 
+def gemm_wide_fp8(w8: Sequence[torch.Tensor], exps: Sequence[Optional[torch.Tensor]], n_blocks: Sequence[int], k: Sequence[int], rows: int,
+                  b: Sequence[torch.Tensor], out: Sequence[torch.Tensor], *, epilogue: int, waves: int, u: int, n_valid: Optional[int] = None):
+    """umoe_gemm_wide_fp8: the gate/up (SwiGLU, 8, 1) or down (bf16, 8, 2) launch of gemm_wide on WP8 weights `w8[g]` (uint8) with their row
+    exponents `exps[g]` (int8, 16 per block; quant.pack_wp8 / pack_wp8_gate_up).  Bit-identical to gemm_wide on the dequantized weights."""
+    G = len(w8)
+    assert G == len(exps) == len(n_blocks) == len(k) == len(b) == len(out) and G >= 1
+
+    def ptrs(ts, strided=False):
+        return (C.c_void_p * G)(*[None if t is None else (_pv(t) if strided else _p(t).value) for t in ts])
+
+    row_major = epilogue != EPI_SWIGLU
+    ldo = out[0].stride(0) if row_major else 0
+    if row_major:
+        assert all(o.dim() == 2 and o.stride(0) == ldo and o.shape[0] >= rows for o in out)
+        if n_valid is None:
+            n_valid = out[0].shape[1]
+    L.check(L.lib().umoe_gemm_wide_fp8(ptrs(w8), ptrs(exps), (C.c_int * G)(*[int(v) for v in n_blocks]), (C.c_int * G)(*[int(v) for v in k]), G,
+                                       rows, ptrs(b), ptrs(out, strided=row_major), ldo, n_valid or 0, epilogue, waves, u, _stream()),
+            "umoe_gemm_wide_fp8")
+    return out
+
+
 def linear(x: torch.Tensor, w_packed: torch.Tensor, N: int, *, bias: Optional[torch.Tensor] = None, norm_w=None,
            rms_eps=1e-6, resid=None, out_f32=False, nt=0) -> torch.Tensor:
     """y = [rmsnorm](x) @ W^T (+bias) (+resid): one dense group."""
