@@ -293,6 +293,14 @@ typedef struct {
     int ld_aux;               /* gate at aux_out[row][col], up at aux_out[row][n + col] (what autograd would save) */
 } umoe_tgemm_args;
 int umoe_tiled_gemm(const umoe_tgemm_args* a, umoe_stream_t stream);
+/* The same GEMM on WP8 weights (above; prefill of an engine that holds its experts as e4m3 only): host_w8[g] holds the WP8 blocks of
+ * group g's weight [n][k] and host_exps[g] their row exponents (16 per block); with UMOE_EPI_SWIGLU host_w8[g] is the interleaved
+ * gate/up pair (n = intermediate size, n % 16 == 0) and serves gate and up.  The groups' w / w2 / ldw are not read.  tgemm_kernel's
+ * register-staging form with the e4m3 granules converted on their way into the LDS image, everything behind it shared: every output is
+ * bit-identical to umoe_tiled_gemm's small-tile kernel on the dequantized weights q * 2^e (128- and 256-token tiles by the same rule;
+ * there is no 256 x 256 ping-pong form).  UMOE_EPI_SWIGLU (no aux_out) and UMOE_EPI_BF16; gather list, device-side count and row offset
+ * as umoe_tiled_gemm; k % 32 == 0.  Refused: w_kmajor, K windows (k_off / k_count / k_compact_*), bias, the other epilogues. */
+int umoe_tiled_gemm_wp8(const umoe_tgemm_args* a, const uint8_t* const* host_w8, const int8_t* const* host_exps, umoe_stream_t stream);
 
 /* Weight-gradient form of the tiled GEMM: both operands are row-major with the CONTRACTION index as the row (tokens / expert slots), as
  * autograd holds activations and their gradients -- dW = dY^T X without transposed copies (torch.nn.functional.linear backward,
@@ -775,7 +783,13 @@ int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer_weights* w
  * pointers to WP8 gate/up pairs, their exponents, WP8 down blocks and theirs.  An engine with fp8 weights runs every dense decode layer's
  * experts through the fp8 flat launch (or, above 16 rows with umoe_engine_set_fp8_wide, the wide form on WP8) and nothing else: a decode step it cannot run that way (the launch-per-kernel form UMOE_FLAT_MOE=0
  * UMOE_FUSE_CQ=0, UMOE_FUSE_ROUTER=0, too few compute units for a schedule) is refused before anything is enqueued; expert parallel engines (ep_size > 1) are refused here.
- * umoe_engine_info(e, "expert_fp8") = 1 when the last dense decode layer ran the fp8 launch.  Prefill keeps the bf16 weights. */
+ * umoe_engine_info(e, "expert_fp8") = 1 when the last dense decode layer ran the fp8 launch.  Prefill keeps the bf16 weights.
+ * FP8-ONLY layers: umoe_engine_set_layer may be given NO bf16 expert weight at all (exp_gu, exp_dn, sh_gu, sh_dn and every rm_exp_* /
+ * rm_sh_* NULL; rm_qkv and rm_o present) when this call follows.  The experts of a prefill or admission of such an engine run on the
+ * WP8 blocks at every row count (umoe_tiled_gemm_wp8), decode as above, and every pass that would stream a bf16 expert weight (the
+ * ragged streaming GEMM, the launch-per-kernel decode forms, the bf16 wide form, UMOE_TILED_PREFILL=0) is refused on the host before
+ * anything is enqueued.  umoe_engine_info: "expert_bf16_resident" 0 / 1; "prefill_fp8" 1 when the last prefill / admission ran its
+ * experts on WP8. */
 int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* gu8, const int8_t* const* gu_e, const uint8_t* const* dn8,
                               const int8_t* const* dn_e);
 /* on != 0: a decode step of 17..64 rows of an fp8 engine takes the wide form with umoe_gemm_wide_fp8 for gate/up and down (QKV, o_proj,

@@ -156,7 +156,7 @@ EXPORTS = [
     "umoe_engine_ep_error", "umoe_token_drop", "umoe_router_bwd_drop", "umoe_router_bwd_ex", "umoe_dac_conv1d", "umoe_dac_conv_transpose1d", "umoe_dac_resample", "umoe_vision_rope", "umoe_vision_attn", "umoe_swiglu_pair", "umoe_gelu", "umoe_engine_prefill_pos", "umoe_engine_set_probe", "umoe_engine_info", "umoe_engine_prefill_external", "umoe_engine_set_layer_fp8", "umoe_fp8_convert_probe",
     "umoe_dac_conv1d_win", "umoe_dac_conv_transpose1d_win", "umoe_rvq_from_delayed", "umoe_delay_step_rows",
     "umoe_delay_step_clock", "umoe_engine_reserve", "umoe_engine_admit", "umoe_engine_admit_external", "umoe_gemm_wide", "umoe_pack_rows",
-    "umoe_gemm_wide_fp8", "umoe_engine_set_fp8_wide",
+    "umoe_gemm_wide_fp8", "umoe_engine_set_fp8_wide", "umoe_tiled_gemm_wp8",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -280,6 +280,9 @@ def lib():
         L.umoe_gemm_wide_fp8.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32,
                                          i32, i32, i32, vp]
         L.umoe_engine_set_fp8_wide.argtypes = [vp, i32]
+        if not hasattr(L, "umoe_tiled_gemm_wp8"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_tiled_gemm_wp8): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_tiled_gemm_wp8.argtypes = [C.POINTER(TGemmArgs), C.POINTER(vp), C.POINTER(vp), vp]
         L.umoe_rvq_from_codes.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_nearest.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.umoe_codec_ce_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]

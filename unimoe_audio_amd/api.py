@@ -89,9 +89,11 @@ class UniMoEAudio:
                  model: Optional[UniAudioRVQQwen2_5VLMoEForConditionalGeneration] = None, expert_weights: str = "bf16"):
         """expert_weights "fp8": weight-only fp8 (e4m3, one power-of-two scale per row) of the routed and shared experts
         (model.quantize_experts_): decode streams half the expert bytes, at every batch size from 1 to 32 requests; the whole model then
-        computes with the dequantized weights."""
-        if expert_weights not in ("bf16", "fp8"):
-            raise ValueError(f"expert_weights must be 'bf16' or 'fp8' (got {expert_weights!r})")
+        computes with the dequantized weights.  "fp8-only": the same, and the bf16 expert parameters are released -- each expert as soon
+        as it is loaded and quantized -- so the device holds the fp8 copy of every expert and nothing else (inference only: prefill runs
+        on the fp8 copies too, the module forward / training / saving raise)."""
+        if expert_weights not in ("bf16", "fp8", "fp8-only"):
+            raise ValueError(f"expert_weights must be 'bf16', 'fp8' or 'fp8-only' (got {expert_weights!r})")
         if not torch.cuda.is_available():
             raise RuntimeError("UniMoEAudio needs a ROCm device: the accelerated path has no CPU fallback")
         torch.cuda.set_device(device_id)
@@ -106,11 +108,19 @@ class UniMoEAudio:
                 if not model_path or not os.path.exists(os.path.join(model_path, "config.json")):
                     raise FileNotFoundError("model_path must contain the reference config.json (and the safetensors shards)")
                 cfg = UniMoEAudioConfig.from_json(os.path.join(model_path, "config.json"))
-            self.model = UniAudioRVQQwen2_5VLMoEForConditionalGeneration(cfg)
-            self._load_weights(model_path)
-            self.model = self.model.to(self.device, torch.bfloat16).eval()
+            if expert_weights == "fp8-only":
+                from . import checkpoint
+                # built on the device, each expert quantized and released as its tensors arrive: the bf16 experts are never all resident
+                self.model = checkpoint.from_pretrained(UniAudioRVQQwen2_5VLMoEForConditionalGeneration, model_path or "", device=self.device,
+                                                        config=cfg, expert_weights="fp8-only")
+            else:
+                self.model = UniAudioRVQQwen2_5VLMoEForConditionalGeneration(cfg)
+                self._load_weights(model_path)
+                self.model = self.model.to(self.device, torch.bfloat16).eval()
         if expert_weights == "fp8":
             self.model.quantize_experts_("fp8")
+        elif expert_weights == "fp8-only":
+            self.model.quantize_experts_("fp8", keep_bf16=False)      # (a model handed in; a loaded one is already there: idempotent)
         self._tokenizer = None
         self._dac = None
 

@@ -95,11 +95,25 @@ def iter_tensors(path: str, ep_rank: int = 0, ep_size: int = 1) -> Iterator[Tupl
 
 
 @torch.no_grad()
-def load_checkpoint(model: torch.nn.Module, path: str, ep_rank: int = 0, ep_size: int = 1, strict_hot: bool = True) -> Tuple[List[str], List[str]]:
+def load_checkpoint(model: torch.nn.Module, path: str, ep_rank: int = 0, ep_size: int = 1, strict_hot: bool = True,
+                    expert_weights: str = "bf16") -> Tuple[List[str], List[str]]:
     """Stream a reference checkpoint directory into `model` (parameters keep their device and dtype).
     Returns (missing, unexpected) like `load_state_dict(strict=False)`; with `strict_hot` a missing hot-path tensor is a KeyError
-    and a shape mismatch a ValueError.  Cold tensors (vision tower, lm_head) may be absent on either side."""
+    and a shape mismatch a ValueError.  Cold tensors (vision tower, lm_head) may be absent on either side.
+    expert_weights "fp8-only": an expert module is quantized and its bf16 parameters released (quant.quantize_expert_(keep_bf16=False)) as
+    soon as its three projections have arrived; parameters that were never allocated (dcmoe.unallocated_experts) are filled from the shard."""
+    from . import quant
+    if expert_weights not in ("bf16", "fp8-only"):
+        raise ValueError(f"load_checkpoint: expert_weights must be 'bf16' or 'fp8-only' (got {expert_weights!r})")
     target = dict(model.state_dict(keep_vars=True))
+    owner, arrived = {}, {}            # fp8-only: parameter key -> its expert module; module -> projections that have arrived
+    if expert_weights == "fp8-only":
+        names = {id(mod): mname for mname, mod in model.named_modules()}
+        for layer in model.language_model.layers:
+            routed, shared = quant.expert_modules(layer)
+            for mod in routed + shared:
+                for n in quant._PROJ:
+                    owner[f"{names[id(mod)]}.{n}.weight"] = mod
     n_experts = int(getattr(model.config, "mlp_dynamic_expert_num", 0))
     seen, unexpected = set(), []
     for raw, t in iter_tensors(path, ep_rank, ep_size):
@@ -113,10 +127,28 @@ def load_checkpoint(model: torch.nn.Module, path: str, ep_rank: int = 0, ep_size
         if dst is None:
             unexpected.append(key)
             continue
-        if tuple(dst.shape) != tuple(t.shape):
-            raise ValueError(f"{key}: checkpoint shape {tuple(t.shape)} != parameter shape {tuple(dst.shape)}")
-        dst.copy_(t.to(dst.dtype), non_blocking=False)     # (not `.data.copy_`: the in-place op must bump `_version`)
+        mod = owner.get(key)
+        want = getattr(mod, "_unallocated", {}).get(key.rsplit(".", 2)[1]) if mod is not None else None
+        if want is not None and dst.numel() == 0:          # an expert parameter that was never allocated: the shard's tensor becomes its storage
+            if tuple(want) != tuple(t.shape):
+                raise ValueError(f"{key}: checkpoint shape {tuple(t.shape)} != parameter shape {tuple(want)}")
+            dst.data = t.to(device=dst.device, dtype=dst.dtype).contiguous()
+        else:
+            if tuple(dst.shape) != tuple(t.shape):
+                raise ValueError(f"{key}: checkpoint shape {tuple(t.shape)} != parameter shape {tuple(dst.shape)}")
+            dst.copy_(t.to(dst.dtype), non_blocking=False)     # (not `.data.copy_`: the in-place op must bump `_version`)
         seen.add(key)
+        if mod is not None:
+            got = arrived.setdefault(mod, set())
+            got.add(key.rsplit(".", 2)[1])
+            if len(got) == len(quant._PROJ):               # the expert is complete: its fp8 copy, then its bf16 parameters go
+                quant.quantize_expert_(mod, keep_bf16=False)
+                mod.__dict__.pop("_unallocated", None)
+    if expert_weights == "fp8-only":
+        short = [k for k, mod in owner.items() if not quant.is_released(mod)]
+        if short:
+            raise KeyError(f"checkpoint {path!r} lacks expert tensors (fp8-only needs every expert complete), e.g. {short[:4]}")
+        model._expert_weights = "fp8-only"
     invalidate_packed(model)
     missing = [k for k in target if k not in seen]
     hot = [k for k in missing if not k.startswith(COLD_PREFIXES)]
@@ -252,10 +284,20 @@ def reshard_experts(path_in: str, path_out: str, n_experts: int, target_ep_size:
 
 
 def from_pretrained(cls, local_dir: str, torch_dtype=torch.bfloat16, attn_implementation: Optional[str] = None, device=None,
-                    ep_rank: int = 0, ep_size: int = 1, config=None):
+                    ep_rank: int = 0, ep_size: int = 1, config=None, expert_weights: str = "bf16"):
     """`Model.from_pretrained(local_dir, torch_dtype=bf16, attn_implementation="sdpa"|"eager")` of the reference
     (utils/UniMoE_Audio_mod.py:79-92) for LOCAL directories (the reference never passes anything else: UniMoE_Audio.py:24,60-65).
-    attn_implementation is accepted for signature compatibility: attention always runs on the HIP kernels."""
+    attn_implementation is accepted for signature compatibility: attention always runs on the HIP kernels.
+    expert_weights "fp8" quantizes the experts after loading (model.quantize_experts_); "fp8-only" builds the model WITHOUT storage for
+    the expert parameters and quantizes + releases each expert as soon as its three projections have arrived from the shards: all bf16
+    experts are never resident at once (the result equals loading followed by quantize_experts_(keep_bf16=False))."""
+    if expert_weights not in ("bf16", "fp8", "fp8-only"):
+        raise ValueError(f"expert_weights must be 'bf16', 'fp8' or 'fp8-only' (got {expert_weights!r})")
+    if expert_weights != "bf16" and ep_size != 1:
+        raise ValueError("fp8 expert weights are not supported expert parallel")
+    import contextlib
+    from . import dcmoe
+    lean = dcmoe.unallocated_experts() if expert_weights == "fp8-only" else contextlib.nullcontext()
     from .config import UniMoEAudioConfig
     if attn_implementation not in (None, "sdpa", "eager", "flash_attention_2"):
         raise ValueError(f"unknown attn_implementation {attn_implementation!r}")
@@ -271,12 +313,15 @@ def from_pretrained(cls, local_dir: str, torch_dtype=torch.bfloat16, attn_implem
     old = torch.get_default_dtype()
     torch.set_default_dtype(torch.bfloat16)
     try:
-        if device is not None:
-            with torch.device(device):
+        with lean:
+            if device is not None:
+                with torch.device(device):
+                    model = cls(config)
+            else:
                 model = cls(config)
-        else:
-            model = cls(config)
     finally:
         torch.set_default_dtype(old)
-    load_checkpoint(model, local_dir, ep_rank=ep_rank, ep_size=ep_size)
+    load_checkpoint(model, local_dir, ep_rank=ep_rank, ep_size=ep_size, expert_weights="fp8-only" if expert_weights == "fp8-only" else "bf16")
+    if expert_weights == "fp8":
+        model.quantize_experts_("fp8")
     return model.eval()

@@ -20,7 +20,10 @@ struct LayerDev {
     umoe_layer_weights w;
     std::vector<const uint16_t*> exp_gu, exp_dn, sh_gu, sh_dn;
     std::vector<const uint16_t*> rm_eg, rm_eu, rm_ed, rm_sg, rm_su, rm_sd;   // row-major copies (tiled prefill path)
-    bool has_rm = false;
+    bool has_rm = false;             // has_rm_attn && has_rm_exp
+    bool has_rm_attn = false;        // rm_qkv, rm_o: the attention GEMMs of a prefill of >= 64 rows run tiled
+    bool has_rm_exp = false;         // the row-major expert tensors: MOE_TILED on bf16 weights
+    bool exp_bf16 = true;            // the WP16 expert packs were given; false: an fp8-only layer (WP8 blocks and nothing else)
     bool set = false;
     // fp8 expert weights (umoe_engine_set_layer_fp8): WP8 blocks + per-row exponents, [n_real routed, then n_fix shared]
     std::vector<const uint16_t*> f8_gu, f8_dn;       // (WP8 addresses in the groups' `w` slots)
@@ -98,6 +101,7 @@ struct umoe_engine {
                                  // expert-parallel MoE half (umoe_engine_info; 1 was the removed box-grid launch)
     bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
+    int prefill_fp8 = 0;         // the last prefill / admission ran its experts on the WP8 blocks (umoe_engine_info "prefill_fp8")
     int expert_fp8 = 0;          // the last dense decode layer ran an fp8 launch: the flat one, or the wide form's (umoe_engine_info "expert_fp8")
     bool fp8_wide = false;       // umoe_engine_set_fp8_wide: decode steps of 17..64 rows of an fp8 engine take the wide form on the WP8 weights
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
@@ -420,12 +424,27 @@ extern "C" int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer
     UMOE_REQUIRE(e && w && layer >= 0 && layer < e->c.layers, "umoe_engine_set_layer: bad layer %d", layer);
     LayerDev& L = e->layers[layer];
     L.w = *w;
-    L.exp_gu.assign(w->exp_gu, w->exp_gu + e->E_loc);     // expert parallel: the LOCAL experts' packed weights only
-    L.exp_dn.assign(w->exp_dn, w->exp_dn + e->E_loc);
-    L.sh_gu.assign(w->sh_gu, w->sh_gu + e->c.n_fix);
-    L.sh_dn.assign(w->sh_dn, w->sh_dn + e->c.n_fix);
-    L.has_rm = w->rm_qkv && w->rm_o && w->rm_exp_gate && w->rm_exp_up && w->rm_exp_down &&
-               (e->c.n_fix == 0 || (w->rm_sh_gate && w->rm_sh_up && w->rm_sh_down));
+    // an fp8-only layer: no bf16 expert weight at all, neither the WP16 packs nor the row-major tensors (umoe_engine_set_layer_fp8
+    // follows with the WP8 blocks; every path that would stream a bf16 expert weight is refused, fp8_only_check)
+    const bool any_exp = w->exp_gu || w->exp_dn || w->sh_gu || w->sh_dn || w->rm_exp_gate || w->rm_exp_up || w->rm_exp_down || w->rm_sh_gate ||
+                         w->rm_sh_up || w->rm_sh_down;
+    L.exp_bf16 = any_exp;
+    if (any_exp) {
+        UMOE_REQUIRE(w->exp_gu && w->exp_dn && (e->c.n_fix == 0 || (w->sh_gu && w->sh_dn)),
+                     "umoe_engine_set_layer: layer %d: exp_gu / exp_dn / sh_gu / sh_dn go together (all NULL with every rm_exp_* / rm_sh_*: an fp8-only layer)", layer);
+        L.exp_gu.assign(w->exp_gu, w->exp_gu + e->E_loc);     // expert parallel: the LOCAL experts' packed weights only
+        L.exp_dn.assign(w->exp_dn, w->exp_dn + e->E_loc);
+        L.sh_gu.assign(w->sh_gu, w->sh_gu + e->c.n_fix);
+        L.sh_dn.assign(w->sh_dn, w->sh_dn + e->c.n_fix);
+    } else {
+        UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer: layer %d: an fp8-only layer (no bf16 expert weights) is not supported expert parallel", layer);
+        L.exp_gu.assign(e->E_loc, nullptr); L.exp_dn.assign(e->E_loc, nullptr);
+        L.sh_gu.assign(e->c.n_fix, nullptr); L.sh_dn.assign(e->c.n_fix, nullptr);
+    }
+    L.has_rm_attn = w->rm_qkv && w->rm_o;
+    L.has_rm_exp = w->rm_exp_gate && w->rm_exp_up && w->rm_exp_down && (e->c.n_fix == 0 || (w->rm_sh_gate && w->rm_sh_up && w->rm_sh_down));
+    L.has_rm = L.has_rm_attn && L.has_rm_exp;
+    L.rm_eg.clear(); L.rm_eu.clear(); L.rm_ed.clear(); L.rm_sg.clear(); L.rm_su.clear(); L.rm_sd.clear();
     if (L.has_rm) {
         L.rm_eg.assign(w->rm_exp_gate, w->rm_exp_gate + e->c.n_real);
         L.rm_eu.assign(w->rm_exp_up, w->rm_exp_up + e->c.n_real);
@@ -852,7 +871,12 @@ static int flat_wgs(const umoe_engine* e) { return e->n_cu < 256 ? e->n_cu : 256
 static MoeForm moe_form(const umoe_engine* e, const LayerDev& L, int n_tok) {
     const umoe_engine_cfg& c = e->c;
     if (wide_mode(e, n_tok)) return MOE_WIDE;
-    if (!dense_mode(e, n_tok)) return (L.has_rm && n_tok >= 64 && e->tiled_prefill && c.n_real + c.n_fix <= 12) ? MOE_TILED : MOE_RAGGED;
+    if (!dense_mode(e, n_tok)) {
+        // an fp8-only layer: the tiled kernel on the WP8 blocks at EVERY row count (nothing else reads e4m3 outside the decode launches;
+        // fp8_only_check refused UMOE_TILED_PREFILL=0 and more than 12 groups before anything was enqueued)
+        if (!L.exp_bf16) return MOE_TILED;
+        return (L.has_rm && n_tok >= 64 && e->tiled_prefill && c.n_real + c.n_fix <= 12) ? MOE_TILED : MOE_RAGGED;
+    }
     // the shapes the router riders are written for (router4_body<9, 2>; dense_mode: <= 16 rows)
     if (!(e->fuse_router && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096))) return MOE_ROUTER;
     const int n_wg = flat_wgs(e);
@@ -875,13 +899,20 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     const umoe_engine_cfg& c = e->c;
     const int D = c.hidden, G = c.n_real + c.n_fix, Imax = c.inter_dyn > c.inter_shared ? c.inter_dyn : c.inter_shared;
     int rc;
+    const bool f8 = !L.exp_bf16;     // an fp8-only layer: the same two launches on the WP8 blocks (umoe_tiled_gemm_wp8), [routed, then shared]
+    const uint8_t* w8[12];
+    const int8_t* ex[12];
     umoe_tgroup_t tg[12];
     memset(tg, 0, sizeof(tg));
     for (int x = 0; x < G; ++x) {
         const umoe_group_t& src = gu_groups[x];
         const bool sh = x >= c.n_real;
-        tg[x].w = sh ? L.rm_sg[x - c.n_real] : L.rm_eg[x];
-        tg[x].w2 = sh ? L.rm_su[x - c.n_real] : L.rm_eu[x];
+        if (f8) {
+            w8[x] = reinterpret_cast<const uint8_t*>(L.f8_gu[x]); ex[x] = L.f8e_gu[x];
+        } else {
+            tg[x].w = sh ? L.rm_sg[x - c.n_real] : L.rm_eg[x];
+            tg[x].w2 = sh ? L.rm_su[x - c.n_real] : L.rm_eu[x];
+        }
         tg[x].rows = src.rows; tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
         tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
         tg[x].n = sh ? c.inter_shared : c.inter_dyn; tg[x].k = D; tg[x].ldw = D;
@@ -889,13 +920,17 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     umoe_tgemm_args ta{};
     ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok; ta.a = e->h2; ta.lda = D; ta.out = e->hbuf; ta.ldo = Imax;
     ta.epilogue = UMOE_EPI_SWIGLU;
-    if ((rc = umoe_tiled_gemm(&ta, s))) return rc;
+    if ((rc = f8 ? umoe_tiled_gemm_wp8(&ta, w8, ex, s) : umoe_tiled_gemm(&ta, s))) return rc;
     PROF(K_GATEUP);
     memset(tg, 0, sizeof(tg));
     for (int x = 0; x < G; ++x) {
         const umoe_group_t& src = gu_groups[G + x];
         const bool sh = x >= c.n_real;
-        tg[x].w = sh ? L.rm_sd[x - c.n_real] : L.rm_ed[x];
+        if (f8) {
+            w8[x] = reinterpret_cast<const uint8_t*>(L.f8_dn[x]); ex[x] = L.f8e_dn[x];
+        } else {
+            tg[x].w = sh ? L.rm_sd[x - c.n_real] : L.rm_ed[x];
+        }
         tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
         tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
         tg[x].n = D; tg[x].k = sh ? c.inter_shared : c.inter_dyn; tg[x].ldw = tg[x].k;
@@ -903,8 +938,9 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     umoe_tgemm_args td{};
     td.groups = tg; td.num_groups = G; td.max_rows = n_tok; td.a = e->hbuf; td.lda = Imax; td.out = e->ybuf; td.ldo = D;
     td.epilogue = UMOE_EPI_BF16;
-    if ((rc = umoe_tiled_gemm(&td, s))) return rc;
+    if ((rc = f8 ? umoe_tiled_gemm_wp8(&td, w8, ex, s) : umoe_tiled_gemm(&td, s))) return rc;
     PROF(K_DOWN);
+    if (f8) e->prefill_fp8 = 1;
     return 0;
 }
 
@@ -983,7 +1019,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     PROF(-1);
     // many rows (prefill): the compute-bound tiled MFMA kernel on the row-major weights; decode: weight streaming
     const bool wide = wide_mode(e, n_tok);
-    const bool tiled = !wide && L.has_rm && n_tok >= 64 && e->tiled_prefill;
+    const bool tiled = !wide && (L.exp_bf16 ? L.has_rm : L.has_rm_attn) && n_tok >= 64 && e->tiled_prefill;     // (an fp8-only layer has no rm_exp_*)
     if (wide) {
         rc = wide_dense(e, e->hin, D, L.w.qkv_w, QKV / 16, L.w.qkv_b, nullptr, e->qkv, QKV, QKV, UMOE_EPI_BF16, 16, n_tok, s);
     } else if (tiled) {
@@ -1076,6 +1112,8 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
         e->row_tiles = 1;
     }
     UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT && form != MOE_WIDE), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
+    UMOE_REQUIRE(L.exp_bf16 || (L.has_f8 && (form == MOE_TILED || form == MOE_FLAT || form == MOE_WIDE)),
+                 "umoe_engine: layer %d holds no bf16 expert weights (fp8-only) and this pass would stream them", l);
     umoe_router_args ra{};
     ra.x = e->x1; ra.gate_w = L.w.gate_w; ra.norm_w = L.w.post_norm; ra.h_out = e->h2; ra.S = n_tok; ra.D = D;
     ra.n_dyn = c.n_dyn; ra.n_real = c.n_real; ra.n_fix = c.n_fix; ra.logits_bf16 = 1; ra.top_p = c.top_p;
@@ -1247,6 +1285,7 @@ static int prefill_state(umoe_engine* e, const uint8_t* valid_host, int T, const
 }
 
 static int fp8_step_check(umoe_engine* e);
+static int fp8_only_check(umoe_engine* e, int prefill_tok);
 
 extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const uint8_t* valid_host, int T, const int32_t* pos3_host,
                                        const int32_t* next_pos_host, umoe_stream_t stream) {
@@ -1264,6 +1303,8 @@ extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const 
     int rc;
     // a one-token prompt takes the dense decode layout, i.e. the fp8 flat launch on an fp8 engine: refused up front like a decode step
     if (e->fp8 && dense_mode(e, n_tok) && (rc = fp8_step_check(e))) return rc;
+    if ((rc = fp8_only_check(e, dense_mode(e, n_tok) ? 0 : n_tok))) return rc;
+    e->prefill_fp8 = 0;
     if ((rc = ensure_workspace(e, n_tok))) return rc;
     if ((rc = build_groups(e, n_tok, s))) return rc;
     if ((rc = prefill_state(e, valid_host, T, pos3_host, next_pos_host, s))) return rc;
@@ -1481,6 +1522,8 @@ extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b
     const umoe_engine_cfg& c = e->c;
     hipStream_t s = (hipStream_t)stream;
     const int n_tok = 2 * T;
+    if ((rc = fp8_only_check(e, n_tok))) return rc;       // (an admission prefill is never the dense layout)
+    e->prefill_fp8 = 0;
     // positions cumsum(mask) - 1, masked -> 1; kv slot = t (prefill_state, for the pair)
     std::vector<int32_t> pos((size_t)3 * n_tok), kvp(n_tok);
     for (int r = 0; r < 2; ++r) {
@@ -1531,7 +1574,45 @@ extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* 
 // An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch (moe_form: MOE_FLAT) or, with the
 // switch umoe_engine_set_fp8_wide, the wide form on the WP8 weights (17..64 rows): the launch-per-kernel forms would stream bf16 expert
 // weights it does not run on.  Checked on the host before anything is enqueued.
+// An engine with fp8-only layers (umoe_engine_set_layer without any bf16 expert weight) holds its experts as WP8 blocks and nothing else:
+// every pass that would stream a bf16 expert weight is refused HERE, on the host, before anything is enqueued, with a message that names
+// the missing weights.  prefill_tok > 0: a prefill / admission of that many tokens outside the dense layout (MOE_TILED on the WP8 blocks,
+// umoe_tiled_gemm_wp8, at every row count -- MOE_RAGGED streams WP16); 0: a pass in the dense decode layout (fp8_step_check's rules, with
+// the launch-per-kernel forms MOE_RIDERS / MOE_ROUTER and the bf16 wide form named as what they are here).
+#define FP8_ONLY_MISSING "this engine holds no bf16 expert weights (fp8-only: exp_gu / exp_dn / sh_gu / sh_dn and rm_exp_* / rm_sh_* were not given)"
+static bool fp8_only(const umoe_engine* e) {
+    for (const LayerDev& L : e->layers)
+        if (L.set && !L.exp_bf16) return true;
+    return false;
+}
+static int fp8_only_check(umoe_engine* e, int prefill_tok) {
+    if (!fp8_only(e)) return 0;
+    const umoe_engine_cfg& c = e->c;
+    UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: " FP8_ONLY_MISSING ": not supported expert parallel (ep_size %d)", c.ep_size);
+    for (int l = 0; l < c.layers; ++l)
+        UMOE_REQUIRE(!e->layers[l].set || e->layers[l].exp_bf16 || e->layers[l].has_f8,
+                     "umoe_engine: layer %d has no expert weights at all: " FP8_ONLY_MISSING " and umoe_engine_set_layer_fp8 was not called", l);
+    if (prefill_tok > 0) {
+        UMOE_REQUIRE(e->tiled_prefill, "umoe_engine: UMOE_TILED_PREFILL=0 runs the experts of a prefill on the weight-streaming GEMM (MOE_RAGGED) over WP16 packs, and "
+                                       FP8_ONLY_MISSING);
+        UMOE_REQUIRE(c.n_real + c.n_fix <= 12, "umoe_engine: a prefill of %d experts per layer takes MOE_RAGGED over WP16 packs (the tiled launch has 12 groups), and "
+                                               FP8_ONLY_MISSING, c.n_real + c.n_fix);
+        UMOE_REQUIRE(c.hidden % 32 == 0 && c.inter_dyn % 32 == 0 && (c.n_fix == 0 || c.inter_shared % 32 == 0),
+                     "umoe_engine: the tiled GEMM on WP8 weights needs hidden and intermediate sizes that are multiples of 32 (%d, %d, %d), and " FP8_ONLY_MISSING,
+                     c.hidden, c.inter_dyn, c.inter_shared);
+        return 0;
+    }
+    if (e->fp8_wide && fp8_wide_on() && wide_shapes(e, c.rows)) return 0;      // the wide form on the WP8 weights
+    UMOE_REQUIRE(!wide_shapes(e, c.rows), "umoe_engine: a decode step of %d rows without the fp8 wide form (umoe_engine_set_fp8_wide, UMOE_WIDE_DECODE) takes the bf16 "
+                                          "wide form or MOE_RAGGED, and " FP8_ONLY_MISSING, c.rows);
+    UMOE_REQUIRE(flat_moe_on(), "umoe_engine: UMOE_FLAT_MOE=0 selects the launch-per-kernel forms (MOE_RIDERS / MOE_ROUTER) over WP16 packs, and " FP8_ONLY_MISSING);
+    UMOE_REQUIRE(e->fuse_router, "umoe_engine: UMOE_FUSE_ROUTER=0 selects the launch-per-kernel form MOE_ROUTER over WP16 packs, and " FP8_ONLY_MISSING);
+    UMOE_REQUIRE(dense_mode(e, c.rows), "umoe_engine: a decode step of %d rows outside the dense layout takes MOE_RAGGED over WP16 packs, and " FP8_ONLY_MISSING, c.rows);
+    return 0;
+}
+
 static int fp8_step_check(umoe_engine* e) {
+    if (int rc = fp8_only_check(e, 0)) return rc;
     if (!e->fp8) return 0;
     const umoe_engine_cfg& c = e->c;
     UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: fp8 expert weights are not supported expert parallel (ep_size %d)", c.ep_size);
@@ -1616,6 +1697,8 @@ extern "C" int umoe_engine_info(umoe_engine* e, const char* key) {
     if (!strcmp(key, "expert_launch")) return e->expert_launch;
     if (!strcmp(key, "row_tiles")) return e->expert_launch == 4 ? e->row_tiles : 1;
     if (!strcmp(key, "expert_fp8")) return e->expert_fp8;
+    if (!strcmp(key, "prefill_fp8")) return e->prefill_fp8;
+    if (!strcmp(key, "expert_bf16_resident")) return fp8_only(e) ? 0 : 1;
     if (!strcmp(key, "n_cu")) return e->n_cu;
     return -1;
 }

@@ -14,6 +14,7 @@ no CPU implementation here: CPU tensors raise.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
@@ -21,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ep as EP
-from . import ops
+from . import ops, quant
 
 
 class _SwiGLUMLP(nn.Module):
@@ -32,6 +33,26 @@ class _SwiGLUMLP(nn.Module):
         self.gate_proj = nn.Linear(hidden_size, intermediate_size, bias=False)
         self.up_proj = nn.Linear(hidden_size, intermediate_size, bias=False)
         self.down_proj = nn.Linear(intermediate_size, hidden_size, bias=False)
+        if _UNALLOCATED[0]:      # unallocated_experts(): each weight's storage goes as soon as it exists; the loader brings the real one
+            self._unallocated = {}
+            for n in ("gate_proj", "up_proj", "down_proj"):
+                p = getattr(self, n).weight
+                self._unallocated[n] = tuple(p.shape)
+                p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+
+
+_UNALLOCATED = [False]
+
+
+@contextlib.contextmanager
+def unallocated_experts():
+    """Expert MLPs constructed inside keep no storage for their three weights (shapes in `_unallocated`): the way
+    checkpoint.from_pretrained(expert_weights="fp8-only") builds a model whose bf16 experts are never all resident."""
+    old, _UNALLOCATED[0] = _UNALLOCATED[0], True
+    try:
+        yield
+    finally:
+        _UNALLOCATED[0] = old
 
 
 class AudioSharedExpertMLP(_SwiGLUMLP):
@@ -138,6 +159,10 @@ class UniMoEAudioSparseMoeBlock(nn.Module):
         if self._packed is not None and key == self._packed_key:
             return self._packed
         ex, sh = self._experts(), self.fixed_real_moe
+        if quant.is_released(self):
+            # fp8-only: there is no bf16 expert weight to pack -- the decode engine reads the WP8 copies (quant.py), the forward refuses
+            self._packed, self._packed_key = dict(exp_gu=[], exp_dn=[], sh_gu=[], sh_dn=[], released=True), key
+            return self._packed
         for p in self.parameters():
             if p.dtype != torch.bfloat16 or not p.is_cuda:
                 raise L.UmoeError("UniMoEAudioSparseMoeBlock runs on the HIP path only: parameters must be bf16 on a ROCm "
@@ -186,6 +211,8 @@ class UniMoEAudioSparseMoeBlock(nn.Module):
     # ---- forward ------------------------------------------------------------------------------------------
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 aux_balance_weight: Optional[torch.Tensor] = None):
+        if quant.is_released(self):
+            raise L.UmoeError(quant._released_msg("UniMoEAudioSparseMoeBlock.forward"))
         if not hidden_states.is_cuda:
             raise L.UmoeError("UniMoEAudioSparseMoeBlock.forward needs device tensors; the CPU restatement lives in "
                               "oracle/ and is test infrastructure only")

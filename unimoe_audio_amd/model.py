@@ -118,11 +118,12 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
 
     @classmethod
     def from_pretrained(cls, local_dir: str, torch_dtype=torch.bfloat16, attn_implementation: Optional[str] = None, device=None,
-                        ep_rank: int = 0, ep_size: int = 1, config=None):
-        """Reference signature (utils/UniMoE_Audio_mod.py:79-92) for local checkpoint directories; see checkpoint.py."""
+                        ep_rank: int = 0, ep_size: int = 1, config=None, expert_weights: str = "bf16"):
+        """Reference signature (utils/UniMoE_Audio_mod.py:79-92) for local checkpoint directories; see checkpoint.py.
+        expert_weights (not in the reference): "fp8" / "fp8-only" quantize the experts while loading."""
         from . import checkpoint
         return checkpoint.from_pretrained(cls, local_dir, torch_dtype=torch_dtype, attn_implementation=attn_implementation,
-                                          device=device, ep_rank=ep_rank, ep_size=ep_size, config=config)
+                                          device=device, ep_rank=ep_rank, ep_size=ep_size, config=config, expert_weights=expert_weights)
 
     @torch.no_grad()
     def init_synthetic(self, seed: int = 1234, std: Optional[float] = None):
@@ -227,6 +228,8 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
                      aux_balance_weight: Optional[torch.Tensor] = None, output_router_logits_and_topk: bool = False, kv_sink=None):
         """kv_sink(layer, k [B, KVH, T, hd], v): called with every layer's roped keys / values (the buffers are reused by the next layer:
         copy what you keep) -- how an expert-parallel engine that holds only its local experts gets its KV cache from this forward."""
+        if quant.is_released(self.language_model):
+            raise L.UmoeError(quant._released_msg("the module forward"))
         cfg, dev = self.config, inputs_embeds.device
         B, T, D = inputs_embeds.shape
         H, KVH, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -358,13 +361,14 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
                expert_weights: Optional[str] = None) -> "DecodeEngine":
         """The decode engine for this shape, rebuilt when the shape, the weights (data pointer / version of any parameter) or the
         expert-parallel link changed.  `ep`: an unimoe_audio_amd.ep.EpLink (every rank of the link calls this together).
-        `expert_weights` "bf16" / "fp8" (None: "fp8" when quantize_experts_('fp8') ran on this model, else "bf16").  An fp8 engine built
-        here decodes batches of 9 to 32 requests in the wide form on the fp8 weights (DecodeEngine fp8_wide=True)."""
+        `expert_weights` "bf16" / "fp8" / "fp8-only" (None: what quantize_experts_ left on this model, else "bf16").  An fp8 engine built
+        here decodes batches of 9 to 32 requests in the wide form on the fp8 weights (DecodeEngine fp8_wide=True).  "fp8-only": the
+        engine holds the fp8 copy of every expert and nothing else -- its prefill runs on them too."""
         need_L = max_prompt + max_tokens + 8
         e = self._engine
         key = self._pack_key()
-        fmt = expert_weights or ("fp8" if quant.is_quantized(self) else "bf16")
-        fp8_wide = fmt == "fp8"
+        fmt = expert_weights or quant.expert_format(self)
+        fp8_wide = fmt in ("fp8", "fp8-only")
         if (e is None or e.batch != batch or e.Lmax < need_L or e.Tmax < max_tokens + 64 or e.pack_key != key or e.ep is not ep
                 or e.expert_weights != fmt or e.fp8_wide != fp8_wide):
             if e is not None:
@@ -373,11 +377,13 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
                                         fp8_wide=fp8_wide)
         return self._engine
 
-    def quantize_experts_(self, fmt: str = "fp8"):
+    def quantize_experts_(self, fmt: str = "fp8", keep_bf16: bool = True):
         """Weight-only fp8 of the routed and shared experts (unimoe_audio_amd/quant.py): the parameters become their dequantized
         values W_deq in place; decode engines built afterwards stream the e4m3 copies (half the expert bytes): the flat expert launch
-        up to 8 requests, the wide step's gate/up and down launches for 9 to 32."""
-        return quant.quantize_experts_(self, fmt)
+        up to 8 requests, the wide step's gate/up and down launches for 9 to 32.  keep_bf16=False: the bf16 expert parameters are
+        released (inference only: engines built afterwards are "fp8-only" and prefill on the e4m3 copies; quant.dequantize_experts_
+        brings the parameters back)."""
+        return quant.quantize_experts_(self, fmt, keep_bf16=keep_bf16)
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, dec_output: DecoderOutput, max_tokens, min_tokens=None,
@@ -512,10 +518,12 @@ class DecodeEngine:
         """fp8_wide: an fp8 engine of 9 to 32 requests decodes in the wide form with the gate/up and down launches on the fp8 weights
         (umoe_engine_set_fp8_wide).  False (default): such an engine refuses its decode step, as it always did; model.engine() passes True."""
         cfg = model.config
-        fmt = expert_weights or ("fp8" if quant.is_quantized(model) else "bf16")
-        if fmt not in ("bf16", "fp8"):
-            raise L.UmoeError(f"expert_weights must be 'bf16' or 'fp8' (got {fmt!r})")
-        if fmt == "fp8":
+        fmt = expert_weights or quant.expert_format(model)
+        if fmt not in ("bf16", "fp8", "fp8-only"):
+            raise L.UmoeError(f"expert_weights must be 'bf16', 'fp8' or 'fp8-only' (got {fmt!r})")
+        if fmt != "fp8-only" and quant.is_released(model):
+            raise L.UmoeError(quant._released_msg(f"DecodeEngine(expert_weights={fmt!r})"))
+        if fmt in ("fp8", "fp8-only"):
             if ep is not None and ep.size > 1:
                 raise L.UmoeError("fp8 expert weights run on the flat expert launch only: not with expert parallel decode")
             quant.check_quantized(model)      # refuses stale fp8 copies (a weight edited after quantize_experts_)
@@ -587,23 +595,28 @@ class DecodeEngine:
                 raise L.UmoeError(f"the model holds {len(ex)} routed experts per layer: expected {n_real} (replicated) or {e_loc} (sharded for ep_size {self.ep_size})")
             self.sharded = sharded
             lo = 0 if sharded else self.ep_rank * e_loc
-            eg, ed = arr(pk["exp_gu"][lo:lo + e_loc]), arr(pk["exp_dn"][lo:lo + e_loc])
-            sg, sd = arr(pk["sh_gu"]), arr(pk["sh_dn"])
+            only = self.expert_weights == "fp8-only"     # no bf16 expert weight goes to the engine: NULL for the WP16 packs and the rm_* tensors
+            eg = ed = sg = sd = None
+            if not only:
+                eg, ed = arr(pk["exp_gu"][lo:lo + e_loc]), arr(pk["exp_dn"][lo:lo + e_loc])
+                sg, sd = arr(pk["sh_gu"]), arr(pk["sh_dn"])
             rm = [p for mods in (ex, sh) for m_ in mods for p in (m_.gate_proj.weight, m_.up_proj.weight, m_.down_proj.weight)]
             if not all(p.is_contiguous() for p in rm + [layer.self_attn.o_proj.weight]):
                 raise L.UmoeError("engine weights must be contiguous")
-            if sharded:
+            if sharded or only:
                 reg = reu = red = None
             else:
                 reg, reu, red = arr([m_.gate_proj.weight for m_ in ex]), arr([m_.up_proj.weight for m_ in ex]), arr([m_.down_proj.weight for m_ in ex])
-            rsg, rsu, rsd = arr([m_.gate_proj.weight for m_ in sh]), arr([m_.up_proj.weight for m_ in sh]), arr([m_.down_proj.weight for m_ in sh])
+            rsg = rsu = rsd = None
+            if not only:
+                rsg, rsu, rsd = arr([m_.gate_proj.weight for m_ in sh]), arr([m_.up_proj.weight for m_ in sh]), arr([m_.down_proj.weight for m_ in sh])
             w = L.LayerWeights(in_norm=layer.input_layernorm.weight.data_ptr(), qkv_w=qkv_w.data_ptr(), qkv_b=qkv_b.data_ptr(),
                                o_w=o_w.data_ptr(), post_norm=layer.post_attention_layernorm.weight.data_ptr(),
                                gate_w=layer.mlp.gate.weight.data_ptr(), exp_gu=eg, exp_dn=ed, sh_gu=sg, sh_dn=sd,
                                rm_qkv=lp["qkv_rm"].data_ptr(), rm_o=layer.self_attn.o_proj.weight.data_ptr(),
                                rm_exp_gate=reg, rm_exp_up=reu, rm_exp_down=red, rm_sh_gate=rsg, rm_sh_up=rsu, rm_sh_down=rsd)
             L.check(lib.umoe_engine_set_layer(self.h, li, C.byref(w)), "umoe_engine_set_layer")
-            if self.expert_weights == "fp8":
+            if self.expert_weights in ("fp8", "fp8-only"):
                 self._set_layer_fp8(li, ex, sh)
         emb, head = mpk["emb"], mpk["head"]
         # (slack: the temporal stream of a video advances by seconds-per-grid * tokens_per_second per frame pair, model.py:597-603)

@@ -587,6 +587,31 @@ def tiled_gemm(groups: Sequence[dict], a: torch.Tensor, out: torch.Tensor, *, ma
     return out
 
 
+def tiled_gemm_wp8(groups: Sequence[dict], a: torch.Tensor, out: torch.Tensor, *, max_rows: int, epilogue=EPI_BF16):
+    """umoe_tiled_gemm_wp8: tiled_gemm on WP8 weights.  Each group dict has w8 (uint8 WP8 blocks; SwiGLU: the interleaved gate/up pair) and
+    exps (int8, 16 per block) from quant.pack_wp8 / pack_wp8_gate_up, n and k, optional rows / row_off / count tensors and static_count /
+    a_row_base / out_row_base / a_col_off / out_col_off ints.  Bit-identical to tiled_gemm's small-tile kernel on the dequantized weights."""
+    G = len(groups)
+    arr = (L.TGroup * G)()
+    keep = []
+    for i, g in enumerate(groups):
+        for k in ("rows", "row_off", "count"):
+            t = g.get(k)
+            if t is not None:
+                keep.append(t)
+                setattr(arr[i], k, t.data_ptr())
+        for k in ("static_count", "a_row_base", "out_row_base", "a_col_off", "out_col_off"):
+            setattr(arr[i], k, int(g.get(k, 0)))
+        arr[i].n, arr[i].k = int(g["n"]), int(g["k"])
+        assert g["w8"].dtype == torch.uint8 and g["exps"].dtype == torch.int8
+    w8 = (C.c_void_p * G)(*[g["w8"].data_ptr() for g in groups])
+    ex = (C.c_void_p * G)(*[g["exps"].data_ptr() for g in groups])
+    args = L.TGemmArgs(groups=C.cast(arr, C.c_void_p), num_groups=G, max_rows=max_rows, a=_pv(a), lda=a.stride(0), resid=None, out=_pv(out),
+                       ldo=out.stride(-2), epilogue=epilogue, aux_out=None, ld_aux=0)
+    L.check(L.lib().umoe_tiled_gemm_wp8(C.byref(args), w8, ex, _stream()), "umoe_tiled_gemm_wp8")
+    return out
+
+
 def tiled_gemm_tn(groups: Sequence[dict], p: torch.Tensor, q: torch.Tensor, out: torch.Tensor, *, k_split: int = 1):
     """out_g[m][n] = sum_k p[k][p_col_off + m] * q[k][q_col_off + n] over the group's row window (umoe_tiled_gemm_tn): the weight-gradient
     product dW = dY^T X on row-major activations, no transposed copies.  Group dict: m, n, optional p / q / out tensors of its own,

@@ -7,6 +7,11 @@ quantized model IS an ordinary bf16 model with weights W_deq = q * 2^e.  quantiz
 so prefill, the module-level forward and training run the unchanged bf16 kernels on the numbers the fp8 decode launch
 (moe_flat_fp8_kernel) converts to -- its outputs are bit-identical to the bf16 engine run on W_deq.
 
+fp8-only (quantize_experts_(keep_bf16=False)): the expert parameters are RELEASED once their WP8 copy exists (`p.data` becomes an
+empty tensor, shapes stay in `_fp8["shape"]`), and an engine built on such a model holds the WP8 copy of every expert and nothing else:
+its prefill runs the tiled GEMM on the e4m3 blocks (umoe_tiled_gemm_wp8).  The module forward, training and state_dict saving of such a
+model raise; dequantize_experts_ restores W_deq exactly.
+
 Load-time only (torch ops, CPU or GPU): not a hot path.  WP8 layout: include/umoe.h.
 """
 from typing import Tuple
@@ -88,27 +93,112 @@ def expert_modules(layer):
     return list(layer.mlp.dynamic_real_moe.deepspeed_moe.experts.deepspeed_experts), list(layer.mlp.fixed_real_moe)
 
 
+def _released_msg(what: str) -> str:
+    return (f"{what}: this model holds its expert weights as fp8 only (quantize_experts_(keep_bf16=False) released the bf16 parameters); "
+            "the decode engine runs on them (expert_weights='fp8-only') -- call unimoe_audio_amd.quant.dequantize_experts_(model) to get "
+            "the bf16 parameters back (exact: W_deq)")
+
+
+def _refuse_state_dict(module, prefix, keep_vars):
+    from . import _lib as L
+    raise L.UmoeError(_released_msg(f"state_dict of {prefix or 'an expert'}"))
+
+
+def _release(m):
+    """Drops the three bf16 parameters of a quantized expert module (the WP8 copy stays) and makes saving it an error."""
+    for name in _PROJ:
+        p = getattr(m, name).weight
+        p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+    m._fp8["released"] = True
+    if m._fp8.get("hook") is None:
+        m._fp8["hook"] = m.register_state_dict_pre_hook(_refuse_state_dict)
+
+
+def is_released(m) -> bool:
+    """True for an expert module (or a DCMoE block / a model holding one) whose bf16 parameters were released."""
+    st = getattr(m, "_fp8", None)
+    if st is not None:
+        return bool(st.get("released"))
+    return any(bool(getattr(x, "_fp8", None) and x._fp8.get("released")) for x in m.modules())
+
+
 @torch.no_grad()
-def quantize_experts_(model, fmt: str = "fp8"):
+def quantize_expert_(m, keep_bf16: bool = True):
+    """One expert module (gate_proj / up_proj / down_proj): the e4m3 copy in WP8 layout on `m._fp8`; the parameters become W_deq, or,
+    with keep_bf16=False, are released as soon as the copy exists."""
+    if is_released(m):
+        if keep_bf16:
+            from . import _lib as L
+            raise L.UmoeError(_released_msg("quantize_experts_(keep_bf16=True)"))
+        return m
+    qe, ver = {}, {}
+    for name in _PROJ:
+        p = getattr(m, name).weight
+        q, e = quantize_fp8_rows(p)
+        if keep_bf16:
+            p.copy_(dequantize_fp8_rows(q, e).to(p.dtype))
+        qe[name] = (q.to(p.device), e.to(p.device))
+        ver[name] = (p._version, p.data_ptr())
+    m._fp8 = dict(gu=pack_wp8_gate_up(*qe["gate_proj"], *qe["up_proj"]), dn=pack_wp8(*qe["down_proj"]), ver=ver,
+                  shape={n: tuple(getattr(m, n).weight.shape) for n in _PROJ}, released=False, hook=None)
+    if not keep_bf16:
+        _release(m)
+    return m
+
+
+@torch.no_grad()
+def quantize_experts_(model, fmt: str = "fp8", keep_bf16: bool = True):
     """Quantizes the gate / up / down weights of the routed AND shared experts of every layer in place: each parameter becomes W_deq.
     The e4m3 copies are kept on the expert module ONCE, already in the engine's WP8 layout (`_fp8["gu"]` gate/up interleaved, `_fp8["dn"]`:
     (packed, exponents)), with every parameter's version (a later change is detected by check_quantized).  Router gate, attention, codec
-    head and embeddings stay bf16.  Idempotent."""
+    head and embeddings stay bf16.  Idempotent.
+    keep_bf16=False: each expert's three parameters are released as soon as its WP8 copy exists (the peak is ONE expert's bf16) and
+    model._expert_weights becomes "fp8-only": the decode engine runs on the WP8 copies alone, everything else that needs the bf16
+    parameters raises (dequantize_experts_ restores them)."""
     if fmt != "fp8":
         raise ValueError(f"quantize_experts_: unknown format {fmt!r} (only 'fp8')")
     for layer in model.language_model.layers:
         routed, shared = expert_modules(layer)
         for m in routed + shared:
-            qe, ver = {}, {}
+            quantize_expert_(m, keep_bf16)
+    model._expert_weights = "fp8" if keep_bf16 else "fp8-only"
+    if not keep_bf16:
+        _drop_packs(model)
+    return model
+
+
+def _drop_packs(model):
+    """The WP16 packs (model.packed(), each block's prepare()) and an engine built on them hold the bytes the release is about."""
+    from .checkpoint import invalidate_packed
+    invalidate_packed(model)
+
+
+@torch.no_grad()
+def dequantize_experts_(model):
+    """Restores W_deq = q * 2^e into every expert parameter from its WP8 copy (exact), released or not: an fp8-only model becomes the
+    model quantize_experts_(keep_bf16=True) leaves -- forward, training, saving and bf16 / fp8 engines work again."""
+    for layer in model.language_model.layers:
+        routed, shared = expert_modules(layer)
+        for m in routed + shared:
+            st = getattr(m, "_fp8", None)
+            if st is None:
+                from . import _lib as L
+                raise L.UmoeError("dequantize_experts_: an expert has no fp8 weights (quantize_experts_ first)")
             for name in _PROJ:
                 p = getattr(m, name).weight
-                q, e = quantize_fp8_rows(p)
-                p.copy_(dequantize_fp8_rows(q, e).to(p.dtype))
-                qe[name] = (q.to(p.device), e.to(p.device))
-                ver[name] = (p._version, p.data_ptr())
-            m._fp8 = dict(gu=pack_wp8_gate_up(*qe["gate_proj"], *qe["up_proj"]), dn=pack_wp8(*qe["down_proj"]), ver=ver,
-                          shape={n: tuple(getattr(m, n).weight.shape) for n in _PROJ})
+                q, e = expert_qe(m, name)
+                w = dequantize_fp8_rows(q, e).to(device=p.device, dtype=p.dtype)
+                if tuple(p.shape) == tuple(w.shape):
+                    p.copy_(w)
+                else:
+                    p.data = w.contiguous()
+                st["ver"][name] = (p._version, p.data_ptr())
+            st["released"] = False
+            if st.get("hook") is not None:
+                st["hook"].remove()
+                st["hook"] = None
     model._expert_weights = "fp8"
+    _drop_packs(model)
     return model
 
 
@@ -124,8 +214,13 @@ def expert_qe(m, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
     return unpack_wp8(packed.view(NB, 2, -1)[:, half].reshape(-1), ex.view(NB, 2, 16)[:, half].reshape(-1), N, K)
 
 
+def expert_format(model) -> str:
+    """"bf16", "fp8" (quantized, bf16 parameters kept as W_deq) or "fp8-only" (quantized, bf16 parameters released)."""
+    return getattr(model, "_expert_weights", "bf16")
+
+
 def is_quantized(model) -> bool:
-    return getattr(model, "_expert_weights", "bf16") == "fp8"
+    return expert_format(model) in ("fp8", "fp8-only")
 
 
 def check_quantized(model):
@@ -138,6 +233,8 @@ def check_quantized(model):
             store = getattr(m, "_fp8", None)
             if store is None:
                 raise L.UmoeError(f"layer {li} expert {xi} has no fp8 weights: call quantize_experts_('fp8')")
+            if store.get("released"):
+                continue               # no bf16 parameter that could differ from the fp8 copy
             for name in _PROJ:
                 p = getattr(m, name).weight
                 ver, ptr = store["ver"][name]
