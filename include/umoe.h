@@ -415,7 +415,7 @@ int umoe_transpose_slots_compact(const uint16_t* src, int ld_src, int C, const i
 /* SwiGLU backward, core.py:31,49: gu [rows][2I] = (gate | up) pre-activations saved by the forward
  * (umoe_tgemm_args.aux_out), dh [rows][I] -> dgu [rows][2I] = (dgate | dup).  total_rows: device scalar or NULL. */
 /* y[i] = bf16(float(x[i]) * noise[i]): the training-time input jitter on the gate's copy of the rows (core.py:240-244: the reference
- * multiplies a float copy and casts back) in one pass instead of three elementwise launches.  n % 8 == 0. */
+ * multiplies a float copy and casts back) in one pass instead of three elementwise launches.  n % 8 == 0; n == 0: the pointers may be null. */
 int umoe_mul_noise(const uint16_t* x, const float* noise, long n, uint16_t* y, umoe_stream_t stream);
 int umoe_swiglu_bwd(const uint16_t* dh, int ld_dh, const uint16_t* gu, int ld_gu, int I, const int32_t* total_rows,
                     int max_rows, uint16_t* dgu, int ld_dgu, umoe_stream_t stream);
@@ -598,12 +598,13 @@ int umoe_attn_prefill_fwd(const umoe_attn_args* a, umoe_stream_t stream);
 
 /* ------------------------------------------------------------------ codec side
  * codec_embedding (model.py:655-661): out[r] = sum_c Emb_c[tok[r][c]], bf16 adds in channel order.
- * emb [C][V][D]. */
+ * emb [C][V][D].  Ids outside [0, V - 1] are clamped into the table.  rows == 0: a success that touches nothing (the pointers may be null). */
 int umoe_codec_embed_sum(const int32_t* tok, const uint16_t* emb, int rows, int C, int V, int D, uint16_t* out,
                          umoe_stream_t stream);
 /* backward of the same (the reference's autograd of the C nn.Embedding gathers, model.py:655-661): d_emb[c][v] = sum over the rows r
  * with tok[r][c] == v of d_out[r], fp32 accumulation in ASCENDING row order (deterministic), one rounding to bf16; rows of the table
- * nobody selected are written as zeros.  D % 8 == 0, D <= 2048 * 8. */
+ * nobody selected are written as zeros; ids outside [0, V - 1] contribute nowhere (they are NOT clamped: placeholder positions carry
+ * id -1).  D % 8 == 0, D <= 2048 * 8.  rows == 0: tok and d_out may be null, d_emb is all zeros. */
 int umoe_codec_embed_sum_bwd(const int32_t* tok, const uint16_t* d_out, int rows, int C, int V, int D, uint16_t* d_emb,
                              umoe_stream_t stream);
 

@@ -325,7 +325,8 @@ __global__ __launch_bounds__(256) void codec_embed_kernel(const int32_t* __restr
 
 extern "C" int umoe_codec_embed_sum(const int32_t* tok, const uint16_t* emb, int rows, int C, int V, int D,
                                     uint16_t* out, umoe_stream_t stream) {
-    UMOE_REQUIRE(tok && emb && out && D % 8 == 0 && C > 0, "umoe_codec_embed_sum: bad argument");
+    // no rows: nothing is read or written, and an empty tensor's pointer is null
+    UMOE_REQUIRE(rows >= 0 && (rows == 0 || (tok && emb && out)) && D % 8 == 0 && C > 0, "umoe_codec_embed_sum: bad argument");
     if (rows == 0) return 0;
     codec_embed_kernel<<<dim3((unsigned)rows), 256, 0, (hipStream_t)stream>>>(tok, emb, C, V, D, out);
     UMOE_LAUNCH_CHECK();
@@ -449,7 +450,8 @@ __global__ __launch_bounds__(256) void codec_embed_bwd_rows_kernel(const int32_t
 
 extern "C" int umoe_codec_embed_sum_bwd(const int32_t* tok, const uint16_t* d_out, int rows, int C, int V, int D, uint16_t* d_emb,
                                         umoe_stream_t stream) {
-    UMOE_REQUIRE(tok && d_out && d_emb && D % 8 == 0 && D <= 2048 * 8 && C > 0 && V > 0 && rows >= 0 && C <= 65535,
+    // no rows: tok and d_out are not read (an empty tensor's pointer is null); the table gradient is all zeros
+    UMOE_REQUIRE((rows == 0 || (tok && d_out)) && d_emb && D % 8 == 0 && D <= 2048 * 8 && C > 0 && V > 0 && rows >= 0 && C <= 65535,
                  "umoe_codec_embed_sum_bwd: bad argument (D %% 8 == 0, D <= 16384)");
     if ((long)V > 4L * rows && rows > 0 && rows <= 0x7fffffff / 2) {
         UMOE_HIP(hipMemsetAsync(d_emb, 0, (size_t)C * V * D * 2, (hipStream_t)stream));
@@ -473,7 +475,7 @@ __global__ __launch_bounds__(256) void mul_noise_kernel(const uint16_t* __restri
 }
 
 extern "C" int umoe_mul_noise(const uint16_t* x, const float* noise, long n, uint16_t* y, umoe_stream_t stream) {
-    UMOE_REQUIRE(x && noise && y && n >= 0 && n % 8 == 0 && ((size_t)x & 15) == 0 && ((size_t)noise & 15) == 0 && ((size_t)y & 15) == 0,
+    UMOE_REQUIRE((n == 0 || (x && noise && y)) && n >= 0 && n % 8 == 0 && ((size_t)x & 15) == 0 && ((size_t)noise & 15) == 0 && ((size_t)y & 15) == 0,
                  "umoe_mul_noise: n %% 8 == 0 and 16-byte aligned pointers");
     if (n == 0) return 0;
     const long n8 = n / 8;
