@@ -54,6 +54,17 @@ int umoe_pack_gate_up(const uint16_t* Wg, const uint16_t* Wu, int I, int K, uint
  * with KB2 = ceil(KB/2), KB = K/32; bytes past the end of a K quarter (K/4 % 16 == 8, e.g. K = 1376) and padded rows are zero.
  * Exponents: 16 per block, exps[nb*16 + r] (0 for padded rows).  Gate/up blocks are interleaved as in umoe_pack_gate_up.  Packed on
  * the host side (unimoe_audio_amd/quant.py). */
+/* bf16 expert weights in 12 bits, lossless ("WP12", the default of the flat expert launch: umoe_engine_set_layer_w12).  Same blocks,
+ * lanes and K quarters as WP16; per lane and k-step the 8 LOW bytes raw and a 4-bit code of each HIGH byte (sign + exponent bits 7..1):
+ * sign << 3 | (high & 0x7f) - base, with one window base per 16-row block (8 consecutive values, 16 binades).  Block nb takes KB * 768
+ * bytes: the low bytes, then the code words.  CS = 2 k-steps per chunk when KB is even, else 1:
+ *   low [((c*64 + lane)*CS + s)*8 + j] = low byte of WP16[((nb*KB + c*CS + s)*64 + lane)*8 + j]
+ *   code[((c*64 + lane)*CS + s)*4 + b] = code of element (0,1,4,5)[b] | code of element (2,3,6,7)[b] << 4
+ * so `c & 0x0f0f0f0f` and `(c >> 4) & 0x0f0f0f0f` hold four codes in byte lanes and one v_perm_b32 per operand dword joins high and
+ * low bytes.  Block record: 40 u32 per block -- words 0..32 the exceptions (values whose high byte is outside the window: zeros,
+ * denormals, inf / NaN, outliers), sorted by k-step, k-step << 25 | lane << 19 | element << 16 | bf16 bits, terminated and padded by
+ * 0xffffffff; word 39 the window base.  At most 32 exceptions per block: a matrix with more is not packable and its layer runs the WP16
+ * launch.  KB < 127.  Packed and unpacked on the host side (unimoe_audio_amd/w12.py). */
 
 /* ------------------------------------------------------------------ router
  * Replaces utils/UniMoE_Audio_core.py:246-291,331-339 (gate GEMM, Top-P count :157-167,
@@ -799,6 +810,13 @@ int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* g
  * umoe_engine_info then gives "expert_launch" 4, "expert_fp8" 1, "row_tiles" = tiles.  Steps of 16 rows or fewer take the fp8 flat launch
  * either way.  Default off: a directly constructed fp8 engine of more than 16 rows refuses its decode step as before. */
 int umoe_engine_set_fp8_wide(umoe_engine* e, int on);
+/* WP12 copies of one layer's bf16 expert weights (after umoe_engine_set_layer with the WP16 packs; ep_size 1, no fp8 weights): host
+ * arrays [n_real + n_fix] (routed experts, then shared) of device pointers to WP12 gate/up pairs, their block records, WP12 down blocks
+ * and theirs.  The flat expert launch of this layer then streams them (moe_flat_w12_kernel; the same outputs bit for bit, 0.75 of the
+ * bytes); every other form keeps reading the WP16 packs.  UMOE_FLAT_W12=0 selects the WP16 launch.  umoe_engine_info(e, "expert_w12")
+ * = 1 when the last dense decode layer ran the WP12 launch. */
+int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_t* const* gu12, const uint32_t* const* gu_m, const uint8_t* const* dn12,
+                              const uint32_t* const* dn_m);
 /* test hook: the fp8 launch's conversion path over a row-major e4m3 matrix q [N][K] (K % 8 == 0) with one exponent per row:
  * out[r][k] = bf16 bits of q[r][k] * 2^e[r] */
 int umoe_fp8_convert_probe(const uint8_t* q, const int8_t* e, int N, int K, uint16_t* out, umoe_stream_t stream);

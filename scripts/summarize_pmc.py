@@ -21,7 +21,8 @@ def load(d, counter):
 
 
 fetch, write = load(sys.argv[1], "FETCH_SIZE"), load(sys.argv[2], "WRITE_SIZE")
-alg = {"moe_flat_kernel": 304.3, "wstream_gemm<1, 16, 0, 0, 4, false, true>": 10.5, "wstream_gemm<1, 16, 0, 1, 4, false, true>": 8.4,
+alg = {"moe_flat_kernel": 304.3, "moe_flat_w12_kernel": 304.3,      # (algorithmic bf16 bytes: the WP12 launch streams 0.75 of the expert bytes)
+       "wstream_gemm<1, 16, 0, 0, 4, false, true>": 10.5, "wstream_gemm<1, 16, 0, 1, 4, false, true>": 8.4,
        "wstream_gemm<2, 8, 0, 3, 4, false, true>": 50.5, "wstream_gemm<6, 2, 0, 0, 8, false, true>": 101.4,
        # (kernel names of earlier builds, kept for their recorded counter files)
        "wstream_gemm_rk<0, 2>": 10.5, "wstream_gemm_rk<1, 3>": 8.4, "wstream_gemm<1, 16, 0, 0, 4, false, false, true>": 10.5,

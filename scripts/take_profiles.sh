@@ -22,12 +22,14 @@ TAG=$TAG OUT=$OUT python3 - <<'PY'
 import json, os
 tag, out = os.environ["TAG"], os.environ["OUT"]
 pmc = json.load(open(f"{out}/{tag}_pmc_traffic.json"))["kernels"]
-name = next((k for k in pmc if k.startswith("moe_flat_kernel")), None) or next(k for k in pmc if k.startswith("wstream_gemm<14, 1, 0, 2, 8, true"))
+name = (next((k for k in pmc if k.startswith("moe_flat_w12_kernel")), None) or next((k for k in pmc if k.startswith("moe_flat_kernel")), None)
+        or next(k for k in pmc if k.startswith("wstream_gemm<14, 1, 0, 2, 8, true")))
 us = None
 for line in open(f"{out}/{tag}_decode_kernels.md"):
     if name in line:
         us = float(line.split("|")[3])
-json.dump({"kernel": name, "traffic_bytes": pmc[name]["traffic_bytes"], "kernel_us": us,
+json.dump({"kernel": f"moe_flat_kernel on WP12 expert weights ({name})" if name.startswith("moe_flat_w12") else name,      # (bench.py matches the prefix)
+           "traffic_bytes": pmc[name]["traffic_bytes"], "kernel_us": us,
            "source": f"profiles/{tag}_pmc_traffic.md (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, FETCH x 2) and profiles/{tag}_decode_kernels.md "
                      f"(rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps 20 --warmup 5`); static: not measured by the bench run itself"},
           open(f"{out}/bench_roofline_ref.json", "w"), indent=1)

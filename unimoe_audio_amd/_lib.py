@@ -157,6 +157,7 @@ EXPORTS = [
     "umoe_dac_conv1d_win", "umoe_dac_conv_transpose1d_win", "umoe_rvq_from_delayed", "umoe_delay_step_rows",
     "umoe_delay_step_clock", "umoe_engine_reserve", "umoe_engine_admit", "umoe_engine_admit_external", "umoe_gemm_wide", "umoe_pack_rows",
     "umoe_gemm_wide_fp8", "umoe_engine_set_fp8_wide", "umoe_tiled_gemm_wp8",
+    "umoe_engine_set_layer_w12",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -283,6 +284,9 @@ def lib():
         if not hasattr(L, "umoe_tiled_gemm_wp8"):
             raise UmoeError(f"{_SO} predates this package (no umoe_tiled_gemm_wp8): rebuild it (`make -C unimoe_audio_amd/csrc`)")
         L.umoe_tiled_gemm_wp8.argtypes = [C.POINTER(TGemmArgs), C.POINTER(vp), C.POINTER(vp), vp]
+        if not hasattr(L, "umoe_engine_set_layer_w12"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_engine_set_layer_w12): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_engine_set_layer_w12.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.umoe_rvq_from_codes.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_nearest.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.umoe_codec_ce_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]

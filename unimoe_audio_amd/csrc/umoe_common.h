@@ -248,6 +248,10 @@ bool umoe_moe_flat_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_r
 int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const int8_t* const* e_gu, const int8_t* const* e_dn, uint32_t* flags,
                       int flag_words, int n_wg, hipStream_t s);
 bool umoe_moe_flat_fp8_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
+// The same launch on WP12 expert weights (bf16 in 12 bits, lossless: include/umoe.h): the groups' `w` are WP12 blocks, m_gu / m_dn
+// [num_groups] their block records.  Returns 1 (nothing launched) like umoe_moe_flat: the caller then runs umoe_moe_flat on the WP16 packs.
+int umoe_moe_flat_w12(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const uint32_t* const* m_gu, const uint32_t* const* m_dn, uint32_t* flags,
+                      int flag_words, int n_wg, hipStream_t s);
 
 // A small decode GEMM with row riders in front (umoe_gemm.hip wstream_gemm_rk, umoe_riders_dev.h; decode engine only).  kind 2: the
 // MoE combine of the previous layer rides in the QKV launch; kind 4: the same over the return slab of the expert-parallel exchange.

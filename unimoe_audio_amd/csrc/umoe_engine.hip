@@ -29,6 +29,10 @@ struct LayerDev {
     std::vector<const uint16_t*> f8_gu, f8_dn;       // (WP8 addresses in the groups' `w` slots)
     std::vector<const int8_t*> f8e_gu, f8e_dn;
     bool has_f8 = false;
+    // WP12 copies of the bf16 expert weights (umoe_engine_set_layer_w12): blocks + block records, [n_real routed, then n_fix shared]
+    std::vector<const uint16_t*> w12_gu, w12_dn;
+    std::vector<const uint32_t*> w12m_gu, w12m_dn;
+    bool has_w12 = false;
 };
 
 struct Carver {
@@ -102,6 +106,7 @@ struct umoe_engine {
     bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
     int prefill_fp8 = 0;         // the last prefill / admission ran its experts on the WP8 blocks (umoe_engine_info "prefill_fp8")
+    int expert_w12 = 0;          // the last dense decode layer ran the flat launch on its WP12 copies (umoe_engine_info "expert_w12")
     int expert_fp8 = 0;          // the last dense decode layer ran an fp8 launch: the flat one, or the wide form's (umoe_engine_info "expert_fp8")
     bool fp8_wide = false;       // umoe_engine_set_fp8_wide: decode steps of 17..64 rows of an fp8 engine take the wide form on the WP8 weights
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
@@ -478,6 +483,26 @@ extern "C" int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_
     L.f8e_gu.assign(gu_e, gu_e + G); L.f8e_dn.assign(dn_e, dn_e + G);
     L.has_f8 = true;
     e->fp8 = true;
+    return 0;
+}
+
+extern "C" int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_t* const* gu12, const uint32_t* const* gu_m, const uint8_t* const* dn12,
+                                         const uint32_t* const* dn_m) {
+    UMOE_REQUIRE(e && gu12 && gu_m && dn12 && dn_m && layer >= 0 && layer < e->c.layers, "umoe_engine_set_layer_w12: bad argument (layer %d)", layer);
+    UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer_w12: WP12 expert weights run on the flat expert launch only, not expert parallel (ep_size %d)",
+                 e->c.ep_size);
+    LayerDev& L = e->layers[layer];
+    UMOE_REQUIRE(L.set && L.exp_bf16 && !L.has_f8, "umoe_engine_set_layer_w12: umoe_engine_set_layer(%d) with the WP16 packs first (and no fp8 weights)", layer);
+    const int G = e->c.n_real + e->c.n_fix;
+    for (int i = 0; i < G; ++i)
+        UMOE_REQUIRE(gu12[i] && gu_m[i] && dn12[i] && dn_m[i], "umoe_engine_set_layer_w12: layer %d group %d: null pointer", layer, i);
+    L.w12_gu.assign(G, nullptr); L.w12_dn.assign(G, nullptr);
+    for (int i = 0; i < G; ++i) {
+        L.w12_gu[i] = reinterpret_cast<const uint16_t*>(gu12[i]);
+        L.w12_dn[i] = reinterpret_cast<const uint16_t*>(dn12[i]);
+    }
+    L.w12m_gu.assign(gu_m, gu_m + G); L.w12m_dn.assign(dn_m, dn_m + G);
+    L.has_w12 = true;
     return 0;
 }
 
@@ -859,6 +884,10 @@ enum MoeForm {
 };
 
 // UMOE_FLAT_MOE=0: never the flat expert launch.  Read per enqueue: the step graph captures the choice, A/B scripts toggle it on a live engine.
+static bool flat_w12_on() {      // UMOE_FLAT_W12=0: the flat launch on the WP16 packs although the layer has WP12 copies (A/B, tests)
+    const char* v = getenv("UMOE_FLAT_W12");
+    return !v || atoi(v) != 0;
+}
 static bool flat_moe_on() {
     const char* v = getenv("UMOE_FLAT_MOE");
     return !v || atoi(v) != 0;
@@ -1136,6 +1165,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     dn.max_k = Imax;
     dn.a = e->hbuf; dn.lda = Imax; dn.out = e->ybuf; dn.ldo = D; dn.n_valid = D;
     dn.prologue = UMOE_PRO_PLAIN; dn.epilogue = UMOE_EPI_BF16; dn.nt = dense ? 6 : 0;
+    e->expert_w12 = 0;
     switch (form) {
         case MOE_TILED:
             if ((rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s))) return rc;
@@ -1156,6 +1186,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             gu.rider_pub = &rpub;
             gu.groups_host = e->h_gu_pub.data() + (size_t)l * G;
             const int n_wg = flat_wgs(e);
+            bool w12 = false;
             if (e->fp8) {        // the same launch on the WP8 blocks -- and nothing else (no bf16 path streams these weights)
                 UMOE_REQUIRE(L.has_f8 && G <= UMOE_MAXE, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
                 umoe_group_t g8u[UMOE_MAXE], g8d[UMOE_MAXE];
@@ -1170,12 +1201,28 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
                 gu8.groups_host = g8u; dn8.groups_host = g8d;
                 rc = umoe_moe_flat_fp8(&gu8, &dn8, e8u, e8d, e->ep_words + 64, 512 - 64, n_wg, s);
             } else {
-                rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);
+                rc = 1;
+                if (L.has_w12 && G <= UMOE_MAXE && flat_w12_on()) {      // the same launch on the WP12 copies: the same outputs, 0.75 of the bytes
+                    umoe_group_t g12u[UMOE_MAXE], g12d[UMOE_MAXE];
+                    const uint32_t* m12u[UMOE_MAXE];
+                    const uint32_t* m12d[UMOE_MAXE];
+                    for (int i = 0; i < G; ++i) {
+                        const int x = i < c.n_fix ? c.n_real + i : i - c.n_fix;     // gu groups: the shared experts first (h_gu_pub)
+                        g12u[i] = gu.groups_host[i]; g12u[i].w = L.w12_gu[x]; m12u[i] = L.w12m_gu[x];
+                        g12d[i] = dn.groups_host[i]; g12d[i].w = L.w12_dn[i]; m12d[i] = L.w12m_dn[i];
+                    }
+                    umoe_gemm_args gu12 = gu, dn12 = dn;
+                    gu12.groups_host = g12u; dn12.groups_host = g12d;
+                    rc = umoe_moe_flat_w12(&gu12, &dn12, m12u, m12d, e->ep_words + 64, 512 - 64, n_wg, s);
+                    w12 = rc == 0;
+                }
+                if (rc == 1) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);      // (no WP12 copies, or no schedule at their byte cost)
             }
             UMOE_REQUIRE(rc != 1, "umoe_engine: the %sflat expert launch has no schedule for this shape on %d workgroups (layer %d)", e->fp8 ? "fp8 " : "", n_wg, l);
             if (rc) return rc;
             e->expert_launch = 2;
             e->expert_fp8 = e->fp8 ? 1 : 0;
+            e->expert_w12 = w12 ? 1 : 0;
             PROF(K_GATEUP);      // (booked as gate/up: zero down launches tell the reader which form ran)
             break;
         }
@@ -1697,6 +1744,7 @@ extern "C" int umoe_engine_info(umoe_engine* e, const char* key) {
     if (!strcmp(key, "expert_launch")) return e->expert_launch;
     if (!strcmp(key, "row_tiles")) return e->expert_launch == 4 ? e->row_tiles : 1;
     if (!strcmp(key, "expert_fp8")) return e->expert_fp8;
+    if (!strcmp(key, "expert_w12")) return e->expert_w12;
     if (!strcmp(key, "prefill_fp8")) return e->prefill_fp8;
     if (!strcmp(key, "expert_bf16_resident")) return fp8_only(e) ? 0 : 1;
     if (!strcmp(key, "n_cu")) return e->n_cu;

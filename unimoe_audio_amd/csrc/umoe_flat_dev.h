@@ -94,6 +94,46 @@ __device__ __forceinline__ bf16x8_t flat_f8_frag(uint32_t lo, uint32_t hi, float
     return bf16x8_t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// ---- WP12 expert weights (moe_flat_w12_kernel): bf16 weights in 12 bits, lossless (include/umoe.h "WP12").  Per lane and k-step 8 raw
+// low bytes + 8 four-bit codes of the high bytes (sign + offset into the block's window of 8 high-byte exponents); values outside the
+// window sit in the block's sorted exception list and are patched into the decoded operand.  The operand is the WP16 one, bit for bit,
+// so the MFMAs below are the bf16 kernel's: same tiles, K split, MFMA order.
+#define FLAT_W12_META 40                // u32 per block: exceptions [0, 32] (sentinel-terminated), window base in the last word
+struct flat_w12 {                       // a kernel argument of its own (flat_args stays as it is)
+    const uint32_t* m_gu[FLAT_MAXG];    // block records of the gate/up blocks (blocks interleaved like the weights)
+    const uint32_t* m_dn[FLAT_MAXG];    // ... of the down blocks
+};
+// one k-step of a lane (low bytes l0 = values 0..3, l1 = 4..7; code word c: byte b = value (0,1,4,5)[b] | value (2,3,6,7)[b] << 4)
+// -> the MFMA operand.  wb4 = the window base in every byte (base + offset <= 127: no carry between bytes).
+__device__ __forceinline__ flat_u32x4 flat_w12_frag(uint32_t l0, uint32_t l1, uint32_t c, uint32_t wb4) {
+    const uint32_t hl = (((c & 0x07070707u) + wb4) | ((c & 0x08080808u) << 4));
+    const uint32_t hh = ((((c >> 4) & 0x07070707u) + wb4) | (c & 0x80808080u));
+    // v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first
+    return flat_u32x4{__builtin_amdgcn_perm(hl, l0, 0x05010400u), __builtin_amdgcn_perm(hh, l0, 0x05030402u),
+                      __builtin_amdgcn_perm(hl, l1, 0x07010600u), __builtin_amdgcn_perm(hh, l1, 0x07030602u)};
+}
+// A tile's exception cursor: `m` holds the block record (lane l = word min(l, 39)), st = cursor << 8 | k-step of the entry under it
+// (127: the sentinel).  Entry: k-step << 25 | lane << 19 | element << 16 | bf16 bits.
+__device__ __forceinline__ uint32_t flat_w12_cursor(uint32_t m, int i0, int lane) {
+    const uint32_t cur = (uint32_t)__builtin_popcountll(__ballot((int)(m >> 25) < i0 && lane <= 32));      // (sorted by k-step)
+    return cur << 8 | (uint32_t)__builtin_amdgcn_readlane(m, cur) >> 25;
+}
+__device__ __forceinline__ uint32_t flat_w12_base4(uint32_t m) { return ((uint32_t)__builtin_amdgcn_readlane(m, FLAT_W12_META - 1) & 0xffu) * 0x01010101u; }
+// the rare path (scalar branch taken when the entry under the cursor is of this k-step): every entry of k-step ii into the operand
+__device__ __forceinline__ void flat_w12_patch(flat_u32x4& op, uint32_t m, uint32_t& st, uint32_t ii, int lane) {
+    uint32_t cur = st >> 8, nx;
+    do {
+        const uint32_t en = (uint32_t)__builtin_amdgcn_readlane(m, cur);
+        const uint32_t sh = ((en >> 16) & 1u) * 16u, d = (en >> 17) & 3u;
+        const bool mine = (uint32_t)lane == ((en >> 19) & 63u);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) op[q] = (mine && d == (uint32_t)q) ? ((op[q] & ~(0xffffu << sh)) | ((en & 0xffffu) << sh)) : op[q];
+        ++cur;
+        nx = (uint32_t)__builtin_amdgcn_readlane(m, cur) >> 25;
+    } while (nx == ii);
+    st = cur << 8 | nx;
+}
+
 // ---- gate/up SwiGLU slice: NP pairs of the flat list starting at fp0 (arithmetic of wstream_body<14, 1, PLAIN, SWIGLU, 8> per tile) ----
 // The workgroup normalises the 16 rows ITSELF while it stages them (post-attention RMSNorm, model.py:240): the raw rows exist when the
 // launch starts, so nothing is waited for -- rows requested first, the weight stream right behind them, and the ~2 us of row arithmetic
@@ -108,15 +148,18 @@ __device__ __forceinline__ uint32_t flat_epoch(const umoe_rider_pub& pub) {
 }
 
 // F8: WP8 weights (w_gu holds WP8 addresses, F their exponents): one 16-byte chunk = two k-steps; every chunk index below counts chunks.
-template <int NP, bool PUBLISH = true, bool F8 = false>
+// W12: WP12 weights (w_gu holds WP12 addresses, Wm the block records): a register stage is a 2-step chunk (16 low bytes + 8 code bytes
+// per lane), ONE stage per tile that is requested again as soon as its two MFMAs are issued -- two whole stages would be 168 registers.
+template <int NP, bool PUBLISH = true, bool F8 = false, bool W12 = false>
 __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider_pub& pub, const int fp0, const unsigned b, char* smem, flat_stamps& st,
-                                            const int tid_in, const flat_f8* F = nullptr) {      // tid_in = threadIdx.x (a caller that loops over slices passes an opaque copy: see umoe_moe_ep.hip)
+                                            const int tid_in, const flat_f8* F = nullptr, const flat_w12* Wm = nullptr) {      // tid_in = threadIdx.x (a caller that loops over slices passes an opaque copy: see umoe_moe_ep.hip)
+    static_assert(!(F8 && W12), "one weight format");
     constexpr int NT = 2 * NP, WV = 8, KB = 64;
     const int tid = tid_in, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: every guard around an MFMA is a scalar branch
     constexpr int QS = (KB * 16 + 255) & ~255, RS = QS * 4;
     const int i0 = __builtin_amdgcn_readfirstlane((KB * wave) / WV), i1 = __builtin_amdgcn_readfirstlane((KB * (wave + 1)) / WV);
-    constexpr int CS = F8 ? 2 : 1;                   // k-steps per 16-byte chunk (a wave's 8 steps are whole chunks either way)
+    constexpr int CS = (F8 || W12) ? 2 : 1;          // k-steps per 16-byte chunk (a wave's 8 steps are whole chunks either way)
     const int c0 = i0 / CS, c1 = i1 / CS;
     // the slice straddles at most two groups (a group has far more than 7 pairs).  Every table read is a kernel-argument read with a
     // compile-time offset + a scalar select: ONE batch of scalar loads in front of the first request, no dependent second one
@@ -130,13 +173,22 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
     const flat_u32x4* wp[NT];
     [[maybe_unused]] const int8_t* ep[F8 ? NT : 1];
     [[maybe_unused]] int ev[F8 ? NT : 1];
+    // (W12: wp = the block's low bytes, 16 per lane and chunk; cp = its code words, 8 per lane and chunk; mp = this lane's record word)
+    [[maybe_unused]] const flat_u32x2* cp[W12 ? NT : 1];
+    [[maybe_unused]] const uint32_t* mp[W12 ? NT : 1];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const int pp = fp0 + (t >> 1);
         const bool second = pp >= cut;
         const int lp = pp - (second ? cut : p0);
-        if constexpr (F8) {
+        if constexpr (W12) {
+            const int blk = 2 * lp + (t & 1);
+            const char* base = reinterpret_cast<const char*>(second ? wg1 : wg0) + (size_t)blk * (KB * 768);
+            wp[t] = reinterpret_cast<const flat_u32x4*>(base) + lane;
+            cp[t] = reinterpret_cast<const flat_u32x2*>(base + KB * 512) + lane;
+            mp[t] = (second ? Wm->m_gu[g0 + 1 < FLAT_MAXG ? g0 + 1 : g0] : Wm->m_gu[g0]) + blk * FLAT_W12_META + min(lane, FLAT_W12_META - 1);
+        } else if constexpr (F8) {
             const int blk = 2 * lp + (t & 1);
             wp[t] = reinterpret_cast<const flat_u32x4*>(second ? wg1 : wg0) + ((size_t)blk * (KB / 2)) * 64 + lane;
             ep[t] = (second ? F->e_gu[g0 + 1 < FLAT_MAXG ? g0 + 1 : g0] : F->e_gu[g0]) + blk * 16 + (lane & 15);
@@ -149,6 +201,14 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
         if constexpr (F8) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) ev[t] = *ep[t];
+        }
+    };
+    [[maybe_unused]] flat_u32x2 wc[W12 ? NT : 1];      // W12: the code words of the stage w0; mt: the block records
+    [[maybe_unused]] uint32_t mt[W12 ? NT : 1];
+    auto w12_load_tile = [&](flat_u32x4 (&dst)[NT], int t, int ic) {
+        if constexpr (W12) {
+            dst[t] = __builtin_nontemporal_load(wp[t] + (size_t)ic * 64);
+            wc[t] = __builtin_nontemporal_load(cp[t] + (size_t)ic * 64);
         }
     };
     flat_u32x4 w0[NT], w1[NT];
@@ -215,8 +275,16 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
         //  second stage's 14 requests per wave only delayed the point where the rows are staged -- 8.6 -> 12.1 us -- and bought nothing:
         //  3.020 vs 3.015 ms/step.  The launch runs at the CU's request rate from its first request on.)
         __builtin_amdgcn_sched_barrier(0);
-        load_chunk(w0, c0);
-        load_scales();
+        if constexpr (W12) {
+            // the block records in FRONT of the stage (256 bytes a tile): behind it they would return last, and the first MFMA needs them
+#pragma unroll
+            for (int t = 0; t < NT; ++t) mt[t] = *mp[t];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) w12_load_tile(w0, t, c0);
+        } else {
+            load_chunk(w0, c0);
+            load_scales();
+        }
         __builtin_amdgcn_sched_barrier(0);
         FSTAMP(1);
         norm_stage(buf, nw1);
@@ -246,11 +314,39 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
             }
         }
     };
-    for (int i = c0; i < c1; i += 2) {
-        if (i + 1 < c1) load_chunk(w1, i + 1);
-        compute_chunk(w0, i);
-        if (i + 2 < c1) load_chunk(w0, i + 2);
-        if (i + 1 < c1) compute_chunk(w1, i + 1);
+    if constexpr (W12) {
+        // chunk ic of every tile: decode, patch (a scalar compare per tile and k-step), the two MFMAs; REFILL: the tile's next chunk is
+        // requested right behind them (straight-line: the last chunk is the same body without the requests)
+        uint32_t xs[NT], wb4[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            xs[t] = flat_w12_cursor(mt[t], i0, lane);
+            wb4[t] = flat_w12_base4(mt[t]);
+        }
+        auto w12_chunk = [&](int ic, auto refill) {
+            const uint4 bv0 = *reinterpret_cast<const uint4*>(bbase + flat_lds_chunk_off(QS, h, 2 * ic, mm));
+            const uint4 bv1 = *reinterpret_cast<const uint4*>(bbase + flat_lds_chunk_off(QS, h, 2 * ic + 1, mm));
+            const bf16x8_t bf0 = __builtin_bit_cast(bf16x8_t, bv0), bf1 = __builtin_bit_cast(bf16x8_t, bv1);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                flat_u32x4 o0 = flat_w12_frag(w0[t][0], w0[t][1], wc[t][0], wb4[t]);
+                if ((xs[t] & 0xffu) == (uint32_t)(2 * ic)) flat_w12_patch(o0, mt[t], xs[t], (uint32_t)(2 * ic), lane);
+                flat_u32x4 o1 = flat_w12_frag(w0[t][2], w0[t][3], wc[t][1], wb4[t]);
+                if ((xs[t] & 0xffu) == (uint32_t)(2 * ic + 1)) flat_w12_patch(o1, mt[t], xs[t], (uint32_t)(2 * ic + 1), lane);
+                if constexpr (decltype(refill)::value) w12_load_tile(w0, t, ic + 1);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, o0), bf0, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, o1), bf1, acc[t], 0, 0, 0);
+            }
+        };
+        for (int ic = c0; ic < c1 - 1; ++ic) w12_chunk(ic, std::true_type{});
+        w12_chunk(c1 - 1, std::false_type{});
+    } else {
+        for (int i = c0; i < c1; i += 2) {
+            if (i + 1 < c1) load_chunk(w1, i + 1);
+            compute_chunk(w0, i);
+            if (i + 2 < c1) load_chunk(w0, i + 2);
+            if (i + 1 < c1) compute_chunk(w1, i + 1);
+        }
     }
     // ---- fixed-order cross-wave reduction through the (now free) staging area ----
     FSTAMP(4);
@@ -305,9 +401,12 @@ __device__ __forceinline__ void flat_gateup(const flat_args& A, const umoe_rider
 // F8: WP8 weights (w_dn holds WP8 addresses, F their exponents).  U = 2: one 16-byte load per lane carries the chunk's two k-steps;
 // U = 1 (an odd number of k-steps per K quarter: a wave's slice starts or ends on either half of a 16-byte chunk): one 8-byte load per
 // k-step.  Either way exactly the bf16 kernel's MFMAs -- no padded step is computed.
-template <int ND, int U, bool F8 = false>
+// W12: WP12 weights (w_dn holds WP12 addresses, Wm the block records): a register stage holds U k-steps -- 8 U low bytes + 4 U code bytes
+// per lane, two loads -- and the stages are double-buffered like the bf16 ones (the packer chunks by the parity of KB, as U is chosen).
+template <int ND, int U, bool F8 = false, bool W12 = false>
 __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_pub& pub, const int grp, const int nb0, char* smem, flat_stamps& st,
-                                          const int sb, const int tid_in, const flat_f8* F = nullptr) {
+                                          const int sb, const int tid_in, const flat_f8* F = nullptr, const flat_w12* Wm = nullptr) {
+    static_assert(!(F8 && W12), "one weight format");
     constexpr int NT = ND, WV = 8;
     const int tid = tid_in, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -327,14 +426,22 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
     f32x4_t acc[NT];
     // (F8: a register stage holds U k-steps of e4m3 -- 8 bytes per step -- in ONE load: x4 for U = 2, x2 for U = 1)
     using FW = std::conditional_t<U == 2, flat_u32x4, flat_u32x2>;
-    constexpr int UL = F8 ? 1 : U;                   // loads per register stage and tile
-    using WT = std::conditional_t<F8, FW, flat_u32x4>;
+    constexpr int UL = (F8 || W12) ? 1 : U;          // loads per register stage and tile (W12: + one of the code words)
+    using WT = std::conditional_t<F8 || W12, FW, flat_u32x4>;
+    using CT = std::conditional_t<U == 2, flat_u32x2, uint32_t>;      // W12: the code words of a stage
     const WT* wp[NT];
     [[maybe_unused]] int ev[F8 ? NT : 1];
+    [[maybe_unused]] const CT* cp[W12 ? NT : 1];
+    [[maybe_unused]] uint32_t mt[W12 ? NT : 1];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if constexpr (F8) {
+        if constexpr (W12) {
+            const char* base = reinterpret_cast<const char*>(A.w_dn[grp]) + (size_t)(nb0 + t) * ((size_t)KB * 768);
+            wp[t] = reinterpret_cast<const WT*>(base) + lane;
+            cp[t] = reinterpret_cast<const CT*>(base + (size_t)KB * 512) + lane;
+            mt[t] = Wm->m_dn[grp][(nb0 + t) * FLAT_W12_META + min(lane, FLAT_W12_META - 1)];      // (in front of the first stage, like flat_gateup)
+        } else if constexpr (F8) {
             const int KB2 = (KB + 1) >> 1;           // 16-byte chunks per K quarter (the last one half used when KB is odd)
             wp[t] = reinterpret_cast<const WT*>(reinterpret_cast<const flat_u32x4*>(A.w_dn[grp]) + ((size_t)(nb0 + t) * KB2) * 64 + lane);
         } else {
@@ -342,8 +449,17 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
         }
     }
     WT w0[NT][UL], w1[NT][UL];
+    [[maybe_unused]] CT c0[W12 ? NT : 1], c1[W12 ? NT : 1];
     auto load_chunk = [&](WT (&dst)[NT][UL], int ibase) {
-        if constexpr (F8) {
+        if constexpr (W12) {
+            const int ii = min(ibase, i1 - U) / U;   // (the stage is chunk ii of the block: U = 2 on even KB only, i0 and i1 even)
+            CT(&cd)[W12 ? NT : 1] = (&dst == &w0) ? c0 : c1;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                dst[t][0] = __builtin_nontemporal_load(wp[t] + (size_t)ii * 64);
+                cd[t] = __builtin_nontemporal_load(cp[t] + (size_t)ii * 64);
+            }
+        } else if constexpr (F8) {
             const int ii = min(ibase, i1 - U);       // (U = 2: ibase and i1 even -- the stage is the whole chunk ii / 2)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
@@ -399,6 +515,14 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
     FSTAMP(sb + 1);
     const int h = lane >> 4, mm = lane & 15;
     const char* bbase = smem + mm * RS;
+    [[maybe_unused]] uint32_t xs[W12 ? NT : 1], wb4[W12 ? NT : 1];
+    if constexpr (W12) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            xs[t] = flat_w12_cursor(mt[t], i0, lane);
+            wb4[t] = flat_w12_base4(mt[t]);
+        }
+    }
     auto compute_chunk = [&](const WT (&src)[NT][UL], int ibase) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -408,7 +532,14 @@ __device__ __forceinline__ void flat_down(const flat_args& A, const umoe_rider_p
                 const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, bv);
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    if constexpr (F8)
+                    if constexpr (W12) {
+                        const CT(&cs)[NT] = (&src == &w0) ? c0 : c1;
+                        uint32_t cw;
+                        if constexpr (U == 2) cw = cs[t][u]; else cw = cs[t];
+                        flat_u32x4 o = flat_w12_frag(src[t][0][2 * u], src[t][0][2 * u + 1], cw, wb4[t]);
+                        if ((xs[t] & 0xffu) == (uint32_t)ii) flat_w12_patch(o, mt[t], xs[t], (uint32_t)ii, lane);
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, o), bfrag, acc[t], 0, 0, 0);
+                    } else if constexpr (F8)
                         acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(flat_f8_frag(src[t][0][2 * u], src[t][0][2 * u + 1], flat_f8_scale(ev[t])), bfrag, acc[t], 0, 0, 0);
                     else
                         acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, src[t][u]), bfrag, acc[t], 0, 0, 0);

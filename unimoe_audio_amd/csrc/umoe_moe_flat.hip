@@ -30,9 +30,11 @@
 
 #define FLAT_RIDER_LDS 512      // bytes of LDS behind the GEMM area for the riders' partial sums (router4_body: 4 + 4 * 16 floats)
 
-// The body of both kernels below.  F8: WP8 blocks + per-row exponents *F (flat_gateup / flat_down with F8); F = nullptr for bf16 weights.
-template <bool F8>
-__device__ __forceinline__ void moe_flat_body(const flat_args& A, const umoe_router_args& ra, const umoe_rider_pub& pub, const int lds_gemm, const flat_f8* F) {
+// The body of the kernels below.  F8: WP8 blocks + per-row exponents *F (flat_gateup / flat_down with F8); W12: WP12 blocks + block
+// records *Wm; both nullptr for bf16 weights.
+template <bool F8, bool W12 = false>
+__device__ __forceinline__ void moe_flat_body(const flat_args& A, const umoe_router_args& ra, const umoe_rider_pub& pub, const int lds_gemm, const flat_f8* F,
+                                              const flat_w12* Wm = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned b = blockIdx.x;
     const unsigned eg = A.gu[b], ed = A.dn[b];
@@ -63,10 +65,10 @@ __device__ __forceinline__ void moe_flat_body(const flat_args& A, const umoe_rou
     }
     const int fp0 = (int)(eg & 2047u), np = (int)((eg >> 11) & 7u);
     switch (np) {
-        case 4: flat_gateup<4, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
-        case 5: flat_gateup<5, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
-        case 6: flat_gateup<6, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
-        case 7: flat_gateup<7, true, F8>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F); break;
+        case 4: flat_gateup<4, true, F8, W12>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F, Wm); break;
+        case 5: flat_gateup<5, true, F8, W12>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F, Wm); break;
+        case 6: flat_gateup<6, true, F8, W12>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F, Wm); break;
+        case 7: flat_gateup<7, true, F8, W12>(A, pub, fp0, b, smem, st, (int)threadIdx.x, F, Wm); break;
         default: break;
     }
     for (int sl = 0; sl < FLAT_SLICES; ++sl) {
@@ -76,25 +78,25 @@ __device__ __forceinline__ void moe_flat_body(const flat_args& A, const umoe_rou
         __syncthreads();     // (the reduction slab of the previous GEMM is the staging area of this one)
         if (A.dn_kb[grp] & 1) {
             switch (nd) {
-                case 1: flat_down<1, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 2: flat_down<2, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 3: flat_down<3, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 4: flat_down<4, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 5: flat_down<5, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 6: flat_down<6, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 7: flat_down<7, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 8: flat_down<8, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 9: flat_down<9, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                default: flat_down<10, 1, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 1: flat_down<1, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 2: flat_down<2, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 3: flat_down<3, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 4: flat_down<4, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 5: flat_down<5, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 6: flat_down<6, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 7: flat_down<7, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 8: flat_down<8, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 9: flat_down<9, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                default: flat_down<10, 1, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
             }
         } else {
             switch (nd) {
-                case 1: flat_down<1, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 2: flat_down<2, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 3: flat_down<3, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 4: flat_down<4, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                case 5: flat_down<5, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
-                default: flat_down<6, 2, F8>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F); break;
+                case 1: flat_down<1, 2, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 2: flat_down<2, 2, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 3: flat_down<3, 2, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 4: flat_down<4, 2, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                case 5: flat_down<5, 2, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
+                default: flat_down<6, 2, F8, W12>(A, pub, grp, nb0, smem, st, 7 + 4 * sl, (int)threadIdx.x, F, Wm); break;
             }
         }
     }
@@ -117,6 +119,12 @@ __global__ __launch_bounds__(512, 1) void moe_flat_fp8_kernel(const flat_args A,
     moe_flat_body<true>(A, ra, pub, lds_gemm, &F);
 }
 
+// The same launch on WP12 expert weights (bf16 in 12 bits, lossless: the outputs are those of moe_flat_kernel, bit for bit).
+__global__ __launch_bounds__(512, 1) void moe_flat_w12_kernel(const flat_args A, const umoe_router_args ra, const umoe_rider_pub pub, const int lds_gemm,
+                                                              const flat_w12 W) {
+    moe_flat_body<false, true>(A, ra, pub, lds_gemm, nullptr, &W);
+}
+
 // ------------------------------------------------------------------------------------ host: the static schedule
 // Model (units: KiB a workgroup takes in; 1 KiB ~ 38 ns at 26 GB/s): a pair costs 2 * kb KiB, a down block kb KiB, a rider loses
 // `rider` KiB in front of its slice, a down slice `stage` KiB for the wait + the rows, a published slice is seen `flagc` KiB later.
@@ -133,7 +141,8 @@ struct FlatShape {
     int pairs[FLAT_MAXG], dn_nb[FLAT_MAXG], dn_kb[FLAT_MAXG], dn_src[FLAT_MAXG];
     int rider_less, heavy_at;           // experiment knobs: -1 = search
     double rider, stage, flagc, pair_scale;
-    int fp8;                            // 1: WP8 weights -- a pair and a block cost half the KiB (the fixed costs above stay)
+    int fp8;                            // weight format: 1: WP8 -- a pair and a block cost half the KiB (the fixed costs above stay); 2: WP12 -- 0.75
+    double wcost() const { return fp8 == 1 ? 0.5 : fp8 == 2 ? 0.75 : 1.0; }
     bool operator==(const FlatShape& o) const { return memcmp(this, &o, sizeof(*this)) == 0; }
 };
 
@@ -147,7 +156,7 @@ static bool flat_assign(const FlatShape& sh, const double* avail, const double* 
     for (int j = 0; j < n; ++j) { fre[j] = avail[j]; o.n[j] = 0; }
     for (int q = 0; q < sh.G; ++q) {
         const int i = ex[q];
-        const double se = seam[sh.dn_src[i]], cb = sh.fp8 ? 0.5 * sh.dn_kb[i] : (double)sh.dn_kb[i];
+        const double se = seam[sh.dn_src[i]], cb = sh.wcost() * sh.dn_kb[i];
         const int ndmax = (sh.dn_kb[i] & 1) ? FLAT_ND_MAX1 : FLAT_ND_MAX2;
         int left = sh.dn_nb[i], next = 0;
         while (left > 0) {
@@ -179,10 +188,10 @@ static void flat_plan(const FlatShape& sh, FlatPlan& out) {
     for (int i = 0; i < G; ++i) { pair0[i] = P; P += sh.pairs[i]; }
     pair0[G] = P;
     if (P >= 2048) return;
-    const double cp = sh.fp8 ? (double)sh.kb_gu : 2.0 * sh.kb_gu;
+    const double cp = sh.wcost() * 2.0 * sh.kb_gu;
     double total = P * cp + S * sh.rider + n * sh.stage;
     int kb_big = 0;
-    for (int i = 0; i < G; ++i) { total += (sh.fp8 ? 0.5 : 1.0) * sh.dn_nb[i] * sh.dn_kb[i]; kb_big = std::max(kb_big, sh.dn_kb[i]); }
+    for (int i = 0; i < G; ++i) { total += sh.wcost() * sh.dn_nb[i] * sh.dn_kb[i]; kb_big = std::max(kb_big, sh.dn_kb[i]); }
     FlatPlan best;
     double best_T = 1e30;
     std::vector<int> np(n), fp0(n);
@@ -299,9 +308,9 @@ static void flat_knobs(FlatShape& sh) {
 }
 
 // Returns 0 (launched), 1 (shapes / CU count do not allow it: nothing launched), < 0 error.  `f8` (umoe_moe_flat_fp8): the groups' weight
-// pointers are WP8 blocks, f8 holds their exponents in the same group order.
+// pointers are WP8 blocks, f8 holds their exponents in the same group order.  `w12` (umoe_moe_flat_w12): WP12 blocks and their records.
 static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s,
-                           const flat_f8* f8) {
+                           const flat_f8* f8, const flat_w12* w12 = nullptr) {
     UMOE_REQUIRE(gu && dn && flags, "umoe_moe_flat: null argument");
     const int G = gu->num_groups;
     if (!(gu->fused_router && gu->rider_pub && gu->groups_host && dn->groups_host && G == dn->num_groups && G <= FLAT_MAXG && gu->prologue == UMOE_PRO_PLAIN &&
@@ -333,10 +342,11 @@ static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, u
         sh.dn_src[i] = j;
     }
     flat_knobs(sh);
-    sh.fp8 = f8 ? 1 : 0;
-    static FlatShape cached_shapes[2];      // one plan per weight format (an A/B of the two engines in one process re-plans neither)
-    static FlatPlan cached_plans[2];
-    static bool haves[2] = {false, false};
+    sh.fp8 = f8 ? 1 : w12 ? 2 : 0;
+    if (w12 && (sh.kb_gu & 1)) return 1;    // (flat_gateup streams 2-step WP12 chunks)
+    static FlatShape cached_shapes[3];      // one plan per weight format (an A/B of the engines in one process re-plans none)
+    static FlatPlan cached_plans[3];
+    static bool haves[3] = {false, false, false};
     FlatShape& cached_shape = cached_shapes[sh.fp8];
     FlatPlan& cached_plan = cached_plans[sh.fp8];
     bool& have = haves[sh.fp8];
@@ -379,8 +389,9 @@ static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, u
     lds = std::max(lds, (size_t)8 * 2 * FLAT_NP_MAX * 1024);
     lds = std::max(lds, (size_t)8 * FLAT_ND_MAX1 * 1024);
     if (lds + FLAT_RIDER_LDS > 160 * 1024) return 1;
-    static size_t configured[2] = {0, 0};
-    const void* kfn = f8 ? reinterpret_cast<const void*>(&moe_flat_fp8_kernel) : reinterpret_cast<const void*>(&moe_flat_kernel);
+    static size_t configured[3] = {0, 0, 0};
+    const void* kfn = f8 ? reinterpret_cast<const void*>(&moe_flat_fp8_kernel)
+                         : w12 ? reinterpret_cast<const void*>(&moe_flat_w12_kernel) : reinterpret_cast<const void*>(&moe_flat_kernel);
     if (lds + FLAT_RIDER_LDS > configured[sh.fp8]) {
         UMOE_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + FLAT_RIDER_LDS)));
         configured[sh.fp8] = lds + FLAT_RIDER_LDS;
@@ -388,6 +399,7 @@ static int moe_flat_launch(const umoe_gemm_args* gu, const umoe_gemm_args* dn, u
     umoe_router_args rr = *r;
     rr.h_out = nullptr;          // nobody reads normalised rows from memory: every workgroup makes its own copy in LDS
     if (f8) moe_flat_fp8_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds, *f8);
+    else if (w12) moe_flat_w12_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds, *w12);
     else moe_flat_kernel<<<dim3((unsigned)n_wg), 512, lds + FLAT_RIDER_LDS, s>>>(A, rr, pub, (int)lds);
     UMOE_LAUNCH_CHECK();
     return 0;
@@ -407,6 +419,21 @@ int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const 
         F.e_gu[i] = e_gu[i]; F.e_dn[i] = e_dn[i];
     }
     return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, &F);
+}
+
+// The same launch on WP12 weights: the groups' `w` are WP12 blocks (unimoe_audio_amd/w12.py), m_gu / m_dn their block records in the
+// same group order.  Returns 1 like umoe_moe_flat when no schedule exists (the caller then runs the bf16 launch: the same outputs).
+int umoe_moe_flat_w12(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const uint32_t* const* m_gu, const uint32_t* const* m_dn, uint32_t* flags,
+                      int flag_words, int n_wg, hipStream_t s) {
+    UMOE_REQUIRE(m_gu && m_dn && gu && dn && gu->num_groups <= FLAT_MAXG, "umoe_moe_flat_w12: bad argument");
+    flat_w12 W;
+    memset(&W, 0, sizeof(W));
+    for (int i = 0; i < gu->num_groups; ++i) {
+        UMOE_REQUIRE(m_gu[i] && m_dn[i], "umoe_moe_flat_w12: group %d has no block records", i);
+        UMOE_REQUIRE(dn->groups_host && dn->groups_host[i].k / 32 < 127, "umoe_moe_flat_w12: group %d: K too large for the exception records", i);
+        W.m_gu[i] = m_gu[i]; W.m_dn[i] = m_dn[i];
+    }
+    return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, nullptr, &W);
 }
 
 // Does a schedule exist for this decode shape on n_wg workgroups?  (the engine asks before it drops the RMSNorm launch)
@@ -454,6 +481,11 @@ static int flat_plan_probe(int n_wg, int S, int D, int I_dyn, int I_sh, int n_re
 
 extern "C" int umoe_moe_flat_plan_probe(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix, double* out, int out_len) {
     return flat_plan_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out, out_len, 0);
+}
+
+// the same for WP12 expert weights (the plan moe_flat_w12_kernel runs: a pair and a block cost 0.75 of the KiB)
+extern "C" int umoe_moe_flat_plan_w12_probe(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix, double* out, int out_len) {
+    return flat_plan_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out, out_len, 2);
 }
 
 // the same for WP8 expert weights (the plan moe_flat_fp8_kernel runs: a pair and a block cost half the KiB)

@@ -9,6 +9,7 @@ replayed as a hipGraph, no per-step host synchronisation (the reference has > 50
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
@@ -16,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import ops, quant
+from . import ops, quant, w12
 from . import row_params as RP
 from .codec_utils import DecoderOutput
 from .config import UniMoEAudioConfig
@@ -357,6 +358,23 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
     def _pack_key(self):
         return tuple((p.data_ptr(), p._version) for n, p in self.named_parameters() if not n.startswith("visual."))
 
+    def packed_w12(self) -> list:
+        """WP12 copies of the expert packs (unimoe_audio_amd/w12.py: the bf16 weights in 12 bits, lossless) for the flat expert launch,
+        packed once per parameter version like packed(): per layer dict(gu=[(blocks, records)], dn=[...]) over the routed experts, then
+        the shared ones -- or None for a layer with a block over the exception cap (it runs the bf16 launch)."""
+        key = self._pack_key()
+        if getattr(self, "_pk12", None) is not None and self._pk12_key == key:
+            return self._pk12
+        D = self.config.hidden_size
+        out = []
+        for lp in self.packed()["layers"]:
+            pk = lp["moe"]
+            gu = [w12.pack(t.view(torch.int16), D // 32) for t in pk["exp_gu"] + pk["sh_gu"]]
+            dn = [w12.pack(t.view(torch.int16), t.numel() // (D // 16 * 512)) for t in pk["exp_dn"] + pk["sh_dn"]]
+            out.append(None if any(x is None for x in gu + dn) else dict(gu=gu, dn=dn))
+        self._pk12, self._pk12_key = out, key
+        return out
+
     def engine(self, batch: int, max_prompt: int, max_tokens: int, attn_splits: int = 8, ep=None,
                expert_weights: Optional[str] = None) -> "DecodeEngine":
         """The decode engine for this shape, rebuilt when the shape, the weights (data pointer / version of any parameter) or the
@@ -547,6 +565,9 @@ class DecodeEngine:
         self.ep = ep
         self.ep_rank, self.ep_size = (0, 1) if ep is None else (ep.rank, ep.size)
         self.pack_key = model._pack_key()
+        # the flat expert launch (ep 1, <= 16 rows, bf16 experts) streams WP12 copies of the expert weights: the same bits in 0.75 of the
+        # bytes.  UMOE_FLAT_W12=0: the WP16 launch, and nothing is packed.
+        self.w12 = fmt == "bf16" and self.ep_size == 1 and self.rows <= 16 and os.environ.get("UMOE_FLAT_W12", "1") != "0"
         h = C.c_void_p()
         L.check(L.lib().umoe_engine_create(C.byref(c), C.byref(h)), "umoe_engine_create")
         self.h = h
@@ -618,6 +639,8 @@ class DecodeEngine:
             L.check(lib.umoe_engine_set_layer(self.h, li, C.byref(w)), "umoe_engine_set_layer")
             if self.expert_weights in ("fp8", "fp8-only"):
                 self._set_layer_fp8(li, ex, sh)
+            elif self.w12:
+                self._set_layer_w12(li)
         emb, head = mpk["emb"], mpk["head"]
         # (slack: the temporal stream of a video advances by seconds-per-grid * tokens_per_second per frame pair, model.py:597-603)
         max_pos = self.Lmax + 4104 if max_pos_override is None else int(max_pos_override)
@@ -628,6 +651,16 @@ class DecodeEngine:
         L.check(lib.umoe_engine_set_globals(self.h, m.language_model.norm.weight.data_ptr(), emb.data_ptr(), head.data_ptr(),
                                             cos.data_ptr(), sin.data_ptr(), max_pos, delay), "umoe_engine_set_globals")
         torch.cuda.synchronize()
+
+    def _set_layer_w12(self, li):
+        """WP12 blocks + block records of one layer's experts (routed, then shared); a layer that is not packable keeps the bf16 launch."""
+        pk = self.model.packed_w12()[li]
+        if pk is None:
+            return
+        self._k(pk)
+        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        L.check(L.lib().umoe_engine_set_layer_w12(self.h, li, arr([d for d, _ in pk["gu"]]), arr([m for _, m in pk["gu"]]),
+                                                  arr([d for d, _ in pk["dn"]]), arr([m for _, m in pk["dn"]])), "umoe_engine_set_layer_w12")
 
     def _set_layer_fp8(self, li, ex, sh):
         """WP8 blocks + exponents of one layer's experts (routed, then shared) from the (q, e) quantize_experts_ kept."""
