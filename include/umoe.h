@@ -253,6 +253,18 @@ int umoe_gemm_wide(const uint16_t* const* host_w, const int* host_n_blocks, cons
 int umoe_gemm_wide_fp8(const uint8_t* const* host_w8, const int8_t* const* host_exps, const int* host_n_blocks, const int* host_k,
                        int num_groups, int rows, const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid,
                        int epilogue, int waves, int u, umoe_stream_t stream);
+/* The gate/up and the down launch of the wide step on WP12 weights (above, "WP12": the bf16 bits in 12 bits per weight): host_w12[g] holds
+ * the WP12 blocks of group g (K / 32 * 768 bytes per 16-row block, gate/up blocks interleaved as in umoe_pack_gate_up), host_meta[g] their
+ * block records (40 u32 per block); everything else is umoe_gemm_wide's -- tiles, K split, reduction order, epilogue, operand-order tiles in
+ * and (SwiGLU) out.  A lane rebuilds the WP16 operand of a (block, k-step) once, in front of the MFMAs of all row tiles, so every output
+ * is bit-identical to umoe_gemm_wide on the WP16 weights the blocks were packed from.  Accepts exactly (UMOE_EPI_SWIGLU, 8, 1) and
+ * (UMOE_EPI_BF16, 8, 2); no bias, no residual; 17..64 rows.  A group with an even K / 32 streams 2-step chunks (16 low bytes + 8 code bytes
+ * per lane), one with an odd K / 32 (u = 2 only) 1-step chunks (8 + 4), as the packer lays them; groups of both kinds may share a launch.
+ * K % 32 == 0, K / 32 < 127; the gate/up launch (u = 1) needs K % 512 == 0 (every wave slice whole chunks) and n_blocks % 4 == 0.
+ * Weights, input tiles and outputs are 16-byte aligned, records 4-byte aligned.  Anything else is refused with nothing launched. */
+int umoe_gemm_wide_w12(const uint8_t* const* host_w12, const uint32_t* const* host_meta, const int* host_n_blocks, const int* host_k,
+                       int num_groups, int rows, const uint16_t* const* host_b, void* const* host_out, int ldo, int n_valid,
+                       int epilogue, int waves, int u, umoe_stream_t stream);
 /* rows [rows][lda] (row-major, the first k columns) -> operand-order tiles for umoe_gemm_wide: packed holds ceil(rows / 16) * 16 * k
  * elements, pad rows of the last tile are written as zeros and their source is not read.  norm_w != NULL (k 2048 / 4096): RMSNorm in
  * front, values bit-identical to umoe_router_fwd(norm_only).  x, packed and norm_w are 16-byte aligned, lda % 8 == 0. */
@@ -813,10 +825,17 @@ int umoe_engine_set_fp8_wide(umoe_engine* e, int on);
 /* WP12 copies of one layer's bf16 expert weights (after umoe_engine_set_layer with the WP16 packs; ep_size 1, no fp8 weights): host
  * arrays [n_real + n_fix] (routed experts, then shared) of device pointers to WP12 gate/up pairs, their block records, WP12 down blocks
  * and theirs.  The flat expert launch of this layer then streams them (moe_flat_w12_kernel; the same outputs bit for bit, 0.75 of the
- * bytes); every other form keeps reading the WP16 packs.  UMOE_FLAT_W12=0 selects the WP16 launch.  umoe_engine_info(e, "expert_w12")
+ * bytes), and so does the wide form with umoe_engine_set_w12_wide; every other form keeps reading the WP16 packs.  UMOE_FLAT_W12=0 selects the WP16 launch.  umoe_engine_info(e, "expert_w12")
  * = 1 when the last dense decode layer ran the WP12 launch. */
 int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_t* const* gu12, const uint32_t* const* gu_m, const uint8_t* const* dn12,
                               const uint32_t* const* dn_m);
+/* on != 0: the wide form of a decode step of 17..64 rows (wide_mode and its size table are untouched: the switch changes which kernel a
+ * wide step runs, not whether the step is wide) runs the gate/up and down launches of every layer that has WP12 copies
+ * (umoe_engine_set_layer_w12 stores them at any row count) through umoe_gemm_wide_w12: the same outputs bit for bit, 0.75 of the expert
+ * bytes.  A layer without copies (not packable) and an fp8 engine keep their launches.  UMOE_WIDE_W12=0, read per enqueue, forces the WP16
+ * launches on such an engine.  umoe_engine_info(e, "expert_w12") = 1 when the last layer's wide expert launches ran on WP12;
+ * "expert_launch" stays 4 and "row_tiles" the tile count.  Default off. */
+int umoe_engine_set_w12_wide(umoe_engine* e, int on);
 /* test hook: the fp8 launch's conversion path over a row-major e4m3 matrix q [N][K] (K % 8 == 0) with one exponent per row:
  * out[r][k] = bf16 bits of q[r][k] * 2^e[r] */
 int umoe_fp8_convert_probe(const uint8_t* q, const int8_t* e, int N, int K, uint16_t* out, umoe_stream_t stream);

@@ -158,6 +158,7 @@ EXPORTS = [
     "umoe_delay_step_clock", "umoe_engine_reserve", "umoe_engine_admit", "umoe_engine_admit_external", "umoe_gemm_wide", "umoe_pack_rows",
     "umoe_gemm_wide_fp8", "umoe_engine_set_fp8_wide", "umoe_tiled_gemm_wp8",
     "umoe_engine_set_layer_w12",
+    "umoe_gemm_wide_w12", "umoe_engine_set_w12_wide",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -287,6 +288,11 @@ def lib():
         if not hasattr(L, "umoe_engine_set_layer_w12"):
             raise UmoeError(f"{_SO} predates this package (no umoe_engine_set_layer_w12): rebuild it (`make -C unimoe_audio_amd/csrc`)")
         L.umoe_engine_set_layer_w12.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        if not hasattr(L, "umoe_gemm_wide_w12"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_gemm_wide_w12): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_gemm_wide_w12.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32,
+                                         i32, i32, i32, vp]
+        L.umoe_engine_set_w12_wide.argtypes = [vp, i32]
         L.umoe_rvq_from_codes.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_nearest.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.umoe_codec_ce_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]

@@ -377,7 +377,7 @@ class UniMoEAudio:
 
     @torch.no_grad()
     def serve(self, requests, slots: int = 8, output_dir: Optional[str] = "./", poll_every: int = 16, max_prompt_tokens: int = 512,
-              max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None):
+              max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None, w12_wide: Optional[bool] = None):
         """Continuous batching: a generator that takes SpeechRequest / MusicRequest objects from any iterable (read lazily) and yields
         (index, wav path) as each request ends -- index = the request's position in `requests`, the file is
         `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows (1..32) decode together,
@@ -385,12 +385,13 @@ class UniMoEAudio:
         stream the fp8 copies); a request is admitted into a row as soon as one is free (first in, first out, checked every `poll_every` steps), while the other
         rows keep decoding (DecodeEngine.admit, unimoe_audio_amd/serve.py).  Each request's prompt pair is built as generate_batch builds it
         and keeps its own length.  The engine is sized once: max_prompt_tokens per prompt, max_audio_seconds per request; a request beyond
-        either is refused when its turn comes.  Not for expert-parallel engines, video prompts or streamed chunks."""
+        either is refused when its turn comes.  `w12_wide`: above 8 slots, bf16 expert weights stream as their lossless 12-bit copies in the wide
+        step (model.engine).  Not for expert-parallel engines, video prompts or streamed chunks."""
         from .serve import MAX_SLOTS_WIDE, Scheduler
         if not 1 <= slots <= MAX_SLOTS_WIDE:
             raise ValueError(f"serve: slots must be 1..{MAX_SLOTS_WIDE} (got {slots})")
         cfg = self.model.config
-        eng = self.model.engine(slots, int(max_prompt_tokens), 50 * int(max_audio_seconds), expert_weights=expert_weights)
+        eng = self.model.engine(slots, int(max_prompt_tokens), 50 * int(max_audio_seconds), expert_weights=expert_weights, w12_wide=w12_wide)
         eng.start_serving(int(max_prompt_tokens))
         app = self
 

@@ -106,8 +106,9 @@ struct umoe_engine {
     bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
     int prefill_fp8 = 0;         // the last prefill / admission ran its experts on the WP8 blocks (umoe_engine_info "prefill_fp8")
-    int expert_w12 = 0;          // the last dense decode layer ran the flat launch on its WP12 copies (umoe_engine_info "expert_w12")
+    int expert_w12 = 0;          // the last layer of the last decode step ran its expert launches on the WP12 copies: the flat launch, or the wide form's (umoe_engine_info "expert_w12")
     int expert_fp8 = 0;          // the last dense decode layer ran an fp8 launch: the flat one, or the wide form's (umoe_engine_info "expert_fp8")
+    bool w12_wide = false;       // umoe_engine_set_w12_wide: the wide form's gate/up and down launches stream the WP12 copies of a layer that has them
     bool fp8_wide = false;       // umoe_engine_set_fp8_wide: decode steps of 17..64 rows of an fp8 engine take the wide form on the WP8 weights
     int n_cu = 0;                // compute units of the device (UMOE_FAKE_CUS overrides: tests of the co-residency guards)
     bool tiled_prefill = true;   // UMOE_TILED_PREFILL=0: weight-streaming kernels for every row count (A/B, tests)
@@ -506,6 +507,12 @@ extern "C" int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_
     return 0;
 }
 
+extern "C" int umoe_engine_set_w12_wide(umoe_engine* e, int on) {
+    UMOE_REQUIRE(e, "umoe_engine_set_w12_wide: null engine");
+    e->w12_wide = on != 0;
+    return 0;
+}
+
 extern "C" int umoe_engine_set_fp8_wide(umoe_engine* e, int on) {
     UMOE_REQUIRE(e, "umoe_engine_set_fp8_wide: null engine");
     e->fp8_wide = on != 0;
@@ -888,6 +895,10 @@ static bool flat_w12_on() {      // UMOE_FLAT_W12=0: the flat launch on the WP16
     const char* v = getenv("UMOE_FLAT_W12");
     return !v || atoi(v) != 0;
 }
+static bool wide_w12_on() {      // UMOE_WIDE_W12=0: the wide step's expert launches on the WP16 packs although the switch is on (A/B, escape hatch)
+    const char* v = getenv("UMOE_WIDE_W12");
+    return !v || atoi(v) != 0;
+}
 static bool flat_moe_on() {
     const char* v = getenv("UMOE_FLAT_MOE");
     return !v || atoi(v) != 0;
@@ -999,6 +1010,11 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
     const uint16_t *wgu[12], *wdn[12], *bx[12], *bh[12];
     const uint8_t *wgu8[12], *wdn8[12];
     const int8_t *egu[12], *edn[12];
+    // the layer's WP12 copies ([routed, then shared], as umoe_engine_set_layer_w12 stored them): the same two launches, the same outputs
+    // bit for bit, 0.75 of the bytes.  A layer without copies (not packable) runs the WP16 launches
+    const bool w12 = !f8 && e->w12_wide && L.has_w12 && wide_w12_on();
+    const uint8_t *wgu12[12], *wdn12[12];
+    const uint32_t *mgu[12], *mdn[12];
     void *oh[12], *oy[12];
     int nb_gu[12], nb_dn[12], k_gu[12], k_dn[12];
     for (int x = 0; x < G; ++x) {
@@ -1010,6 +1026,10 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
             wgu8[x] = reinterpret_cast<const uint8_t*>(L.f8_gu[x]); egu[x] = L.f8e_gu[x];
             wdn8[x] = reinterpret_cast<const uint8_t*>(L.f8_dn[x]); edn[x] = L.f8e_dn[x];
         }
+        if (w12) {
+            wgu12[x] = reinterpret_cast<const uint8_t*>(L.w12_gu[x]); mgu[x] = L.w12m_gu[x];
+            wdn12[x] = reinterpret_cast<const uint8_t*>(L.w12_dn[x]); mdn[x] = L.w12m_dn[x];
+        }
         bx[x] = e->wide_in;
         oh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;      // [tiles][16 * I] in operand order
         bh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;
@@ -1018,13 +1038,16 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
         nb_dn[x] = D / 16; k_dn[x] = I;
     }
     if (f8) rc = umoe_gemm_wide_fp8(wgu8, egu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, UMOE_EPI_SWIGLU, 8, 1, s);
+    else if (w12) rc = umoe_gemm_wide_w12(wgu12, mgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, UMOE_EPI_SWIGLU, 8, 1, s);
     else rc = umoe_gemm_wide(wgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, nullptr, nullptr, UMOE_EPI_SWIGLU, 8, 1, s);
     if (rc) return rc;
     PROF(K_GATEUP);
     if (f8) rc = umoe_gemm_wide_fp8(wdn8, edn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, UMOE_EPI_BF16, 8, 2, s);
+    else if (w12) rc = umoe_gemm_wide_w12(wdn12, mdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, UMOE_EPI_BF16, 8, 2, s);
     else rc = umoe_gemm_wide(wdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, nullptr, nullptr, UMOE_EPI_BF16, 8, 2, s);
     if (rc) return rc;
     PROF(K_DOWN);
+    e->expert_w12 = w12 ? 1 : 0;
     return 0;
 }
 
@@ -1165,7 +1188,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     dn.max_k = Imax;
     dn.a = e->hbuf; dn.lda = Imax; dn.out = e->ybuf; dn.ldo = D; dn.n_valid = D;
     dn.prologue = UMOE_PRO_PLAIN; dn.epilogue = UMOE_EPI_BF16; dn.nt = dense ? 6 : 0;
-    e->expert_w12 = 0;
+    if (e->in_decode_step) e->expert_w12 = 0;      // (a decode step's word: an admission prefill between two replays of the step graph leaves it)
     switch (form) {
         case MOE_TILED:
             if ((rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s))) return rc;

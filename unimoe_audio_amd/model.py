@@ -376,23 +376,26 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         return out
 
     def engine(self, batch: int, max_prompt: int, max_tokens: int, attn_splits: int = 8, ep=None,
-               expert_weights: Optional[str] = None) -> "DecodeEngine":
+               expert_weights: Optional[str] = None, w12_wide: Optional[bool] = None) -> "DecodeEngine":
         """The decode engine for this shape, rebuilt when the shape, the weights (data pointer / version of any parameter) or the
         expert-parallel link changed.  `ep`: an unimoe_audio_amd.ep.EpLink (every rank of the link calls this together).
         `expert_weights` "bf16" / "fp8" / "fp8-only" (None: what quantize_experts_ left on this model, else "bf16").  An fp8 engine built
         here decodes batches of 9 to 32 requests in the wide form on the fp8 weights (DecodeEngine fp8_wide=True).  "fp8-only": the
-        engine holds the fp8 copy of every expert and nothing else -- its prefill runs on them too."""
+        engine holds the fp8 copy of every expert and nothing else -- its prefill runs on them too.  `w12_wide`: a bf16 engine
+        of more than 8 requests streams the lossless 12-bit copies of the expert weights in its wide step (DecodeEngine w12_wide; None:
+        WIDE_W12_DEFAULT, set by the measurement of DESIGN 4l)."""
         need_L = max_prompt + max_tokens + 8
         e = self._engine
         key = self._pack_key()
         fmt = expert_weights or quant.expert_format(self)
         fp8_wide = fmt in ("fp8", "fp8-only")
+        w12_wide = (WIDE_W12_DEFAULT if w12_wide is None else bool(w12_wide)) and fmt == "bf16" and 2 * batch > 16 and (ep is None or ep.size == 1)
         if (e is None or e.batch != batch or e.Lmax < need_L or e.Tmax < max_tokens + 64 or e.pack_key != key or e.ep is not ep
-                or e.expert_weights != fmt or e.fp8_wide != fp8_wide):
+                or e.expert_weights != fmt or e.fp8_wide != fp8_wide or e.w12_wide != w12_wide):
             if e is not None:
                 e.close()
             self._engine = DecodeEngine(self, batch, Lmax=need_L, Tmax=max_tokens + 64, attn_splits=attn_splits, ep=ep, expert_weights=fmt,
-                                        fp8_wide=fp8_wide)
+                                        fp8_wide=fp8_wide, w12_wide=w12_wide)
         return self._engine
 
     def quantize_experts_(self, fmt: str = "fp8", keep_bf16: bool = True):
@@ -527,13 +530,22 @@ class StreamUpdate(NamedTuple):
     rows: List[Tuple[int, int, int, bool]]
 
 
+# model.engine(): do the bf16 engines of more than 8 requests stream the WP12 copies in their wide step?  Decided by the A/B of
+# scripts/wide_w12_bench.py (profiles/wide_w12.json): on only if the WP12 leg beat the WP16 leg by more than the larger spread at
+# every measured batch.  Measured: 4.683 -> 4.189 / 5.539 -> 5.105 / 5.933 -> 5.349 ms per step at batch 16 / 24 / 32, spreads under 0.02 ms.
+WIDE_W12_DEFAULT = True
+
+
 class DecodeEngine:
     """Python face of umoe_engine_*: packs the weights once, owns the C engine and the decode state."""
 
     def __init__(self, model: UniAudioRVQQwen2_5VLMoEForConditionalGeneration, batch: int, Lmax: int, Tmax: int,
                  attn_splits: int = 8, max_pos: Optional[int] = None, ep=None, ep_connect: bool = True, expert_weights: Optional[str] = None,
-                 fp8_wide: bool = False):
-        """fp8_wide: an fp8 engine of 9 to 32 requests decodes in the wide form with the gate/up and down launches on the fp8 weights
+                 fp8_wide: bool = False, w12_wide: bool = False):
+        """w12_wide: a bf16 engine of 9 to 32 requests (ep 1) packs the WP12 copies of its expert weights (model.packed_w12(), shared with
+        the flat engines) and its wide step streams them in the gate/up and down launches (umoe_engine_set_w12_wide): the same outputs bit
+        for bit, 0.75 of the expert bytes; the WP16 packs stay (prefill and the ragged path read them).  False (default): nothing is packed.
+        fp8_wide: an fp8 engine of 9 to 32 requests decodes in the wide form with the gate/up and down launches on the fp8 weights
         (umoe_engine_set_fp8_wide).  False (default): such an engine refuses its decode step, as it always did; model.engine() passes True."""
         cfg = model.config
         fmt = expert_weights or quant.expert_format(model)
@@ -547,6 +559,7 @@ class DecodeEngine:
             quant.check_quantized(model)      # refuses stale fp8 copies (a weight edited after quantize_experts_)
         self.expert_weights = fmt
         self.fp8_wide = bool(fp8_wide)
+        self.w12_wide = bool(w12_wide)
         dev = model.device
         if dev.type != "cuda":
             raise L.UmoeError("DecodeEngine needs the model on a ROCm device; there is no CPU path in the product")
@@ -568,6 +581,8 @@ class DecodeEngine:
         # the flat expert launch (ep 1, <= 16 rows, bf16 experts) streams WP12 copies of the expert weights: the same bits in 0.75 of the
         # bytes.  UMOE_FLAT_W12=0: the WP16 launch, and nothing is packed.
         self.w12 = fmt == "bf16" and self.ep_size == 1 and self.rows <= 16 and os.environ.get("UMOE_FLAT_W12", "1") != "0"
+        # the wide step (17..64 rows) on the same copies, on request
+        self.w12_wide_on = self.w12_wide and fmt == "bf16" and self.ep_size == 1 and self.rows > 16
         h = C.c_void_p()
         L.check(L.lib().umoe_engine_create(C.byref(c), C.byref(h)), "umoe_engine_create")
         self.h = h
@@ -575,6 +590,8 @@ class DecodeEngine:
         self._pack_weights(max_pos)
         if self.fp8_wide:
             L.check(L.lib().umoe_engine_set_fp8_wide(self.h, 1), "umoe_engine_set_fp8_wide")
+        if self.w12_wide_on:
+            L.check(L.lib().umoe_engine_set_w12_wide(self.h, 1), "umoe_engine_set_w12_wide")
         if ep is not None and ep.size > 1 and ep_connect:
             ep.connect(self.h)
         self.tokens = None
@@ -639,7 +656,7 @@ class DecodeEngine:
             L.check(lib.umoe_engine_set_layer(self.h, li, C.byref(w)), "umoe_engine_set_layer")
             if self.expert_weights in ("fp8", "fp8-only"):
                 self._set_layer_fp8(li, ex, sh)
-            elif self.w12:
+            elif self.w12 or self.w12_wide_on:
                 self._set_layer_w12(li)
         emb, head = mpk["emb"], mpk["head"]
         # (slack: the temporal stream of a video advances by seconds-per-grid * tokens_per_second per frame pair, model.py:597-603)

@@ -312,6 +312,28 @@ def gemm_wide_fp8(w8: Sequence[torch.Tensor], exps: Sequence[Optional[torch.Tens
     return out
 
 
+def gemm_wide_w12(w12: Sequence[torch.Tensor], meta: Sequence[Optional[torch.Tensor]], n_blocks: Sequence[int], k: Sequence[int], rows: int,
+                  b: Sequence[torch.Tensor], out: Sequence[torch.Tensor], *, epilogue: int, waves: int, u: int, n_valid: Optional[int] = None):
+    """umoe_gemm_wide_w12: the gate/up (SwiGLU, 8, 1) or down (bf16, 8, 2) launch of gemm_wide on WP12 blocks `w12[g]` (uint8) with their
+    block records `meta[g]` (int32, 40 per block; unimoe_audio_amd/w12.py pack).  Bit-identical to gemm_wide on the WP16 weights."""
+    G = len(w12)
+    assert G == len(meta) == len(n_blocks) == len(k) == len(b) == len(out) and G >= 1
+
+    def ptrs(ts, strided=False):
+        return (C.c_void_p * G)(*[None if t is None else (_pv(t) if strided else _p(t).value) for t in ts])
+
+    row_major = epilogue != EPI_SWIGLU
+    ldo = out[0].stride(0) if row_major else 0
+    if row_major:
+        assert all(o.dim() == 2 and o.stride(0) == ldo and o.shape[0] >= rows for o in out)
+        if n_valid is None:
+            n_valid = out[0].shape[1]
+    L.check(L.lib().umoe_gemm_wide_w12(ptrs(w12), ptrs(meta), (C.c_int * G)(*[int(v) for v in n_blocks]), (C.c_int * G)(*[int(v) for v in k]), G,
+                                       rows, ptrs(b), ptrs(out, strided=row_major), ldo, n_valid or 0, epilogue, waves, u, _stream()),
+            "umoe_gemm_wide_w12")
+    return out
+
+
 def linear(x: torch.Tensor, w_packed: torch.Tensor, N: int, *, bias: Optional[torch.Tensor] = None, norm_w=None,
            rms_eps=1e-6, resid=None, out_f32=False, nt=0) -> torch.Tensor:
     """y = [rmsnorm](x) @ W^T (+bias) (+resid): one dense group."""
