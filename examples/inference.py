@@ -111,9 +111,10 @@ def main():
     ap.add_argument("--model", "-m", required=True)
     ap.add_argument("--device", "-d", type=int, default=0)
     ap.add_argument("--no-reuse", action="store_true")
-    ap.add_argument("--expert-weights", choices=["bf16", "fp8", "fp8-only"], default="bf16",
+    ap.add_argument("--expert-weights", choices=["bf16", "fp8", "fp8-only", "w12-only"], default="bf16",
                     help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step; with --serve at every --slots 1..32); "
-                         "fp8-only: the same and the bf16 expert weights are released (5.5 GB of experts instead of 27 GB, prefill on the e4m3 copies)")
+                         "fp8-only: the same and the bf16 expert weights are released (5.5 GB of experts instead of 27 GB, prefill on the e4m3 copies); "
+                         "w12-only: the bf16 expert weights are released in favour of their lossless 12-bit copies (no result changes by a bit; prefill on the copies)")
     ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
     ap.add_argument("--serve", action="store_true", help="with --requests: serve the list as a queue (UniMoEAudio.serve): --slots rows decode "
                                                          "together and a request is admitted as soon as a row is free; any number of requests")

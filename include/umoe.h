@@ -324,6 +324,15 @@ int umoe_tiled_gemm(const umoe_tgemm_args* a, umoe_stream_t stream);
  * there is no 256 x 256 ping-pong form).  UMOE_EPI_SWIGLU (no aux_out) and UMOE_EPI_BF16; gather list, device-side count and row offset
  * as umoe_tiled_gemm; k % 32 == 0.  Refused: w_kmajor, K windows (k_off / k_count / k_compact_*), bias, the other epilogues. */
 int umoe_tiled_gemm_wp8(const umoe_tgemm_args* a, const uint8_t* const* host_w8, const int8_t* const* host_exps, umoe_stream_t stream);
+/* The same GEMM on WP12 weights ("WP12" below; prefill of an engine that holds its bf16 experts as the lossless 12-bit copies only):
+ * host_w12[g] holds the WP12 blocks of group g's weight [n][k] (16-byte aligned) and host_meta[g] their block records (40 words per
+ * block, 4-byte aligned); with UMOE_EPI_SWIGLU host_w12[g] is the interleaved gate/up pair (n = intermediate size, n % 16 == 0) and
+ * serves gate and up.  The groups' w / w2 / ldw are not read.  tgemm_kernel's register-staging form with the granules rebuilt on their
+ * way into the LDS image and the blocks' exceptions patched into it, everything behind it shared: every output is bit-identical to
+ * umoe_tiled_gemm's small-tile kernel on the row-major weights (128- and 256-token tiles by the same rule; no ping-pong form).
+ * UMOE_EPI_SWIGLU (no aux_out) and UMOE_EPI_BF16; gather list, device-side count and row offset as umoe_tiled_gemm; k % 32 == 0,
+ * k / 32 < 127.  Refused: w_kmajor, K windows (k_off / k_count / k_compact_*), bias, the other epilogues. */
+int umoe_tiled_gemm_w12(const umoe_tgemm_args* a, const uint8_t* const* host_w12, const uint32_t* const* host_meta, umoe_stream_t stream);
 
 /* Weight-gradient form of the tiled GEMM: both operands are row-major with the CONTRACTION index as the row (tokens / expert slots), as
  * autograd holds activations and their gradients -- dW = dY^T X without transposed copies (torch.nn.functional.linear backward,
@@ -826,7 +835,13 @@ int umoe_engine_set_fp8_wide(umoe_engine* e, int on);
  * arrays [n_real + n_fix] (routed experts, then shared) of device pointers to WP12 gate/up pairs, their block records, WP12 down blocks
  * and theirs.  The flat expert launch of this layer then streams them (moe_flat_w12_kernel; the same outputs bit for bit, 0.75 of the
  * bytes), and so does the wide form with umoe_engine_set_w12_wide; every other form keeps reading the WP16 packs.  UMOE_FLAT_W12=0 selects the WP16 launch.  umoe_engine_info(e, "expert_w12")
- * = 1 when the last dense decode layer ran the WP12 launch. */
+ * = 1 when the last dense decode layer ran the WP12 launch.
+ * After umoe_engine_set_layer with EVERY bf16 expert pointer NULL (the layer shape of fp8-only) the layer becomes a w12-only layer: the
+ * WP12 copies are all it has.  Its experts run a prefill / admission of any row count on them (umoe_tiled_gemm_w12), its decode is the
+ * WP12 flat launch up to 16 rows and the WP12 wide form at every row count 17..64 (umoe_engine_set_w12_wide must be on); every pass or
+ * switch that would stream a bf16 expert weight is refused on the host before anything is enqueued, with a message that names the missing
+ * weights.  Layers may be mixed with layers that kept their bf16 weights.  umoe_engine_info: "w12_only_layers", "prefill_w12" (1: the last
+ * prefill or admission ran experts on WP12), "expert_bf16_resident" (0 only when no layer holds bf16 expert weights). */
 int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_t* const* gu12, const uint32_t* const* gu_m, const uint8_t* const* dn12,
                               const uint32_t* const* dn_m);
 /* on != 0: the wide form of a decode step of 17..64 rows (wide_mode and its size table are untouched: the switch changes which kernel a

@@ -159,6 +159,7 @@ EXPORTS = [
     "umoe_gemm_wide_fp8", "umoe_engine_set_fp8_wide", "umoe_tiled_gemm_wp8",
     "umoe_engine_set_layer_w12",
     "umoe_gemm_wide_w12", "umoe_engine_set_w12_wide",
+    "umoe_tiled_gemm_w12",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -293,6 +294,9 @@ def lib():
         L.umoe_gemm_wide_w12.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32,
                                          i32, i32, i32, vp]
         L.umoe_engine_set_w12_wide.argtypes = [vp, i32]
+        if not hasattr(L, "umoe_tiled_gemm_w12"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_tiled_gemm_w12): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_tiled_gemm_w12.argtypes = [C.POINTER(TGemmArgs), C.POINTER(vp), C.POINTER(vp), vp]
         L.umoe_rvq_from_codes.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.umoe_rvq_nearest.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.umoe_codec_ce_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]

@@ -91,9 +91,11 @@ class UniMoEAudio:
         (model.quantize_experts_): decode streams half the expert bytes, at every batch size from 1 to 32 requests; the whole model then
         computes with the dequantized weights.  "fp8-only": the same, and the bf16 expert parameters are released -- each expert as soon
         as it is loaded and quantized -- so the device holds the fp8 copy of every expert and nothing else (inference only: prefill runs
-        on the fp8 copies too, the module forward / training / saving raise)."""
-        if expert_weights not in ("bf16", "fp8", "fp8-only"):
-            raise ValueError(f"expert_weights must be 'bf16', 'fp8' or 'fp8-only' (got {expert_weights!r})")
+        on the fp8 copies too, the module forward / training / saving raise).  "w12-only": the bf16 expert parameters are released
+        in favour of the LOSSLESS 12-bit copies that bf16 engines decode from anyway; prefill runs on them too and no bit of any result
+        changes (inference only, like fp8-only)."""
+        if expert_weights not in ("bf16", "fp8", "fp8-only", "w12-only"):
+            raise ValueError(f"expert_weights must be 'bf16', 'fp8', 'fp8-only' or 'w12-only' (got {expert_weights!r})")
         if not torch.cuda.is_available():
             raise RuntimeError("UniMoEAudio needs a ROCm device: the accelerated path has no CPU fallback")
         torch.cuda.set_device(device_id)
@@ -108,11 +110,11 @@ class UniMoEAudio:
                 if not model_path or not os.path.exists(os.path.join(model_path, "config.json")):
                     raise FileNotFoundError("model_path must contain the reference config.json (and the safetensors shards)")
                 cfg = UniMoEAudioConfig.from_json(os.path.join(model_path, "config.json"))
-            if expert_weights == "fp8-only":
+            if expert_weights in ("fp8-only", "w12-only"):
                 from . import checkpoint
                 # built on the device, each expert quantized and released as its tensors arrive: the bf16 experts are never all resident
                 self.model = checkpoint.from_pretrained(UniAudioRVQQwen2_5VLMoEForConditionalGeneration, model_path or "", device=self.device,
-                                                        config=cfg, expert_weights="fp8-only")
+                                                        config=cfg, expert_weights=expert_weights)
             else:
                 self.model = UniAudioRVQQwen2_5VLMoEForConditionalGeneration(cfg)
                 self._load_weights(model_path)
@@ -121,6 +123,8 @@ class UniMoEAudio:
             self.model.quantize_experts_("fp8")
         elif expert_weights == "fp8-only":
             self.model.quantize_experts_("fp8", keep_bf16=False)      # (a model handed in; a loaded one is already there: idempotent)
+        elif expert_weights == "w12-only":
+            self.model.quantize_experts_("w12", keep_bf16=False)
         self._tokenizer = None
         self._dac = None
 

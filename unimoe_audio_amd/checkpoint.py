@@ -101,13 +101,15 @@ def load_checkpoint(model: torch.nn.Module, path: str, ep_rank: int = 0, ep_size
     Returns (missing, unexpected) like `load_state_dict(strict=False)`; with `strict_hot` a missing hot-path tensor is a KeyError
     and a shape mismatch a ValueError.  Cold tensors (vision tower, lm_head) may be absent on either side.
     expert_weights "fp8-only": an expert module is quantized and its bf16 parameters released (quant.quantize_expert_(keep_bf16=False)) as
-    soon as its three projections have arrived; parameters that were never allocated (dcmoe.unallocated_experts) are filled from the shard."""
+    soon as its three projections have arrived; parameters that were never allocated (dcmoe.unallocated_experts) are filled from the shard.
+    "w12-only": the same with the lossless WP12 copies (quant.w12_expert_); an expert that is not packable keeps its parameters, and so,
+    in the end, does its whole layer."""
     from . import quant
-    if expert_weights not in ("bf16", "fp8-only"):
-        raise ValueError(f"load_checkpoint: expert_weights must be 'bf16' or 'fp8-only' (got {expert_weights!r})")
+    if expert_weights not in ("bf16", "fp8-only", "w12-only"):
+        raise ValueError(f"load_checkpoint: expert_weights must be 'bf16', 'fp8-only' or 'w12-only' (got {expert_weights!r})")
     target = dict(model.state_dict(keep_vars=True))
     owner, arrived = {}, {}            # fp8-only: parameter key -> its expert module; module -> projections that have arrived
-    if expert_weights == "fp8-only":
+    if expert_weights in ("fp8-only", "w12-only"):
         names = {id(mod): mname for mname, mod in model.named_modules()}
         for layer in model.language_model.layers:
             routed, shared = quant.expert_modules(layer)
@@ -142,13 +144,22 @@ def load_checkpoint(model: torch.nn.Module, path: str, ep_rank: int = 0, ep_size
             got = arrived.setdefault(mod, set())
             got.add(key.rsplit(".", 2)[1])
             if len(got) == len(quant._PROJ):               # the expert is complete: its fp8 copy, then its bf16 parameters go
-                quant.quantize_expert_(mod, keep_bf16=False)
+                if expert_weights == "w12-only":
+                    quant.w12_expert_(mod)
+                else:
+                    quant.quantize_expert_(mod, keep_bf16=False)
                 mod.__dict__.pop("_unallocated", None)
     if expert_weights == "fp8-only":
         short = [k for k, mod in owner.items() if not quant.is_released(mod)]
         if short:
             raise KeyError(f"checkpoint {path!r} lacks expert tensors (fp8-only needs every expert complete), e.g. {short[:4]}")
         model._expert_weights = "fp8-only"
+    if expert_weights == "w12-only":
+        short = [k for k, mod in owner.items() if len(arrived.get(mod, ())) != len(quant._PROJ)]
+        if short:
+            raise KeyError(f"checkpoint {path!r} lacks expert tensors (w12-only needs every expert complete), e.g. {short[:4]}")
+        quant.w12_settle_layers_(model)
+        model._expert_weights = "w12-only"
     invalidate_packed(model)
     missing = [k for k in target if k not in seen]
     hot = [k for k in missing if not k.startswith(COLD_PREFIXES)]
@@ -290,14 +301,16 @@ def from_pretrained(cls, local_dir: str, torch_dtype=torch.bfloat16, attn_implem
     attn_implementation is accepted for signature compatibility: attention always runs on the HIP kernels.
     expert_weights "fp8" quantizes the experts after loading (model.quantize_experts_); "fp8-only" builds the model WITHOUT storage for
     the expert parameters and quantizes + releases each expert as soon as its three projections have arrived from the shards: all bf16
-    experts are never resident at once (the result equals loading followed by quantize_experts_(keep_bf16=False))."""
-    if expert_weights not in ("bf16", "fp8", "fp8-only"):
-        raise ValueError(f"expert_weights must be 'bf16', 'fp8' or 'fp8-only' (got {expert_weights!r})")
+    experts are never resident at once (the result equals loading followed by quantize_experts_(keep_bf16=False)).  "w12-only": the same
+    with the lossless WP12 copies (the result equals loading followed by quantize_experts_("w12", keep_bf16=False))."""
+    if expert_weights not in ("bf16", "fp8", "fp8-only", "w12-only"):
+        raise ValueError(f"expert_weights must be 'bf16', 'fp8', 'fp8-only' or 'w12-only' (got {expert_weights!r})")
     if expert_weights != "bf16" and ep_size != 1:
-        raise ValueError("fp8 expert weights are not supported expert parallel")
+        raise ValueError("fp8 expert weights are not supported expert parallel" if expert_weights != "w12-only" else
+                         "w12-only expert weights are not supported expert parallel")
     import contextlib
     from . import dcmoe
-    lean = dcmoe.unallocated_experts() if expert_weights == "fp8-only" else contextlib.nullcontext()
+    lean = dcmoe.unallocated_experts() if expert_weights in ("fp8-only", "w12-only") else contextlib.nullcontext()
     from .config import UniMoEAudioConfig
     if attn_implementation not in (None, "sdpa", "eager", "flash_attention_2"):
         raise ValueError(f"unknown attn_implementation {attn_implementation!r}")
@@ -321,7 +334,7 @@ def from_pretrained(cls, local_dir: str, torch_dtype=torch.bfloat16, attn_implem
                 model = cls(config)
     finally:
         torch.set_default_dtype(old)
-    load_checkpoint(model, local_dir, ep_rank=ep_rank, ep_size=ep_size, expert_weights="fp8-only" if expert_weights == "fp8-only" else "bf16")
+    load_checkpoint(model, local_dir, ep_rank=ep_rank, ep_size=ep_size, expert_weights=expert_weights if expert_weights in ("fp8-only", "w12-only") else "bf16")
     if expert_weights == "fp8":
         model.quantize_experts_("fp8")
     return model.eval()

@@ -33,6 +33,8 @@ struct LayerDev {
     std::vector<const uint16_t*> w12_gu, w12_dn;
     std::vector<const uint32_t*> w12m_gu, w12m_dn;
     bool has_w12 = false;
+    // a w12-only layer: umoe_engine_set_layer without any bf16 expert weight, then umoe_engine_set_layer_w12 -- the WP12 copies and nothing else
+    bool w12_only() const { return set && !exp_bf16 && has_w12 && !has_f8; }
 };
 
 struct Carver {
@@ -105,6 +107,7 @@ struct umoe_engine {
                                  // expert-parallel MoE half (umoe_engine_info; 1 was the removed box-grid launch)
     bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
                                  // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
+    int prefill_w12 = 0;         // the last prefill / admission ran experts on the WP12 copies (umoe_engine_info "prefill_w12")
     int prefill_fp8 = 0;         // the last prefill / admission ran its experts on the WP8 blocks (umoe_engine_info "prefill_fp8")
     int expert_w12 = 0;          // the last layer of the last decode step ran its expert launches on the WP12 copies: the flat launch, or the wide form's (umoe_engine_info "expert_w12")
     int expert_fp8 = 0;          // the last dense decode layer ran an fp8 launch: the flat one, or the wide form's (umoe_engine_info "expert_fp8")
@@ -249,8 +252,14 @@ static bool fp8_wide_on() {
     const char* v = getenv("UMOE_WIDE_DECODE");
     return !v || atoi(v) != 0;
 }
+static int w12_only_layers(const umoe_engine* e) {
+    int n = 0;
+    for (const LayerDev& L : e->layers) n += L.w12_only() ? 1 : 0;
+    return n;
+}
 static bool wide_mode(const umoe_engine* e, int n_tok) {
     if (!e->in_decode_step || !wide_shapes(e, n_tok)) return false;
+    if (w12_only_layers(e)) return true;      // at EVERY size, on the WP12 copies: a w12-only layer has no other path above 16 rows (w12_only_check saw the switches)
     return e->fp8 ? e->fp8_wide && fp8_wide_on() : wide_on(n_tok);
 }
 
@@ -493,7 +502,8 @@ extern "C" int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_
     UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer_w12: WP12 expert weights run on the flat expert launch only, not expert parallel (ep_size %d)",
                  e->c.ep_size);
     LayerDev& L = e->layers[layer];
-    UMOE_REQUIRE(L.set && L.exp_bf16 && !L.has_f8, "umoe_engine_set_layer_w12: umoe_engine_set_layer(%d) with the WP16 packs first (and no fp8 weights)", layer);
+    // (a layer that umoe_engine_set_layer received with every bf16 expert pointer NULL becomes a w12-only layer here)
+    UMOE_REQUIRE(L.set && !L.has_f8, "umoe_engine_set_layer_w12: umoe_engine_set_layer(%d) with the WP16 packs first (and no fp8 weights)", layer);
     const int G = e->c.n_real + e->c.n_fix;
     for (int i = 0; i < G; ++i)
         UMOE_REQUIRE(gu12[i] && gu_m[i] && dn12[i] && dn_m[i], "umoe_engine_set_layer_w12: layer %d group %d: null pointer", layer, i);
@@ -881,6 +891,8 @@ static int run_moe_ep(umoe_engine* e, int l, int n_tok, hipStream_t s) {
 // ------------------------------------------------------------------------------------ the MoE half of one layer (ep_size 1)
 // What a layer's router and experts are enqueued as: decided ONCE per layer on the host, from the shape and the switches, and each
 // form is one block of run_layer with no fall-through into another.
+#define W12_ONLY_MISSING "this engine holds no bf16 expert weights for its w12-only layers (exp_gu / exp_dn / sh_gu / sh_dn and rm_exp_* / rm_sh_* were not given: the WP12 copies are all there is)"
+extern "C" int umoe_moe_flat_plan_w12_probe(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix, double* out, int out_len);
 enum MoeForm {
     MOE_TILED,     // >= 64 rows (prefill): router + dispatch tables, tiled MFMA GEMMs on the row-major weights
     MOE_RAGGED,    // router + dispatch tables, weight-streaming GEMMs over the experts' ragged row lists
@@ -914,6 +926,7 @@ static MoeForm moe_form(const umoe_engine* e, const LayerDev& L, int n_tok) {
     if (!dense_mode(e, n_tok)) {
         // an fp8-only layer: the tiled kernel on the WP8 blocks at EVERY row count (nothing else reads e4m3 outside the decode launches;
         // fp8_only_check refused UMOE_TILED_PREFILL=0 and more than 12 groups before anything was enqueued)
+        // (a w12-only layer likewise: the tiled kernel on the WP12 copies, umoe_tiled_gemm_w12; w12_only_check refused the same switches)
         if (!L.exp_bf16) return MOE_TILED;
         return (L.has_rm && n_tok >= 64 && e->tiled_prefill && c.n_real + c.n_fix <= 12) ? MOE_TILED : MOE_RAGGED;
     }
@@ -939,15 +952,19 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     const umoe_engine_cfg& c = e->c;
     const int D = c.hidden, G = c.n_real + c.n_fix, Imax = c.inter_dyn > c.inter_shared ? c.inter_dyn : c.inter_shared;
     int rc;
-    const bool f8 = !L.exp_bf16;     // an fp8-only layer: the same two launches on the WP8 blocks (umoe_tiled_gemm_wp8), [routed, then shared]
+    const bool w12 = L.w12_only();   // a w12-only layer: the same two launches on the WP12 copies (umoe_tiled_gemm_w12), [routed, then shared]
+    const bool f8 = !L.exp_bf16 && !w12;      // an fp8-only layer: the same two launches on the WP8 blocks (umoe_tiled_gemm_wp8), [routed, then shared]
     const uint8_t* w8[12];
     const int8_t* ex[12];
+    const uint32_t* wm[12];
     umoe_tgroup_t tg[12];
     memset(tg, 0, sizeof(tg));
     for (int x = 0; x < G; ++x) {
         const umoe_group_t& src = gu_groups[x];
         const bool sh = x >= c.n_real;
-        if (f8) {
+        if (w12) {
+            w8[x] = reinterpret_cast<const uint8_t*>(L.w12_gu[x]); wm[x] = L.w12m_gu[x];
+        } else if (f8) {
             w8[x] = reinterpret_cast<const uint8_t*>(L.f8_gu[x]); ex[x] = L.f8e_gu[x];
         } else {
             tg[x].w = sh ? L.rm_sg[x - c.n_real] : L.rm_eg[x];
@@ -960,13 +977,15 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     umoe_tgemm_args ta{};
     ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok; ta.a = e->h2; ta.lda = D; ta.out = e->hbuf; ta.ldo = Imax;
     ta.epilogue = UMOE_EPI_SWIGLU;
-    if ((rc = f8 ? umoe_tiled_gemm_wp8(&ta, w8, ex, s) : umoe_tiled_gemm(&ta, s))) return rc;
+    if ((rc = w12 ? umoe_tiled_gemm_w12(&ta, w8, wm, s) : f8 ? umoe_tiled_gemm_wp8(&ta, w8, ex, s) : umoe_tiled_gemm(&ta, s))) return rc;
     PROF(K_GATEUP);
     memset(tg, 0, sizeof(tg));
     for (int x = 0; x < G; ++x) {
         const umoe_group_t& src = gu_groups[G + x];
         const bool sh = x >= c.n_real;
-        if (f8) {
+        if (w12) {
+            w8[x] = reinterpret_cast<const uint8_t*>(L.w12_dn[x]); wm[x] = L.w12m_dn[x];
+        } else if (f8) {
             w8[x] = reinterpret_cast<const uint8_t*>(L.f8_dn[x]); ex[x] = L.f8e_dn[x];
         } else {
             tg[x].w = sh ? L.rm_sd[x - c.n_real] : L.rm_ed[x];
@@ -978,9 +997,10 @@ static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* 
     umoe_tgemm_args td{};
     td.groups = tg; td.num_groups = G; td.max_rows = n_tok; td.a = e->hbuf; td.lda = Imax; td.out = e->ybuf; td.ldo = D;
     td.epilogue = UMOE_EPI_BF16;
-    if ((rc = f8 ? umoe_tiled_gemm_wp8(&td, w8, ex, s) : umoe_tiled_gemm(&td, s))) return rc;
+    if ((rc = w12 ? umoe_tiled_gemm_w12(&td, w8, wm, s) : f8 ? umoe_tiled_gemm_wp8(&td, w8, ex, s) : umoe_tiled_gemm(&td, s))) return rc;
     PROF(K_DOWN);
     if (f8) e->prefill_fp8 = 1;
+    if (w12) e->prefill_w12 = 1;
     return 0;
 }
 
@@ -1013,6 +1033,7 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
     // the layer's WP12 copies ([routed, then shared], as umoe_engine_set_layer_w12 stored them): the same two launches, the same outputs
     // bit for bit, 0.75 of the bytes.  A layer without copies (not packable) runs the WP16 launches
     const bool w12 = !f8 && e->w12_wide && L.has_w12 && wide_w12_on();
+    UMOE_REQUIRE(w12 || L.exp_bf16 || f8, "umoe_engine: the wide form of a w12-only layer runs on its WP12 copies only, and " W12_ONLY_MISSING);
     const uint8_t *wgu12[12], *wdn12[12];
     const uint32_t *mgu[12], *mdn[12];
     void *oh[12], *oy[12];
@@ -1164,7 +1185,9 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
         e->row_tiles = 1;
     }
     UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT && form != MOE_WIDE), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
-    UMOE_REQUIRE(L.exp_bf16 || (L.has_f8 && (form == MOE_TILED || form == MOE_FLAT || form == MOE_WIDE)),
+    UMOE_REQUIRE(!L.w12_only() || form == MOE_TILED || form == MOE_FLAT || form == MOE_WIDE,
+                 "umoe_engine: layer %d: this pass would stream bf16 expert weights, and " W12_ONLY_MISSING, l);
+    UMOE_REQUIRE(L.exp_bf16 || L.w12_only() || (L.has_f8 && (form == MOE_TILED || form == MOE_FLAT || form == MOE_WIDE)),
                  "umoe_engine: layer %d holds no bf16 expert weights (fp8-only) and this pass would stream them", l);
     umoe_router_args ra{};
     ra.x = e->x1; ra.gate_w = L.w.gate_w; ra.norm_w = L.w.post_norm; ra.h_out = e->h2; ra.S = n_tok; ra.D = D;
@@ -1239,6 +1262,8 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
                     rc = umoe_moe_flat_w12(&gu12, &dn12, m12u, m12d, e->ep_words + 64, 512 - 64, n_wg, s);
                     w12 = rc == 0;
                 }
+                UMOE_REQUIRE(rc != 1 || L.exp_bf16, "umoe_engine: layer %d: the flat expert launch on the WP12 copies cannot run (UMOE_FLAT_W12, schedule), and "
+                                                    W12_ONLY_MISSING, l);
                 if (rc == 1) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);      // (no WP12 copies, or no schedule at their byte cost)
             }
             UMOE_REQUIRE(rc != 1, "umoe_engine: the %sflat expert launch has no schedule for this shape on %d workgroups (layer %d)", e->fp8 ? "fp8 " : "", n_wg, l);
@@ -1356,6 +1381,7 @@ static int prefill_state(umoe_engine* e, const uint8_t* valid_host, int T, const
 
 static int fp8_step_check(umoe_engine* e);
 static int fp8_only_check(umoe_engine* e, int prefill_tok);
+static int w12_only_check(umoe_engine* e, int prefill_tok);
 
 extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const uint8_t* valid_host, int T, const int32_t* pos3_host,
                                        const int32_t* next_pos_host, umoe_stream_t stream) {
@@ -1374,7 +1400,9 @@ extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const 
     // a one-token prompt takes the dense decode layout, i.e. the fp8 flat launch on an fp8 engine: refused up front like a decode step
     if (e->fp8 && dense_mode(e, n_tok) && (rc = fp8_step_check(e))) return rc;
     if ((rc = fp8_only_check(e, dense_mode(e, n_tok) ? 0 : n_tok))) return rc;
+    if ((rc = w12_only_check(e, dense_mode(e, n_tok) ? 0 : n_tok))) return rc;
     e->prefill_fp8 = 0;
+    e->prefill_w12 = 0;
     if ((rc = ensure_workspace(e, n_tok))) return rc;
     if ((rc = build_groups(e, n_tok, s))) return rc;
     if ((rc = prefill_state(e, valid_host, T, pos3_host, next_pos_host, s))) return rc;
@@ -1593,7 +1621,9 @@ extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b
     hipStream_t s = (hipStream_t)stream;
     const int n_tok = 2 * T;
     if ((rc = fp8_only_check(e, n_tok))) return rc;       // (an admission prefill is never the dense layout)
+    if ((rc = w12_only_check(e, n_tok))) return rc;
     e->prefill_fp8 = 0;
+    e->prefill_w12 = 0;
     // positions cumsum(mask) - 1, masked -> 1; kv slot = t (prefill_state, for the pair)
     std::vector<int32_t> pos((size_t)3 * n_tok), kvp(n_tok);
     for (int r = 0; r < 2; ++r) {
@@ -1652,7 +1682,7 @@ extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* 
 #define FP8_ONLY_MISSING "this engine holds no bf16 expert weights (fp8-only: exp_gu / exp_dn / sh_gu / sh_dn and rm_exp_* / rm_sh_* were not given)"
 static bool fp8_only(const umoe_engine* e) {
     for (const LayerDev& L : e->layers)
-        if (L.set && !L.exp_bf16) return true;
+        if (L.set && !L.exp_bf16 && !L.w12_only()) return true;
     return false;
 }
 static int fp8_only_check(umoe_engine* e, int prefill_tok) {
@@ -1681,8 +1711,64 @@ static int fp8_only_check(umoe_engine* e, int prefill_tok) {
     return 0;
 }
 
+// The same for w12-only layers (umoe_engine_set_layer without any bf16 expert weight, then umoe_engine_set_layer_w12): their experts are
+// the WP12 copies and nothing else.  A prefill / admission of any row count runs them MOE_TILED on umoe_tiled_gemm_w12; a decode step is
+// the WP12 flat launch up to 16 rows and the WP12 wide form at EVERY row count 17..64.  Whatever would stream a bf16 expert weight of
+// such a layer is refused here, before anything is enqueued.  Layers may be mixed: a layer that was not packable keeps its bf16 weights
+// and its paths; the passes and switches below reach every layer, so one w12-only layer is enough to refuse them.
+static bool flat_w12_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix) {
+    static int key[7] = {-1, -1, -1, -1, -1, -1, -1};
+    static bool ans = false;
+    const int k[7] = {n_wg, S, D, I_dyn, I_sh, n_real, n_fix};
+    if (memcmp(k, key, sizeof(k)) == 0) return ans;      // (asked before every step: a plan search costs the host milliseconds)
+    bool ok = false;
+    if (n_wg >= 1 && n_wg <= 256) {
+        std::vector<double> out(3 + 9 * (size_t)n_wg);
+        ok = umoe_moe_flat_plan_w12_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out.data(), (int)out.size()) == 0 && out[0] != 0.0;
+    }
+    memcpy(key, k, sizeof(k));
+    ans = ok;
+    return ans;
+}
+static int w12_only_check(umoe_engine* e, int prefill_tok) {
+    if (!w12_only_layers(e)) return 0;
+    const umoe_engine_cfg& c = e->c;
+    UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: " W12_ONLY_MISSING ": not supported expert parallel (ep_size %d)", c.ep_size);
+    if (prefill_tok > 0) {
+        UMOE_REQUIRE(e->tiled_prefill, "umoe_engine: UMOE_TILED_PREFILL=0 runs the experts of a prefill on the weight-streaming GEMM (MOE_RAGGED) over WP16 packs, and "
+                                       W12_ONLY_MISSING);
+        UMOE_REQUIRE(c.n_real + c.n_fix <= 12, "umoe_engine: a prefill of %d experts per layer takes MOE_RAGGED over WP16 packs (the tiled launch has 12 groups), and "
+                                               W12_ONLY_MISSING, c.n_real + c.n_fix);
+        UMOE_REQUIRE(c.hidden % 32 == 0 && c.inter_dyn % 32 == 0 && (c.n_fix == 0 || c.inter_shared % 32 == 0) && c.hidden / 32 < 127 && c.inter_dyn / 32 < 127 &&
+                         c.inter_shared / 32 < 127,
+                     "umoe_engine: the tiled GEMM on WP12 weights needs hidden and intermediate sizes that are multiples of 32 below 4064 (%d, %d, %d), and "
+                     W12_ONLY_MISSING, c.hidden, c.inter_dyn, c.inter_shared);
+        return 0;
+    }
+    if (wide_shapes(e, c.rows)) {      // 17..64 rows: the wide form on the WP12 copies, at every size
+        UMOE_REQUIRE(fp8_wide_on(), "umoe_engine: UMOE_WIDE_DECODE=0 sends a decode step of %d rows to MOE_RAGGED over WP16 packs, and " W12_ONLY_MISSING, c.rows);
+        UMOE_REQUIRE(e->w12_wide && wide_w12_on(), "umoe_engine: UMOE_WIDE_W12=0 (or umoe_engine_set_w12_wide off) runs the wide form of %d rows on the WP16 packs, and "
+                                                   W12_ONLY_MISSING, c.rows);
+        return 0;
+    }
+    UMOE_REQUIRE(dense_mode(e, c.rows), "umoe_engine: a decode step of %d rows outside the dense layout takes MOE_RAGGED over WP16 packs, and " W12_ONLY_MISSING, c.rows);
+    UMOE_REQUIRE(flat_moe_on(), "umoe_engine: UMOE_FLAT_MOE=0 selects the launch-per-kernel forms (MOE_RIDERS / MOE_ROUTER) over WP16 packs, and " W12_ONLY_MISSING);
+    UMOE_REQUIRE(e->fuse_router, "umoe_engine: UMOE_FUSE_ROUTER=0 selects the launch-per-kernel form MOE_ROUTER over WP16 packs, and " W12_ONLY_MISSING);
+    UMOE_REQUIRE(flat_w12_on(), "umoe_engine: UMOE_FLAT_W12=0 runs the flat expert launch on the WP16 packs, and " W12_ONLY_MISSING);
+    UMOE_REQUIRE(c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096) && c.n_real + c.n_fix <= UMOE_MAXE,
+                 "umoe_engine: this shape selects the launch-per-kernel form MOE_ROUTER over WP16 packs (the flat expert launch is written for 9 + 2 experts at "
+                 "hidden 2048 / 4096), and " W12_ONLY_MISSING);
+    const int n_wg = flat_wgs(e);
+    UMOE_REQUIRE(n_wg > 0 && umoe_moe_flat_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix) &&
+                     flat_w12_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix),
+                 "umoe_engine: the flat expert launch on the WP12 copies has no schedule on %d compute units (MOE_RIDERS would stream WP16 packs), and " W12_ONLY_MISSING,
+                 e->n_cu);
+    return 0;
+}
+
 static int fp8_step_check(umoe_engine* e) {
     if (int rc = fp8_only_check(e, 0)) return rc;
+    if (int rc = w12_only_check(e, 0)) return rc;
     if (!e->fp8) return 0;
     const umoe_engine_cfg& c = e->c;
     UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: fp8 expert weights are not supported expert parallel (ep_size %d)", c.ep_size);
@@ -1769,7 +1855,14 @@ extern "C" int umoe_engine_info(umoe_engine* e, const char* key) {
     if (!strcmp(key, "expert_fp8")) return e->expert_fp8;
     if (!strcmp(key, "expert_w12")) return e->expert_w12;
     if (!strcmp(key, "prefill_fp8")) return e->prefill_fp8;
-    if (!strcmp(key, "expert_bf16_resident")) return fp8_only(e) ? 0 : 1;
+    if (!strcmp(key, "prefill_w12")) return e->prefill_w12;
+    if (!strcmp(key, "w12_only_layers")) return w12_only_layers(e);
+    if (!strcmp(key, "expert_bf16_resident")) {      // (a mixed engine -- w12-only layers next to layers that kept their bf16 weights -- still holds some)
+        if (fp8_only(e)) return 0;
+        for (const LayerDev& L : e->layers)
+            if (L.set && L.exp_bf16) return 1;
+        return w12_only_layers(e) ? 0 : 1;
+    }
     if (!strcmp(key, "n_cu")) return e->n_cu;
     return -1;
 }

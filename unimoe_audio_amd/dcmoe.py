@@ -160,7 +160,8 @@ class UniMoEAudioSparseMoeBlock(nn.Module):
             return self._packed
         ex, sh = self._experts(), self.fixed_real_moe
         if quant.is_released(self):
-            # fp8-only: there is no bf16 expert weight to pack -- the decode engine reads the WP8 copies (quant.py), the forward refuses
+            # fp8-only / w12-only: there is no bf16 expert weight to pack -- the decode engine reads the WP8 / WP12 copies (quant.py), the
+            # forward refuses
             self._packed, self._packed_key = dict(exp_gu=[], exp_dn=[], sh_gu=[], sh_dn=[], released=True), key
             return self._packed
         for p in self.parameters():
@@ -212,7 +213,7 @@ class UniMoEAudioSparseMoeBlock(nn.Module):
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 aux_balance_weight: Optional[torch.Tensor] = None):
         if quant.is_released(self):
-            raise L.UmoeError(quant._released_msg("UniMoEAudioSparseMoeBlock.forward"))
+            raise L.UmoeError(quant._released_msg("UniMoEAudioSparseMoeBlock.forward", quant.released_w12(self)))
         if not hidden_states.is_cuda:
             raise L.UmoeError("UniMoEAudioSparseMoeBlock.forward needs device tensors; the CPU restatement lives in "
                               "oracle/ and is test infrastructure only")

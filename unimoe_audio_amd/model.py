@@ -121,7 +121,8 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
     def from_pretrained(cls, local_dir: str, torch_dtype=torch.bfloat16, attn_implementation: Optional[str] = None, device=None,
                         ep_rank: int = 0, ep_size: int = 1, config=None, expert_weights: str = "bf16"):
         """Reference signature (utils/UniMoE_Audio_mod.py:79-92) for local checkpoint directories; see checkpoint.py.
-        expert_weights (not in the reference): "fp8" / "fp8-only" quantize the experts while loading."""
+        expert_weights (not in the reference): "fp8" / "fp8-only" quantize the experts while loading; "w12-only" keeps their lossless
+        12-bit copies only."""
         from . import checkpoint
         return checkpoint.from_pretrained(cls, local_dir, torch_dtype=torch_dtype, attn_implementation=attn_implementation,
                                           device=device, ep_rank=ep_rank, ep_size=ep_size, config=config, expert_weights=expert_weights)
@@ -230,7 +231,7 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         """kv_sink(layer, k [B, KVH, T, hd], v): called with every layer's roped keys / values (the buffers are reused by the next layer:
         copy what you keep) -- how an expert-parallel engine that holds only its local experts gets its KV cache from this forward."""
         if quant.is_released(self.language_model):
-            raise L.UmoeError(quant._released_msg("the module forward"))
+            raise L.UmoeError(quant._released_msg("the module forward", quant.released_w12(self.language_model)))
         cfg, dev = self.config, inputs_embeds.device
         B, T, D = inputs_embeds.shape
         H, KVH, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -364,11 +365,16 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         the shared ones -- or None for a layer with a block over the exception cap (it runs the bf16 launch)."""
         key = self._pack_key()
         if getattr(self, "_pk12", None) is not None and self._pk12_key == key:
-            return self._pk12
+            # (a released layer's entry is read from its modules every time, on the model's device: a move after the release is followed)
+            return [quant.w12_layer_copies(layer, self.device) if lp["moe"].get("released") else c
+                    for c, lp, layer in zip(self._pk12, self.packed()["layers"], self.language_model.layers)]
         D = self.config.hidden_size
         out = []
-        for lp in self.packed()["layers"]:
+        for lp, layer in zip(self.packed()["layers"], self.language_model.layers):
             pk = lp["moe"]
+            if pk.get("released"):      # w12-only: the copies made when the layer's parameters were released (quant.w12_expert_)
+                out.append(quant.w12_layer_copies(layer, self.device))
+                continue
             gu = [w12.pack(t.view(torch.int16), D // 32) for t in pk["exp_gu"] + pk["sh_gu"]]
             dn = [w12.pack(t.view(torch.int16), t.numel() // (D // 16 * 512)) for t in pk["exp_dn"] + pk["sh_dn"]]
             out.append(None if any(x is None for x in gu + dn) else dict(gu=gu, dn=dn))
@@ -379,9 +385,10 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
                expert_weights: Optional[str] = None, w12_wide: Optional[bool] = None) -> "DecodeEngine":
         """The decode engine for this shape, rebuilt when the shape, the weights (data pointer / version of any parameter) or the
         expert-parallel link changed.  `ep`: an unimoe_audio_amd.ep.EpLink (every rank of the link calls this together).
-        `expert_weights` "bf16" / "fp8" / "fp8-only" (None: what quantize_experts_ left on this model, else "bf16").  An fp8 engine built
+        `expert_weights` "bf16" / "fp8" / "fp8-only" / "w12-only" (None: what quantize_experts_ left on this model, else "bf16").  An fp8 engine built
         here decodes batches of 9 to 32 requests in the wide form on the fp8 weights (DecodeEngine fp8_wide=True).  "fp8-only": the
-        engine holds the fp8 copy of every expert and nothing else -- its prefill runs on them too.  `w12_wide`: a bf16 engine
+        engine holds the fp8 copy of every expert and nothing else -- its prefill runs on them too.  "w12-only": the engine
+        holds the lossless WP12 copies and nothing else; prefill, the flat launch and the wide step all read them.  `w12_wide`: a bf16 engine
         of more than 8 requests streams the lossless 12-bit copies of the expert weights in its wide step (DecodeEngine w12_wide; None:
         WIDE_W12_DEFAULT, set by the measurement of DESIGN 4l)."""
         need_L = max_prompt + max_tokens + 8
@@ -403,7 +410,8 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
         values W_deq in place; decode engines built afterwards stream the e4m3 copies (half the expert bytes): the flat expert launch
         up to 8 requests, the wide step's gate/up and down launches for 9 to 32.  keep_bf16=False: the bf16 expert parameters are
         released (inference only: engines built afterwards are "fp8-only" and prefill on the e4m3 copies; quant.dequantize_experts_
-        brings the parameters back)."""
+        brings the parameters back).  fmt "w12" with keep_bf16=False: the parameters are released in favour of their LOSSLESS WP12 copies
+        ("w12-only": no result changes by a bit; a layer that is not packable keeps its parameters)."""
         return quant.quantize_experts_(self, fmt, keep_bf16=keep_bf16)
 
     @torch.no_grad()
@@ -549,10 +557,16 @@ class DecodeEngine:
         (umoe_engine_set_fp8_wide).  False (default): such an engine refuses its decode step, as it always did; model.engine() passes True."""
         cfg = model.config
         fmt = expert_weights or quant.expert_format(model)
-        if fmt not in ("bf16", "fp8", "fp8-only"):
-            raise L.UmoeError(f"expert_weights must be 'bf16', 'fp8' or 'fp8-only' (got {fmt!r})")
-        if fmt != "fp8-only" and quant.is_released(model):
-            raise L.UmoeError(quant._released_msg(f"DecodeEngine(expert_weights={fmt!r})"))
+        if fmt not in ("bf16", "fp8", "fp8-only", "w12-only"):
+            raise L.UmoeError(f"expert_weights must be 'bf16', 'fp8', 'fp8-only' or 'w12-only' (got {fmt!r})")
+        if quant.is_released(model) and fmt != quant.expert_format(model):
+            raise L.UmoeError(quant._released_msg(f"DecodeEngine(expert_weights={fmt!r})", quant.released_w12(model)))
+        if fmt == "w12-only" and quant.expert_format(model) != "w12-only":
+            raise L.UmoeError("DecodeEngine(expert_weights='w12-only') needs a model whose expert parameters were released in favour of their "
+                              "WP12 copies: call model.quantize_experts_('w12', keep_bf16=False) first (an engine that only withheld the "
+                              "bf16 pointers would free nothing)")
+        if fmt == "w12-only" and ep is not None and ep.size > 1:
+            raise L.UmoeError("w12-only expert weights run on one GPU only: not with expert parallel decode")
         if fmt in ("fp8", "fp8-only"):
             if ep is not None and ep.size > 1:
                 raise L.UmoeError("fp8 expert weights run on the flat expert launch only: not with expert parallel decode")
@@ -580,9 +594,10 @@ class DecodeEngine:
         self.pack_key = model._pack_key()
         # the flat expert launch (ep 1, <= 16 rows, bf16 experts) streams WP12 copies of the expert weights: the same bits in 0.75 of the
         # bytes.  UMOE_FLAT_W12=0: the WP16 launch, and nothing is packed.
-        self.w12 = fmt == "bf16" and self.ep_size == 1 and self.rows <= 16 and os.environ.get("UMOE_FLAT_W12", "1") != "0"
+        self.w12 = (fmt == "bf16" and self.ep_size == 1 and self.rows <= 16 and os.environ.get("UMOE_FLAT_W12", "1") != "0") or fmt == "w12-only"
         # the wide step (17..64 rows) on the same copies, on request
-        self.w12_wide_on = self.w12_wide and fmt == "bf16" and self.ep_size == 1 and self.rows > 16
+        # (w12-only: always -- the WP12 copies are all such an engine has, prefill included: DESIGN 4m)
+        self.w12_wide_on = (self.w12_wide and fmt == "bf16" and self.ep_size == 1 and self.rows > 16) or fmt == "w12-only"
         h = C.c_void_p()
         L.check(L.lib().umoe_engine_create(C.byref(c), C.byref(h)), "umoe_engine_create")
         self.h = h
@@ -634,6 +649,8 @@ class DecodeEngine:
             self.sharded = sharded
             lo = 0 if sharded else self.ep_rank * e_loc
             only = self.expert_weights == "fp8-only"     # no bf16 expert weight goes to the engine: NULL for the WP16 packs and the rm_* tensors
+            if self.expert_weights == "w12-only":        # per layer: one that is not packable keeps its bf16 weights and its paths
+                only = m.packed_w12()[li] is not None
             eg = ed = sg = sd = None
             if not only:
                 eg, ed = arr(pk["exp_gu"][lo:lo + e_loc]), arr(pk["exp_dn"][lo:lo + e_loc])
@@ -674,6 +691,9 @@ class DecodeEngine:
         pk = self.model.packed_w12()[li]
         if pk is None:
             return
+        for d, m_ in pk["gu"] + pk["dn"]:
+            if d.device != self.dev or m_.device != self.dev:
+                raise L.UmoeError(f"layer {li}: a WP12 copy lives on {d.device}, the engine on {self.dev}")
         self._k(pk)
         arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         L.check(L.lib().umoe_engine_set_layer_w12(self.h, li, arr([d for d, _ in pk["gu"]]), arr([m for _, m in pk["gu"]]),
@@ -1054,7 +1074,9 @@ class DecodeEngine:
         """Host-side facts about the C engine (umoe_engine_info): "expert_launch" (0 two launches, 2 flat, 3 the one-launch
         expert-parallel MoE half, 4 the wide form of 17..64 rows; 1 was the removed box-grid launch and is never returned), "row_tiles"
         (16-row tiles per weight pass of the wide form, 1 otherwise), "n_cu", "expert_fp8" (1: the last dense decode layer ran an fp8
-        launch: the flat one, or gate/up and down of the wide form)."""
+        launch: the flat one, or gate/up and down of the wide form), "expert_w12" (the same for the WP12 copies), "prefill_fp8" / "prefill_w12"
+        (1: the last prefill or admission ran experts on the WP8 blocks / the WP12 copies), "w12_only_layers" (layers that hold their experts
+        as WP12 copies and nothing else), "expert_bf16_resident" (0 only when no layer holds bf16 expert weights)."""
         return int(L.lib().umoe_engine_info(self.h, key.encode()))
 
     def write_buffer(self, name: str, src: torch.Tensor, offset_bytes: int = 0) -> None:

@@ -634,6 +634,36 @@ def tiled_gemm_wp8(groups: Sequence[dict], a: torch.Tensor, out: torch.Tensor, *
     return out
 
 
+def tiled_gemm_w12(groups: Sequence[dict], a: torch.Tensor, out: torch.Tensor, *, max_rows: int, epilogue=EPI_BF16,
+                   aux_out: Optional[torch.Tensor] = None):
+    """umoe_tiled_gemm_w12: tiled_gemm on WP12 weights.  Each group dict has w12 (uint8 WP12 blocks; SwiGLU: the interleaved gate/up pair)
+    and meta (int32 block records) from w12.pack, n and k, optional rows / row_off / count tensors and static_count / a_row_base /
+    out_row_base / a_col_off / out_col_off ints.  Bit-identical to tiled_gemm's small-tile kernel on the row-major weights."""
+    G = len(groups)
+    arr = (L.TGroup * G)()
+    keep = []
+    for i, g in enumerate(groups):
+        for k in ("rows", "row_off", "count"):
+            t = g.get(k)
+            if t is not None:
+                keep.append(t)
+                setattr(arr[i], k, t.data_ptr())
+        for k in ("static_count", "a_row_base", "out_row_base", "a_col_off", "out_col_off", "w_kmajor"):
+            setattr(arr[i], k, int(g.get(k, 0)))
+        for k in ("bias", "k_off", "k_count"):      # (refused by the library: passed through so that the refusal is the library's)
+            t = g.get(k)
+            if t is not None:
+                keep.append(t)
+                setattr(arr[i], k, t.data_ptr())
+        arr[i].n, arr[i].k = int(g["n"]), int(g["k"])
+    w = (C.c_void_p * G)(*[None if g["w12"] is None else g["w12"].data_ptr() for g in groups])
+    m = (C.c_void_p * G)(*[None if g["meta"] is None else g["meta"].data_ptr() for g in groups])
+    args = L.TGemmArgs(groups=C.cast(arr, C.c_void_p), num_groups=G, max_rows=max_rows, a=_pv(a), lda=a.stride(0), resid=None, out=_pv(out),
+                       ldo=out.stride(-2), epilogue=epilogue, aux_out=_p(aux_out), ld_aux=0 if aux_out is None else aux_out.stride(0))
+    L.check(L.lib().umoe_tiled_gemm_w12(C.byref(args), w, m, _stream()), "umoe_tiled_gemm_w12")
+    return out
+
+
 def tiled_gemm_tn(groups: Sequence[dict], p: torch.Tensor, q: torch.Tensor, out: torch.Tensor, *, k_split: int = 1):
     """out_g[m][n] = sum_k p[k][p_col_off + m] * q[k][q_col_off + n] over the group's row window (umoe_tiled_gemm_tn): the weight-gradient
     product dW = dY^T X on row-major activations, no transposed copies.  Group dict: m, n, optional p / q / out tensors of its own,

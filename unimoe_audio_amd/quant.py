@@ -12,6 +12,11 @@ empty tensor, shapes stay in `_fp8["shape"]`), and an engine built on such a mod
 its prefill runs the tiled GEMM on the e4m3 blocks (umoe_tiled_gemm_wp8).  The module forward, training and state_dict saving of such a
 model raise; dequantize_experts_ restores W_deq exactly.
 
+w12-only (quantize_experts_("w12", keep_bf16=False)): the same release for the LOSSLESS 12-bit copies (w12.py) that bf16 engines
+already decode from.  Each expert's WP12 copies are built from its parameters (`_w12` on the module) and the parameters released; an engine
+built on such a model holds the WP12 copies and nothing else (prefill: umoe_tiled_gemm_w12).  No bit of any result changes, and
+dequantize_experts_ restores the parameters bit for bit.  A layer with a matrix that is not packable keeps its parameters.
+
 Load-time only (torch ops, CPU or GPU): not a hot path.  WP8 layout: include/umoe.h.
 """
 from typing import Tuple
@@ -93,7 +98,11 @@ def expert_modules(layer):
     return list(layer.mlp.dynamic_real_moe.deepspeed_moe.experts.deepspeed_experts), list(layer.mlp.fixed_real_moe)
 
 
-def _released_msg(what: str) -> str:
+def _released_msg(what: str, w12: bool = False) -> str:
+    if w12:
+        return (f"{what}: this model holds its expert weights as the lossless 12-bit copies only (quantize_experts_('w12', keep_bf16=False) "
+                "released the bf16 parameters); the decode engine runs on them (expert_weights='w12-only') -- call "
+                "unimoe_audio_amd.quant.dequantize_experts_(model) to get the bf16 parameters back (bit for bit)")
     return (f"{what}: this model holds its expert weights as fp8 only (quantize_experts_(keep_bf16=False) released the bf16 parameters); "
             "the decode engine runs on them (expert_weights='fp8-only') -- call unimoe_audio_amd.quant.dequantize_experts_(model) to get "
             "the bf16 parameters back (exact: W_deq)")
@@ -101,7 +110,12 @@ def _released_msg(what: str) -> str:
 
 def _refuse_state_dict(module, prefix, keep_vars):
     from . import _lib as L
-    raise L.UmoeError(_released_msg(f"state_dict of {prefix or 'an expert'}"))
+    raise L.UmoeError(_released_msg(f"state_dict of {prefix or 'an expert'}", hasattr(module, "_w12")))
+
+
+def released_w12(m) -> bool:
+    """True for a module (or anything holding one) whose expert parameters were released in favour of their WP12 copies."""
+    return any(bool(getattr(x, "_w12", None) and x._w12.get("released")) for x in m.modules())
 
 
 def _release(m):
@@ -116,10 +130,11 @@ def _release(m):
 
 def is_released(m) -> bool:
     """True for an expert module (or a DCMoE block / a model holding one) whose bf16 parameters were released."""
-    st = getattr(m, "_fp8", None)
-    if st is not None:
-        return bool(st.get("released"))
-    return any(bool(getattr(x, "_fp8", None) and x._fp8.get("released")) for x in m.modules())
+    for attr in ("_fp8", "_w12"):
+        st = getattr(m, attr, None)
+        if st is not None:
+            return bool(st.get("released"))
+    return any(bool(getattr(x, a, None) and getattr(x, a).get("released")) for x in m.modules() for a in ("_fp8", "_w12"))
 
 
 @torch.no_grad()
@@ -155,8 +170,13 @@ def quantize_experts_(model, fmt: str = "fp8", keep_bf16: bool = True):
     keep_bf16=False: each expert's three parameters are released as soon as its WP8 copy exists (the peak is ONE expert's bf16) and
     model._expert_weights becomes "fp8-only": the decode engine runs on the WP8 copies alone, everything else that needs the bf16
     parameters raises (dequantize_experts_ restores them)."""
+    if fmt == "w12":
+        return _w12_experts_(model, keep_bf16)
     if fmt != "fp8":
-        raise ValueError(f"quantize_experts_: unknown format {fmt!r} (only 'fp8')")
+        raise ValueError(f"quantize_experts_: unknown format {fmt!r} ('fp8' or 'w12')")
+    if expert_format(model) == "w12-only":
+        from . import _lib as L
+        raise L.UmoeError(_released_msg("quantize_experts_('fp8')", True))
     for layer in model.language_model.layers:
         routed, shared = expert_modules(layer)
         for m in routed + shared:
@@ -177,6 +197,12 @@ def _drop_packs(model):
 def dequantize_experts_(model):
     """Restores W_deq = q * 2^e into every expert parameter from its WP8 copy (exact), released or not: an fp8-only model becomes the
     model quantize_experts_(keep_bf16=True) leaves -- forward, training, saving and bf16 / fp8 engines work again."""
+    if expert_format(model) == "w12-only" or any(hasattr(x, "_w12") for x in model.modules()):
+        for layer in model.language_model.layers:
+            _w12_restore_layer(layer)
+        model._expert_weights = "bf16"
+        _drop_packs(model)
+        return model
     for layer in model.language_model.layers:
         routed, shared = expert_modules(layer)
         for m in routed + shared:
@@ -215,7 +241,8 @@ def expert_qe(m, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 def expert_format(model) -> str:
-    """"bf16", "fp8" (quantized, bf16 parameters kept as W_deq) or "fp8-only" (quantized, bf16 parameters released)."""
+    """"bf16", "fp8" (quantized, bf16 parameters kept as W_deq), "fp8-only" (quantized, bf16 parameters released) or "w12-only" (bf16
+    parameters released in favour of their lossless WP12 copies)."""
     return getattr(model, "_expert_weights", "bf16")
 
 
@@ -247,3 +274,119 @@ def check_quantized(model):
                 else:
                     raise L.UmoeError(f"layer {li} expert {xi} {name}: the weight changed after quantize_experts_('fp8') -- its fp8 copy is "
                                       "stale; quantize again")
+
+
+# ------------------------------------------------------------------------------------------------ w12-only
+@torch.no_grad()
+def w12_expert_(m) -> bool:
+    """One expert module: its WP12 copies (gate/up interleaved in WP16 order, down) on `m._w12`, the three parameters released as soon as
+    the copies exist.  False, and the module untouched, when one of its matrices is not packable (a block over the exception cap)."""
+    from . import w12
+    if getattr(m, "_w12", None) is not None and m._w12.get("released"):
+        return True
+    wg, wu, wd = (getattr(m, n).weight.detach() for n in _PROJ)
+    I, D = wg.shape
+    if wg.dtype != torch.bfloat16 or I % 16 or D % 32 or I % 32 or D // 32 >= 127 or I // 32 >= 127:
+        return False
+    # On a device the copies get their storage FIRST, at their exact sizes and from an empty cache: served from the blocks that the
+    # packer's temporaries and the released parameters leave behind, each would carry an unsplit remainder of up to 1 MiB that nothing
+    # else can use.  The parameters' blocks go back to the driver as soon as they are released.
+    cuda = wg.is_cuda
+    if cuda:
+        torch.cuda.empty_cache()
+        NBg, NBd = 2 * I // 16, D // 16
+        room = [(torch.empty(NBg * w12.block_bytes(D // 32), dtype=torch.uint8, device=wg.device),
+                 torch.empty(NBg * w12.META, dtype=torch.int32, device=wg.device)),
+                (torch.empty(NBd * w12.block_bytes(I // 32), dtype=torch.uint8, device=wg.device),
+                 torch.empty(NBd * w12.META, dtype=torch.int32, device=wg.device))]
+    gu = w12.pack(w12.wp16_gate_up(wg.contiguous(), wu.contiguous()), D // 32)
+    dn = w12.pack(w12.wp16_from_rows(wd.contiguous()), I // 32) if gu is not None else None
+    if gu is None or dn is None:
+        return False
+    if cuda:
+        for dst, src in zip(room, (gu, dn)):
+            dst[0].copy_(src[0]), dst[1].copy_(src[1])
+        gu, dn = room
+    m._w12 = dict(gu=gu, dn=dn, shape={n: tuple(getattr(m, n).weight.shape) for n in _PROJ}, released=True, hook=None)
+    for name in _PROJ:
+        p = getattr(m, name).weight
+        p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+    m._w12["hook"] = m.register_state_dict_pre_hook(_refuse_state_dict)
+    if cuda:
+        del wg, wu, wd
+        torch.cuda.empty_cache()
+    return True
+
+
+@torch.no_grad()
+def w12_restore_expert_(m):
+    """The three parameters of a released expert module back from its WP12 copies, bit for bit; the copies are dropped."""
+    from . import w12
+    st = getattr(m, "_w12", None)
+    if st is None:
+        return m
+    (I, D) = st["shape"]["gate_proj"]
+    both = w12.rows_from_wp16(w12.unpack(st["gu"][0], st["gu"][1], D // 32), 2 * I, D).view(I // 16, 2, 16, D)      # (the inverse of wp16_gate_up)
+    vals = dict(gate_proj=both[:, 0].reshape(I, D), up_proj=both[:, 1].reshape(I, D),
+                down_proj=w12.rows_from_wp16(w12.unpack(st["dn"][0], st["dn"][1], I // 32), D, I))
+    for name in _PROJ:
+        p = getattr(m, name).weight
+        p.data = vals[name].to(device=p.device, dtype=p.dtype).contiguous()
+    if st.get("hook") is not None:
+        st["hook"].remove()
+    del m._w12
+    m.__dict__.pop("_unallocated", None)
+    return m
+
+
+def _w12_restore_layer(layer):
+    routed, shared = expert_modules(layer)
+    for m in routed + shared:
+        w12_restore_expert_(m)
+
+
+def w12_settle_layers_(model):
+    """A layer is w12-only as a whole or not at all (the engine's layers are): where one expert of a layer kept its parameters (not
+    packable), the layer's released experts get theirs back."""
+    for layer in model.language_model.layers:
+        routed, shared = expert_modules(layer)
+        if any(getattr(m, "_w12", None) is None for m in routed + shared):
+            _w12_restore_layer(layer)
+
+
+@torch.no_grad()
+def _w12_experts_(model, keep_bf16: bool):
+    from . import _lib as L
+    if keep_bf16:
+        raise L.UmoeError("quantize_experts_('w12', keep_bf16=True): nothing to do -- bf16 engines already stream the lossless WP12 copies of "
+                          "the expert weights (DESIGN 4k, 4l); keep_bf16=False releases the bf16 parameters in their favour ('w12-only')")
+    if expert_format(model) in ("fp8", "fp8-only"):
+        raise L.UmoeError(f"quantize_experts_('w12'): this model's experts are {expert_format(model)!r}; dequantize_experts_ first")
+    for layer in model.language_model.layers:
+        routed, shared = expert_modules(layer)
+        if all(getattr(m, "_w12", None) is not None for m in routed + shared):
+            continue                      # idempotent
+        for m in routed + shared:         # (each expert released as soon as its copies exist: the peak is one expert's bf16)
+            if not w12_expert_(m):
+                _w12_restore_layer(layer)     # not packable: the whole layer stays as it was
+                break
+    model._expert_weights = "w12-only"
+    _drop_packs(model)
+    return model
+
+
+def w12_layer_copies(layer, device=None):
+    """dict(gu=[(blocks, records)], dn=[...]) over the routed, then the shared experts of a released layer (None: the layer kept its
+    parameters).  The copies live in a plain dict on the expert module, which nn.Module.to() does not move: with `device` a copy that
+    is elsewhere (a model released on the host, then moved) is moved there first, once, in the module's own store."""
+    routed, shared = expert_modules(layer)
+    mods = routed + shared
+    if not mods or any(getattr(m, "_w12", None) is None for m in mods):
+        return None
+    if device is not None:
+        device = torch.device(device)
+        for m in mods:
+            for k in ("gu", "dn"):
+                if any(t.device != device for t in m._w12[k]):
+                    m._w12[k] = tuple(t.to(device) for t in m._w12[k])
+    return dict(gu=[m._w12["gu"] for m in mods], dn=[m._w12["dn"] for m in mods])
