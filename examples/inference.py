@@ -49,7 +49,7 @@ def load_requests(path):
 
 
 def batch_inference(requests_file, model_path, output="./output", device=0, reuse=True, expert_weights="bf16", stream=False, serve=False,
-                    slots=8):
+                    slots=8, prefix_cache=False):
     global _MODEL
     from unimoe_audio_amd.api import UniMoEAudio
     try:
@@ -60,8 +60,11 @@ def batch_inference(requests_file, model_path, output="./output", device=0, reus
             # continuous batching: `slots` rows decode together, a request takes a row as soon as one is free
             import time
             t0, paths = time.perf_counter(), {}
-            for i, path in _MODEL.serve(reqs, slots=slots, output_dir=output, max_audio_seconds=max(r.max_audio_seconds for r in reqs)):
-                print(f"{time.perf_counter() - t0:8.3f} s  request {i}  {path}", flush=True)
+            for i, path in _MODEL.serve(reqs, slots=slots, output_dir=output, max_audio_seconds=max(r.max_audio_seconds for r in reqs),
+                                        prefix_cache=prefix_cache):
+                hit, n = _MODEL.served_prefix.get(i, (False, 0))
+                note = f"  (voice prefix of {n} tokens {'reused' if hit else 'prefilled'})" if n else ""
+                print(f"{time.perf_counter() - t0:8.3f} s  request {i}  {path}{note}", flush=True)
                 paths[i] = path
             return [paths[i] for i in sorted(paths)]
         if not stream:
@@ -119,11 +122,15 @@ def main():
     ap.add_argument("--serve", action="store_true", help="with --requests: serve the list as a queue (UniMoEAudio.serve): --slots rows decode "
                                                          "together and a request is admitted as soon as a row is free; any number of requests")
     ap.add_argument("--slots", type=int, default=8, help="rows of the serving batch (1..32)")
+    ap.add_argument("--prefix-cache", action="store_true", help="with --serve: speech requests with the same reference audio and prompt text share one "
+                                                                "prefilled voice prompt; each admission prefills only its sentence")
     a = ap.parse_args()
     if a.requests:
         if a.serve and a.stream:
             ap.error("--serve does not stream chunks")
-        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream, a.serve, a.slots)
+        if a.prefix_cache and not a.serve:
+            ap.error("--prefix-cache goes with --serve")
+        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream, a.serve, a.slots, a.prefix_cache)
         sys.exit(0 if out else 1)
     if not a.task or a.input is None:
         ap.error("--task and --input are required (or --requests FILE.json)")

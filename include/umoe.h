@@ -912,6 +912,31 @@ int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b, const uin
                       int prefill_step, int prefix_len, umoe_stream_t stream);
 int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step,
                                int prefix_len, umoe_stream_t stream);
+/* Prefix reuse across admissions (ep_size 1).  A prefix STORE is a caller-owned bf16 device buffer [layers][2 (K, V)][kv_heads][P][head_dim]:
+ * the roped keys and the values of prompt tokens 0 .. P - 1 at rope positions 0 .. P - 1.
+ * umoe_kv_prefix_copy: ONE launch over all layers, K and V and every kv head, in 16-byte pieces (head_dim % 8 == 0).  jobs_host holds
+ *   n_jobs (1..8) records {row, i0, s0, n}.  extract == 0 (install): store tokens [i0, i0 + n) -> slots [s0, s0 + n) of cache row `row`;
+ *   extract != 0: the other way.  The caches are [layers][rows][kv_heads][Lmax][head_dim].  Every range is checked on the host (0 <= i0,
+ *   i0 + n <= P, 0 <= s0, s0 + n <= Lmax, 0 <= row < rows, n >= 0; no two installs overlap in a row, no two extracts in the store);
+ *   nothing outside the named ranges is written.
+ * umoe_engine_prefix_build: runs x_prefix [P][D] ALONE as one row of P tokens (kv_start 0, positions 0 .. P - 1) through the prefill body
+ *   -- tiled at P >= 64, ragged below, as the token count selects everywhere -- into cache row 2b of the FREE pair b, then extracts slots
+ *   [0, P) into `store`.  The store's bits depend on the prefix and the engine's weights only.  kv_start of row 2b becomes 0.
+ *   The host cannot see whether pair b is free: building through a pair that is decoding overwrites its keys and corrupts it.
+ * umoe_engine_admit_prefix: umoe_engine_admit of a pair whose rows both begin with the store's P tokens.  valid_host [2][T] is the mask
+ *   of the FULL pair (row r: first_r pad columns, its prefix token i in slot first_r + i); x_suffix [2 * (T - P)][D] are columns [P, T)
+ *   of the pair's embeddings.  Per row, store tokens [0, max(P - first_r, 0)) are installed into slots [first_r, P); columns [P, T) of
+ *   both rows then run the prefill body behind the cached keys (kv slot P + j, positions from the full mask, q_pos0 P) -- in the shorter
+ *   row these columns begin with its last first_r prefix tokens, recomputed -- and batch entry b is reset as umoe_engine_admit resets it.
+ *   Refused before anything is enqueued: T - P < 2, P < 1, a NULL store, P or 2 * (T - P) beyond the reservation, and whatever
+ *   umoe_engine_admit refuses -- a row that is not left padded among it, which is what keeps every installed prefix token valid and
+ *   below column P. */
+int umoe_kv_prefix_copy(uint16_t* k_cache, uint16_t* v_cache, uint16_t* store, int layers, int rows, int kv_heads, int Lmax, int head_dim,
+                        int P, const int32_t* jobs_host, int n_jobs, int extract, umoe_stream_t stream);
+int umoe_engine_prefix_build(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* x_prefix, int P, uint16_t* store,
+                             umoe_stream_t stream);
+int umoe_engine_admit_prefix(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* store, int P, const uint16_t* x_suffix,
+                             const uint8_t* valid_host, int T, int prefill_step, int prefix_len, umoe_stream_t stream);
 /* Expert parallel decode (ep_size > 1).  umoe_engine_set_layer then takes exp_gu / exp_dn of the n_real / ep_size LOCAL experts
  * (global ids [ep_rank * E_loc, (ep_rank + 1) * E_loc), core.py:505) and EITHER the row-major tensors of ALL n_real experts (the
  * engine then prefills replicated on its tiled path) OR no row-major expert tensors at all (rm_exp_* NULL: the rank holds its local
@@ -933,6 +958,10 @@ int umoe_engine_ep_error(umoe_engine* e, umoe_stream_t stream, int* code_out);
  * NULL switches the probe off.  With a probe the layer's combine runs as its own launch (it cannot ride in a QKV launch whose input
  * is replaced); every other launch is the decode step's own. */
 int umoe_engine_set_probe(umoe_engine* e, const uint16_t* teach_x, uint16_t* dump_x1, uint16_t* dump_x, uint16_t* dump_logits);
+/* router dump of ADMISSION passes for parity tests (umoe_engine_admit, umoe_engine_prefix_build, umoe_engine_admit_prefix): after every
+ * layer of a pass of at most cap_tok tokens, the expert masks [tokens][E] int32 and the bf16 gate logits [tokens][E] of the pass's tokens
+ * are copied to mask_out / logits_out [layers][cap_tok][E] (either may be NULL).  cap_tok 0 switches it off. */
+int umoe_engine_set_admit_dump(umoe_engine* e, int32_t* mask_out, uint16_t* logits_out, int cap_tok);
 /* host-side facts about the engine: "expert_launch" = what the last dense decode layer enqueued for its experts (0 gate/up and down as
  * two launches, 2 the flat launch moe_flat_kernel, 3 the one-launch expert-parallel MoE half moe_ep_kernel; 1 was the box-grid fused
  * launch, which no longer exists, and is never returned), "n_cu" = compute units the co-residency guards assume; -1 for an unknown key */

@@ -160,6 +160,8 @@ EXPORTS = [
     "umoe_engine_set_layer_w12",
     "umoe_gemm_wide_w12", "umoe_engine_set_w12_wide",
     "umoe_tiled_gemm_w12",
+    "umoe_kv_prefix_copy", "umoe_engine_prefix_build", "umoe_engine_admit_prefix",
+    "umoe_engine_set_admit_dump",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -273,6 +275,12 @@ def lib():
         L.umoe_engine_reserve.argtypes = [vp, i32]
         L.umoe_engine_admit.argtypes = [vp, C.POINTER(DecodeIO), i32, vp, vp, i32, i32, i32, vp]
         L.umoe_engine_admit_external.argtypes = [vp, C.POINTER(DecodeIO), i32, vp, i32, i32, i32, vp]
+        if not hasattr(L, "umoe_engine_admit_prefix"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_engine_admit_prefix): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_kv_prefix_copy.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]
+        L.umoe_engine_prefix_build.argtypes = [vp, C.POINTER(DecodeIO), i32, vp, i32, vp, vp]
+        L.umoe_engine_admit_prefix.argtypes = [vp, C.POINTER(DecodeIO), i32, vp, i32, vp, vp, i32, i32, i32, vp]
+        L.umoe_engine_set_admit_dump.argtypes = [vp, vp, vp, i32]
         if not hasattr(L, "umoe_gemm_wide"):
             raise UmoeError(f"{_SO} predates this package (no umoe_gemm_wide): rebuild it (`make -C unimoe_audio_amd/csrc`)")
         L.umoe_gemm_wide.argtypes = [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32,

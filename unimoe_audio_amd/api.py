@@ -21,7 +21,9 @@ import torch
 from .codec_utils import DecoderOutput, generate_output, prepare_audio_prompt, preprocess_codec
 from .config import UniMoEAudioConfig
 from .model import UniAudioRVQQwen2_5VLMoEForConditionalGeneration
+from .prefix_plan import split_point
 from .row_params import scaled as _scaled
+from .serve import VoicePrompt
 
 
 class AudioChunk(NamedTuple):
@@ -61,6 +63,7 @@ class SpeechRequest:
     eos_prob_mul_factor: float = 1.0
     do_sample: bool = True
     seed: int = 0
+    voice: Optional[VoicePrompt] = None      # UniMoEAudio.voice(...): stands for prompt_wav / prompt_codec, and serve() reuses its prefilled prefix
 
 
 @dataclass
@@ -298,39 +301,67 @@ class UniMoEAudio:
                        prompt_wav: Optional[str] = None, output_dir: str = "./", max_audio_seconds: int = 10,
                        min_audio_seconds: int = 2, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                        caption=None, prompt_text=None, prompt_codec=None, save_name: str = "speech", cfg_scale: float = 1.0,
-                       eos_prob_mul_factor: float = 1.0, do_sample: bool = True, seed: int = 0, **_) -> List[str]:
-        enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec)
+                       eos_prob_mul_factor: float = 1.0, do_sample: bool = True, seed: int = 0, voice: Optional[VoicePrompt] = None,
+                       **_) -> List[str]:
+        """voice: a VoicePrompt (UniMoEAudio.voice) in place of prompt_wav / prompt_codec: its reference audio is already encoded"""
+        enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec, voice)
         audios = self.generate_codes(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, cfg_scale,
                                      temperature, top_p, cfg_filter_top_k, eos_prob_mul_factor, do_sample, seed)
         return self._finish(audios, output_dir, save_name)
 
-    def _speech_prompt(self, transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec):
+    def _speech_prompt(self, transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec, voice=None):
         texts_in = self._texts(transcription if transcription is not None else caption)
         ptxt = prompt_transcription if prompt_transcription is not None else prompt_text
+        if voice is not None:
+            pc = voice.pc
+            ptxt = voice.prompt_transcription if ptxt is None else ptxt
+        else:
+            if prompt_codec is None:
+                if prompt_wav is None:
+                    raise ValueError("Please provide a reference audio file.")
+                prompt_codec = self.dac.encode(prompt_wav)
+            pc = preprocess_codec(self.model.config, prompt_codec)
+        texts = []
+        for t in texts_in:
+            texts += self._speech_texts(ptxt, pc.shape[0], t)
+        enc = self.tokenizer(texts, add_special_tokens=False, return_tensors="pt", padding=True)
+        codec = pc.unsqueeze(0).expand(len(texts), -1, -1).reshape(-1, pc.shape[1])
+        return enc, codec
+
+    @staticmethod
+    def _voice_prefix_text(ptxt: str, n_placeholders: int) -> str:
+        """the text every prompt of one voice begins with, negative and positive row alike: up to and including <|SPEECH_START|>"""
+        return (SYSTEM_MESSAGE + INPUT_FORMAT.split("{}")[0] + "<|SPEECH_PROMPT_START|>" + ptxt + "<|SPEECH_PROMPT_END|>" + "<|VOICE_PROMPT_START|>" +
+                "<|AUDIO_PLACEHOLDER|>" * n_placeholders + "<|VOICE_PROMPT_END|>" + "<|SPEECH_START|>")
+
+    def _speech_texts(self, ptxt: str, n_placeholders: int, sentence: str) -> List[str]:
+        """the (negative, positive) prompt pair of one sentence"""
+        head, tail = self._voice_prefix_text(ptxt, n_placeholders), "<|SPEECH_END|>" + INPUT_FORMAT.split("{}")[1] + AUDIO_START
+        return [head + tail, head + sentence + tail]
+
+    @torch.no_grad()
+    def voice(self, prompt_transcription: str, prompt_wav: Optional[str] = None, prompt_codec=None) -> VoicePrompt:
+        """A voice to speak many sentences in: the reference audio is encoded once, its prompt prefix (system message, prompt
+        transcription, the audio placeholders, up to and including <|SPEECH_START|>) tokenised and embedded once, and serve() prefills
+        that prefix once per engine and installs its K / V into every request of the voice (SpeechRequest.voice)."""
         if prompt_codec is None:
             if prompt_wav is None:
                 raise ValueError("Please provide a reference audio file.")
             prompt_codec = self.dac.encode(prompt_wav)
-        cfg = self.model.config
-        pc = preprocess_codec(cfg, prompt_codec)
-        prompt_caption = ("<|SPEECH_PROMPT_START|>" + ptxt + "<|SPEECH_PROMPT_END|>" + "<|VOICE_PROMPT_START|>" +
-                          "<|AUDIO_PLACEHOLDER|>" * pc.shape[0] + "<|VOICE_PROMPT_END|>")
-        wrap = lambda x: prompt_caption + "<|SPEECH_START|>" + x + "<|SPEECH_END|>"   # noqa: E731
-        texts = []
-        for t in texts_in:
-            texts += [SYSTEM_MESSAGE + INPUT_FORMAT.format(wrap("")) + AUDIO_START,
-                      SYSTEM_MESSAGE + INPUT_FORMAT.format(wrap(t)) + AUDIO_START]
-        enc = self.tokenizer(texts, add_special_tokens=False, return_tensors="pt", padding=True)
-        codec = pc.unsqueeze(0).expand(len(texts), -1, -1).reshape(-1, pc.shape[1])
-        return enc, codec
+        pc = preprocess_codec(self.model.config, prompt_codec)
+        enc = self.tokenizer([self._voice_prefix_text(prompt_transcription, pc.shape[0])], add_special_tokens=False, return_tensors="pt", padding=True)
+        ids = enc.input_ids[0][enc.attention_mask[0].bool()]
+        x = self.model.calculate_input_embedding(ids[None].to(self.device), pc.to(self.device))[0].contiguous()
+        return VoicePrompt(prompt_transcription, prompt_codec, pc, ids.tolist(), x)
 
     def text_to_speech_stream(self, transcription: Union[str, List[str], None] = None, prompt_transcription: Optional[str] = None,
                               prompt_wav: Optional[str] = None, output_dir: Optional[str] = None, max_audio_seconds: int = 10,
                               min_audio_seconds: int = 2, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,
                               caption=None, prompt_text=None, prompt_codec=None, save_name: str = "speech", cfg_scale: float = 1.0,
-                              eos_prob_mul_factor: float = 1.0, do_sample: bool = True, chunk_frames: int = 25, seed: int = 0, **_):
+                              eos_prob_mul_factor: float = 1.0, do_sample: bool = True, chunk_frames: int = 25, seed: int = 0,
+                              voice: Optional[VoicePrompt] = None, **_):
         """text_to_speech() as a stream of AudioChunks (see _stream_audio); output_dir: also write text_to_speech()'s wav files at the end"""
-        enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec)
+        enc, codec = self._speech_prompt(transcription, prompt_transcription, prompt_wav, caption, prompt_text, prompt_codec, voice)
         return self._stream_audio(enc.input_ids, enc.attention_mask, codec, max_audio_seconds, min_audio_seconds, chunk_frames, output_dir,
                                   save_name, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
                                   eos_prob_mul_factor=eos_prob_mul_factor, do_sample=do_sample, seed=seed)
@@ -351,7 +382,7 @@ class UniMoEAudio:
         encs, codecs = [], []
         for r in requests:
             if isinstance(r, SpeechRequest):
-                enc, codec = self._speech_prompt(r.transcription, r.prompt_transcription, r.prompt_wav, None, None, r.prompt_codec)
+                enc, codec = self._speech_prompt(r.transcription, r.prompt_transcription, r.prompt_wav, None, None, r.prompt_codec, r.voice)
                 codecs.append(codec)
             elif isinstance(r, MusicRequest):
                 enc = self._music_prompt(r.caption)
@@ -381,7 +412,8 @@ class UniMoEAudio:
 
     @torch.no_grad()
     def serve(self, requests, slots: int = 8, output_dir: Optional[str] = "./", poll_every: int = 16, max_prompt_tokens: int = 512,
-              max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None, w12_wide: Optional[bool] = None):
+              max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None, w12_wide: Optional[bool] = None,
+              prefix_cache: bool = False, prefix_cache_voices: int = 8):
         """Continuous batching: a generator that takes SpeechRequest / MusicRequest objects from any iterable (read lazily) and yields
         (index, wav path) as each request ends -- index = the request's position in `requests`, the file is
         `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows (1..32) decode together,
@@ -390,22 +422,34 @@ class UniMoEAudio:
         rows keep decoding (DecodeEngine.admit, unimoe_audio_amd/serve.py).  Each request's prompt pair is built as generate_batch builds it
         and keeps its own length.  The engine is sized once: max_prompt_tokens per prompt, max_audio_seconds per request; a request beyond
         either is refused when its turn comes.  `w12_wide`: above 8 slots, bf16 expert weights stream as their lossless 12-bit copies in the wide
-        step (model.engine).  Not for expert-parallel engines, video prompts or streamed chunks."""
-        from .serve import MAX_SLOTS_WIDE, Scheduler
+        step (model.engine).  Not for expert-parallel engines, video prompts or streamed chunks.
+        `prefix_cache`: speech requests with equal (prompt_transcription, prompt_wav or id(prompt_codec)) share a VoicePrompt: the voice's
+        prompt prefix is prefilled once per engine, and every admission installs its K / V and prefills only the sentence behind it
+        (DESIGN 4n); at most `prefix_cache_voices` voices are kept, least recently used first out.  A request that carries its own
+        `voice` takes that path whatever the switch says.  self.served_prefix = {index: (hit, P)} tells per request whether the
+        prefix store was there already and how many tokens it covered ((False, 0): admitted in one piece)."""
+        from .serve import MAX_SLOTS_WIDE, Scheduler, VoiceLRU
         if not 1 <= slots <= MAX_SLOTS_WIDE:
             raise ValueError(f"serve: slots must be 1..{MAX_SLOTS_WIDE} (got {slots})")
         cfg = self.model.config
         eng = self.model.engine(slots, int(max_prompt_tokens), 50 * int(max_audio_seconds), expert_weights=expert_weights, w12_wide=w12_wide)
         eng.start_serving(int(max_prompt_tokens))
         app = self
+        voices = VoiceLRU(prefix_cache_voices) if prefix_cache else None
+        prefix_log = []                                    # (hit, P) per admission, in admission order
 
         class Rows:
             """the engine as unimoe_audio_amd.serve.Scheduler drives it"""
             held = {}
 
             def admit(self, row, r):
+                voice = None
                 if isinstance(r, SpeechRequest):
-                    enc, codec = app._speech_prompt(r.transcription, r.prompt_transcription, r.prompt_wav, None, None, r.prompt_codec)
+                    voice = r.voice
+                    if voice is None and voices is not None:
+                        key = (r.prompt_transcription, r.prompt_wav if r.prompt_wav is not None else id(r.prompt_codec))
+                        voice = voices.get(key, lambda: app.voice(r.prompt_transcription, r.prompt_wav, r.prompt_codec))
+                    enc, codec = app._speech_prompt(r.transcription, r.prompt_transcription, r.prompt_wav, None, None, r.prompt_codec, voice)
                 elif isinstance(r, MusicRequest):
                     enc, codec = app._music_prompt(r.caption), None
                 else:
@@ -414,12 +458,20 @@ class UniMoEAudio:
                     raise ValueError("serve: one text per request")
                 if r.max_audio_seconds > max_audio_seconds:
                     raise ValueError(f"serve: a request of {r.max_audio_seconds} s on an engine sized for {max_audio_seconds} s (max_audio_seconds)")
-                x = app.model.calculate_input_embedding(enc.input_ids.to(app.device), None if codec is None else codec.to(app.device))
                 prefill, steps = prepare_audio_prompt(cfg, [None])
-                eng.admit(row, x.reshape(-1, x.shape[-1]).contiguous(), enc.attention_mask, prefill[0], steps[0],
-                          max_tokens=50 * r.max_audio_seconds, min_tokens=50 * r.min_audio_seconds, cfg_scale=r.cfg_scale,
-                          temperature=r.temperature, top_p=r.top_p, top_k=r.cfg_filter_top_k, eos_mul=r.eos_prob_mul_factor,
-                          do_sample=r.do_sample, seed=r.seed)
+                settings = dict(max_tokens=50 * r.max_audio_seconds, min_tokens=50 * r.min_audio_seconds, cfg_scale=r.cfg_scale,
+                                temperature=r.temperature, top_p=r.top_p, top_k=r.cfg_filter_top_k, eos_mul=r.eos_prob_mul_factor,
+                                do_sample=r.do_sample, seed=r.seed)
+                P = app._split_point(enc, voice) if voice is not None else 0
+                if P >= 1:
+                    # a miss builds the store through this (free) row and then admits exactly as a hit does
+                    store, hit = voice.store_for(eng, P, lambda n: eng.build_prefix(row, voice.x[:n].contiguous()))
+                    eng.admit(row, app._suffix_embedding(enc, voice, P), enc.attention_mask, prefill[0], steps[0], prefix=store, prefix_len=P, **settings)
+                    prefix_log.append((hit, P))
+                else:
+                    x = app.model.calculate_input_embedding(enc.input_ids.to(app.device), None if codec is None else codec.to(app.device))
+                    eng.admit(row, x.reshape(-1, x.shape[-1]).contiguous(), enc.attention_mask, prefill[0], steps[0], **settings)
+                    prefix_log.append((False, 0))
                 self.held[row] = r
 
             def steps(self, n):
@@ -438,8 +490,10 @@ class UniMoEAudio:
 
         sched = Scheduler(Rows(), slots, poll_every, max_slots=MAX_SLOTS_WIDE)
         self.served_rows = {}                              # request index -> the row it decoded in (of the last / the running serve())
+        self.served_prefix = {}                            # request index -> (prefix store hit, prefix tokens P)
         for index, (r, codes, length) in sched.run(requests):
             self.served_rows.update({i: row for i, row, _ in sched.admitted})
+            self.served_prefix.update({i: hp for (i, _, _), hp in zip(sched.admitted, prefix_log)})
             audio = generate_output(cfg, codes[None], torch.tensor([length], device=codes.device))[0]
             if output_dir is None:
                 yield index, audio
@@ -448,6 +502,29 @@ class UniMoEAudio:
             path = os.path.join(output_dir, f"generated_{r.save_name}_{index}.wav")
             self.dac.decode(audio.transpose(0, 1).unsqueeze(0), save_path=path, min_duration=1)
             yield index, path
+
+    def _split_point(self, enc, voice: VoicePrompt) -> int:
+        """P of a request in `voice`: the longest common prefix of the pair's id rows and the voice's prefix ids, clamped to T - 2; 0 when
+        an audio placeholder would stay behind it (the columns behind the prefix are embedded as text)"""
+        T = int(enc.input_ids.shape[1])
+        rows = [enc.input_ids[r][enc.attention_mask[r].bool()].tolist() for r in range(2)]
+        P = split_point(rows[0], rows[1], voice.ids, T)
+        ph = self.model.codec_placeholder_value
+        if P < 1 or any(ph in row[P:] for row in rows):
+            return 0
+        return P
+
+    def _suffix_embedding(self, enc, voice: VoicePrompt, P: int) -> torch.Tensor:
+        """[2 * (T - P), D]: columns [P, T) of the pair's embeddings.  Behind its pads the shorter row repeats its last prefix tokens
+        there: those come from the voice's embeddings, everything else is text."""
+        T = int(enc.input_ids.shape[1])
+        x = self.model.language_model.embed_tokens.weight[enc.input_ids[:, P:].to(self.device)]
+        for r in range(2):
+            first = T - int(enc.attention_mask[r].sum())
+            t0, t1 = max(P, first), min(T, first + P)      # column t holds the row's token t - first: a prefix token below first + P
+            if t1 > t0:
+                x[r, t0 - P:t1 - P] = voice.x[t0 - first:t1 - first]
+        return x.reshape(-1, x.shape[-1]).contiguous()
 
     def video_text_to_music(self, video, caption: Union[str, List[str]], output_dir: str = "./", max_audio_seconds: int = 20,
                             min_audio_seconds: int = 8, temperature: float = 1.0, top_p: float = 1.0, cfg_filter_top_k: int = 45,

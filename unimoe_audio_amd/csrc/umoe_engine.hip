@@ -83,9 +83,17 @@ struct umoe_engine {
     int32_t* all_mask = nullptr;
     int64_t* all_topk = nullptr;
     int T_prompt = 0;
-    // admission into a running batch (umoe_engine_admit): the prefill body runs over the 2 cache rows from adm_row0 (-1: the whole batch)
+    // admission into a running batch (umoe_engine_admit): the prefill body runs over the adm_rows cache rows from adm_row0 (-1: the whole
+    // batch).  2 rows: a CFG pair; 1 row: a prefix run alone (umoe_engine_prefix_build)
     int adm_row0 = -1;
-    int32_t* adm_q0 = nullptr;   // [2] zeros: q_pos0 of an admission prefill (the batch's own q_pos0 belongs to the decode steps)
+    int adm_rows = 2;
+    int32_t* adm_q0 = nullptr;   // [4]: {0, 0} q_pos0 of an admission prefill (the batch's own q_pos0 belongs to the decode steps), then {P, P} of
+                                 // an admission behind an installed prefix (umoe_engine_admit_prefix writes them)
+    const int32_t* adm_q = nullptr;   // the pair of adm_q0 the running admission pass reads
+    // router dump of admission passes for the parity tests (umoe_engine_set_admit_dump): [layers][adm_dump_cap][E] expert masks / bf16 gate logits
+    int32_t* adm_dump_mask = nullptr;
+    uint16_t* adm_dump_logits = nullptr;
+    int adm_dump_cap = 0;
     int reserved_tok = 0;        // umoe_engine_reserve: the workspace does not move for prompts up to this many tokens
     // per-layer probe of the parity tests (umoe_engine_set_probe): eager steps only
     const uint16_t* probe_teach = nullptr;
@@ -1081,7 +1089,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     const LayerDev& L = e->layers[l];
     const umoe_group_t* g = e->d_groups + (size_t)l * GPL;
     const umoe_group_t* gh = e->h_groups.data() + (size_t)l * GPL;   // same table, host side
-    const bool adm = e->adm_row0 >= 0;       // admission prefill: cache rows [adm_row0, adm_row0 + 2) only
+    const bool adm = e->adm_row0 >= 0;       // admission prefill: cache rows [adm_row0, adm_row0 + adm_rows) only
     const size_t kv_l = ((size_t)l * c.rows + (adm ? e->adm_row0 : 0)) * c.kv_heads * c.Lmax * c.head_dim;
     int rc;
     // 1. RMSNorm + QKV (+bias)                                   model.py:227, Qwen2_5_VLAttention q/k/v_proj
@@ -1147,7 +1155,7 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     umoe_attn_args t{};
     t.q = e->q_r; t.k_cache = r.k_cache; t.v_cache = r.v_cache; t.kv_start = e->kv_start; t.q_pos0 = e->q_pos0;
     t.rows = c.rows; t.nq = T;
-    if (adm) { t.kv_start = e->kv_start + e->adm_row0; t.q_pos0 = e->adm_q0; t.rows = 2; } t.H = c.heads; t.KVH = c.kv_heads; t.hd = c.head_dim; t.Lmax = c.Lmax; t.splits = splits;
+    if (adm) { t.kv_start = e->kv_start + e->adm_row0; t.q_pos0 = e->adm_q ? e->adm_q : e->adm_q0; t.rows = e->adm_rows; } t.H = c.heads; t.KVH = c.kv_heads; t.hd = c.head_dim; t.Lmax = c.Lmax; t.splits = splits;
     t.scale = 1.0f / sqrtf((float)c.head_dim); t.part_o = e->part_o; t.part_ml = e->part_ml; t.out = e->attn_out;
     if (fuse_rope) {
         t.qkv_raw = e->qkv; t.cos_tab = e->cos_tab; t.sin_tab = e->sin_tab; t.pos3 = e->pos3;
@@ -1308,6 +1316,12 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             e->expert_fp8 = e->fp8 ? 1 : 0;
             e->row_tiles = ceil_div(n_tok, 16);
             break;
+    }
+    if (adm && n_tok <= e->adm_dump_cap && (form == MOE_TILED || form == MOE_RAGGED)) {      // (parity tests: what the router decided for every token of this pass)
+        if (e->adm_dump_mask)
+            UMOE_HIP(hipMemcpyAsync(e->adm_dump_mask + (size_t)l * e->adm_dump_cap * E, e->r_mask, (size_t)n_tok * E * 4, hipMemcpyDeviceToDevice, s));
+        if (e->adm_dump_logits)
+            UMOE_HIP(hipMemcpyAsync(e->adm_dump_logits + (size_t)l * e->adm_dump_cap * E, e->r_logits, (size_t)n_tok * E * 2, hipMemcpyDeviceToDevice, s));
     }
     // 9. combine + residual -> next layer input                   core.py:488,342-351; model.py:242
     umoe_combine_args cb{};
@@ -1559,8 +1573,8 @@ extern "C" int umoe_engine_reserve(umoe_engine* e, int n_tok) {
     int rc;
     if ((rc = ensure_workspace(e, n_tok > e->c.rows ? n_tok : e->c.rows))) return rc;
     if (!e->adm_q0) {
-        UMOE_HIP(hipMalloc(&e->adm_q0, 2 * sizeof(int32_t)));
-        UMOE_HIP(hipMemset(e->adm_q0, 0, 2 * sizeof(int32_t)));
+        UMOE_HIP(hipMalloc(&e->adm_q0, 4 * sizeof(int32_t)));
+        UMOE_HIP(hipMemset(e->adm_q0, 0, 4 * sizeof(int32_t)));
     }
     e->cb_pending = false;
     if ((rc = build_groups(e, e->c.rows, nullptr))) return rc;
@@ -1569,14 +1583,25 @@ extern "C" int umoe_engine_reserve(umoe_engine* e, int n_tok) {
 }
 
 // checks of an admission, all before anything is enqueued; fills start / vc (kv_start, valid_count) of the two rows
+// (split: an admission behind P installed prefix tokens, umoe_engine_admit_prefix -- columns [P, T) are the pass; else the whole prompt)
 static int admit_check(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step, int prefix_len,
-                       int32_t* start, int32_t* vc, const char* who) {
+                       int32_t* start, int32_t* vc, const char* who, bool split = false, int P = 0, const void* store = nullptr) {
     UMOE_REQUIRE(e && io && io->tokens && io->state && valid_host && T > 0, "%s: bad argument", who);
+    if (split) {
+        UMOE_REQUIRE(store, "%s: null prefix store", who);
+        UMOE_REQUIRE(P >= 1, "%s: a prefix of %d tokens (need 1 <= P)", who, P);
+        UMOE_REQUIRE(T - P >= 2, "%s: %d columns behind a prefix of %d tokens (need 2 <= T - P; clamp P to T - 2)", who, T - P, P);
+    }
     const umoe_engine_cfg& c = e->c;
     UMOE_REQUIRE(c.ep_size == 1, "%s: admission is not supported expert parallel (ep_size %d)", who, c.ep_size);
     UMOE_REQUIRE(io->row_clock, "%s: the batch has no per-row clocks (umoe_decode_io.row_clock)", who);
     UMOE_REQUIRE(e->reserved_tok > 0, "%s: umoe_engine_reserve first", who);
-    UMOE_REQUIRE(2 * T <= e->reserved_tok, "%s: a prompt of %d tokens per row is larger than the reservation (%d tokens for the pair)", who, T, e->reserved_tok);
+    if (split) {
+        UMOE_REQUIRE(P <= e->reserved_tok && 2 * (T - P) <= e->reserved_tok,
+                     "%s: a prefix of %d tokens or %d columns per row behind it is larger than the reservation (%d tokens)", who, P, T - P, e->reserved_tok);
+    } else {
+        UMOE_REQUIRE(2 * T <= e->reserved_tok, "%s: a prompt of %d tokens per row is larger than the reservation (%d tokens for the pair)", who, T, e->reserved_tok);
+    }
     UMOE_REQUIRE(b >= 0 && b < c.rows / 2, "%s: row %d outside the batch of %d", who, b, c.rows / 2);
     UMOE_REQUIRE(T < c.Lmax, "%s: prompt length %d does not fit Lmax %d", who, T, c.Lmax);
     UMOE_REQUIRE(prefill_step >= 1 && prefill_step <= prefix_len && prefix_len <= c.Tmax,
@@ -1594,6 +1619,8 @@ static int admit_check(umoe_engine* e, const umoe_decode_io* io, int b, const ui
         start[r] = first;
         vc[r] = cnt;
         UMOE_REQUIRE(cnt + c.Lmax - T < e->max_pos, "%s: rope table too short", who);
+        // (split: the install puts the row's first max(P - first, 0) prefix tokens into slots [first, P); that all of them are valid and lie
+        //  below column P is the left-padding rule just checked)
     }
     return 0;
 }
@@ -1611,13 +1638,15 @@ static int admit_state(umoe_engine* e, const umoe_decode_io* io, int b, int T, i
     return 0;
 }
 
+static int admission_pass(umoe_engine* e, int row0, int n_rows, int T, const uint16_t* x, const std::vector<int32_t>& pos, const std::vector<int32_t>& kvp,
+                          const int32_t* start, const int32_t* q0_host, hipStream_t s);
+
 extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* x, const uint8_t* valid_host, int T, int prefill_step,
                                  int prefix_len, umoe_stream_t stream) {
     int32_t start[2], vc[2];
     int rc;
     if ((rc = admit_check(e, io, b, valid_host, T, prefill_step, prefix_len, start, vc, "umoe_engine_admit"))) return rc;
     UMOE_REQUIRE(x, "umoe_engine_admit: null prompt");
-    const umoe_engine_cfg& c = e->c;
     hipStream_t s = (hipStream_t)stream;
     const int n_tok = 2 * T;
     if ((rc = fp8_only_check(e, n_tok))) return rc;       // (an admission prefill is never the dense layout)
@@ -1636,14 +1665,88 @@ extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b
             kvp[r * T + t] = t;
         }
     }
-    e->adm_row0 = 2 * b;
+    if ((rc = admission_pass(e, 2 * b, 2, T, x, pos, kvp, start, nullptr, s))) return rc;
+    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, s);
+}
+
+extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step,
+                                          int prefix_len, umoe_stream_t stream) {
+    int32_t start[2], vc[2];
+    if (int rc = admit_check(e, io, b, valid_host, T, prefill_step, prefix_len, start, vc, "umoe_engine_admit_external")) return rc;
+    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ prefix store
+// One launch copies token ranges between a prefix store [layers][2][KVH][P][hd] and the K / V slabs [layers][rows][KVH][Lmax][hd]: blockIdx.y
+// = (layer, K | V, kv head), blockIdx.z = job, a thread per 16-byte piece of a token.  Install and extract are the same index arithmetic
+// with source and destination swapped; the ranges were checked on the host.
+struct PrefixJobs {
+    int32_t row[8], i0[8], s0[8], n[8];
+};
+__global__ __launch_bounds__(256) void kv_prefix_copy_kernel(uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache, uint16_t* __restrict__ store,
+                                                             int rows, int KVH, int Lmax, int hd, int P, const PrefixJobs jobs, int extract) {
+    const int j = blockIdx.z, y = blockIdx.y;
+    const int kvh = y % KVH, kv = (y / KVH) & 1, layer = y / (2 * KVH);
+    const int pieces = hd >> 3;                                           // 16-byte pieces per token
+    const int total = jobs.n[j] * pieces;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int tok = idx / pieces, pc = idx - tok * pieces;
+    uint16_t* cache = kv ? v_cache : k_cache;
+    uint16_t* cp = cache + ((((size_t)layer * rows + jobs.row[j]) * KVH + kvh) * Lmax + jobs.s0[j] + tok) * hd + pc * 8;
+    uint16_t* sp = store + ((((size_t)layer * 2 + kv) * KVH + kvh) * P + jobs.i0[j] + tok) * hd + pc * 8;
+    if (extract) st16(sp, ld16(cp));
+    else st16(cp, ld16(sp));
+}
+
+extern "C" int umoe_kv_prefix_copy(uint16_t* k_cache, uint16_t* v_cache, uint16_t* store, int layers, int rows, int kv_heads, int Lmax, int head_dim,
+                                   int P, const int32_t* jobs_host, int n_jobs, int extract, umoe_stream_t stream) {
+    UMOE_REQUIRE(k_cache && v_cache && store && jobs_host, "umoe_kv_prefix_copy: null argument");
+    UMOE_REQUIRE(layers > 0 && rows > 0 && kv_heads > 0 && Lmax > 0 && P > 0 && head_dim > 0 && head_dim % 8 == 0,
+                 "umoe_kv_prefix_copy: bad shape (layers %d rows %d kv_heads %d Lmax %d head_dim %d P %d)", layers, rows, kv_heads, Lmax, head_dim, P);
+    UMOE_REQUIRE(n_jobs >= 1 && n_jobs <= 8, "umoe_kv_prefix_copy: 1..8 jobs per launch (got %d)", n_jobs);
+    UMOE_REQUIRE((size_t)layers * 2 * kv_heads <= 65535, "umoe_kv_prefix_copy: layers * 2 * kv_heads beyond the grid");
+    PrefixJobs jobs{};
+    int n_max = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int row = jobs_host[4 * j], i0 = jobs_host[4 * j + 1], s0 = jobs_host[4 * j + 2], n = jobs_host[4 * j + 3];
+        UMOE_REQUIRE(row >= 0 && row < rows && n >= 0 && i0 >= 0 && i0 <= P - n && s0 >= 0 && s0 <= Lmax - n,
+                     "umoe_kv_prefix_copy: job %d {row %d, i0 %d, s0 %d, n %d} outside the store of %d tokens or the %d slots of %d rows", j, row, i0, s0, n, P,
+                     Lmax, rows);
+        for (int k = 0; k < j; ++k) {      // two jobs must not write the same place (the order of their stores is not defined)
+            if (extract)
+                UMOE_REQUIRE(i0 + n <= jobs.i0[k] || jobs.i0[k] + jobs.n[k] <= i0, "umoe_kv_prefix_copy: extract jobs %d and %d overlap in the store", k, j);
+            else
+                UMOE_REQUIRE(jobs.row[k] != row || s0 + n <= jobs.s0[k] || jobs.s0[k] + jobs.n[k] <= s0, "umoe_kv_prefix_copy: jobs %d and %d overlap in row %d", k, j, row);
+        }
+        jobs.row[j] = row; jobs.i0[j] = i0; jobs.s0[j] = s0; jobs.n[j] = n;
+        n_max = n > n_max ? n : n_max;
+    }
+    if (n_max == 0) return 0;
+    const dim3 grid((unsigned)ceil_div(n_max * (head_dim / 8), 256), (unsigned)(layers * 2 * kv_heads), (unsigned)n_jobs);
+    kv_prefix_copy_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(k_cache, v_cache, store, rows, kv_heads, Lmax, head_dim, P, jobs, extract);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The prefill body over `n_rows` cache rows from row0, T tokens per row (n_tok = n_rows * T), with the positions / slots / q_pos0 the caller
+// laid out: what umoe_engine_admit runs for a pair, here for the prefix alone (1 row) and for the columns behind it (2 rows).  Leaves the group
+// table in decode shape; synchronises (the host vectors are the caller's).
+static int admission_pass(umoe_engine* e, int row0, int n_rows, int T, const uint16_t* x, const std::vector<int32_t>& pos, const std::vector<int32_t>& kvp,
+                          const int32_t* start, const int32_t* q0_host, hipStream_t s) {
+    const umoe_engine_cfg& c = e->c;
+    const int n_tok = n_rows * T;
+    e->adm_row0 = row0;
+    e->adm_rows = n_rows;
+    e->adm_q = q0_host ? e->adm_q0 + 2 : e->adm_q0;
     e->groups_for_tok = -1;              // (a table of the same token count in decode shape is not this pass's table)
-    rc = build_groups(e, n_tok, s);
+    int rc = build_groups(e, n_tok, s);
     if (!rc) {
         rc = [&]() -> int {
             UMOE_HIP(hipMemcpyAsync(e->pos3, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
             UMOE_HIP(hipMemcpyAsync(e->kv_pos, kvp.data(), kvp.size() * 4, hipMemcpyHostToDevice, s));
-            UMOE_HIP(hipMemcpyAsync(e->kv_start + 2 * b, start, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            UMOE_HIP(hipMemcpyAsync(e->kv_start + row0, start, n_rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            if (q0_host) UMOE_HIP(hipMemcpyAsync(e->adm_q0 + 2, q0_host, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
             UMOE_HIP(hipMemcpyAsync(e->x, x, (size_t)n_tok * c.hidden * 2, hipMemcpyDeviceToDevice, s));
             int r2;
             if ((r2 = umoe_rmsnorm_residual_fwd(e->x, nullptr, e->layers[0].w.in_norm, c.rms_eps, n_tok, c.hidden, nullptr, e->hin, s))) return r2;
@@ -1656,19 +1759,83 @@ extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b
         }();
     }
     e->adm_row0 = -1;
+    e->adm_rows = 2;
+    e->adm_q = nullptr;
     e->cb_pending = false;
     e->groups_for_tok = -1;
-    const int rg = build_groups(e, c.rows, s);      // back to decode shape (synchronises: pos / kvp stay alive until here)
-    if (rc) return rc;
-    if (rg) return rg;
-    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, s);
+    const int rg = build_groups(e, c.rows, s);      // back to decode shape (synchronises: the host vectors stay alive until here)
+    return rc ? rc : rg;
 }
 
-extern "C" int umoe_engine_admit_external(umoe_engine* e, const umoe_decode_io* io, int b, const uint8_t* valid_host, int T, int prefill_step,
-                                          int prefix_len, umoe_stream_t stream) {
+extern "C" int umoe_engine_prefix_build(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* x_prefix, int P, uint16_t* store,
+                                        umoe_stream_t stream) {
+    const char* who = "umoe_engine_prefix_build";
+    UMOE_REQUIRE(e && io && io->tokens && io->state && x_prefix, "%s: bad argument", who);
+    UMOE_REQUIRE(store, "%s: null prefix store", who);
+    const umoe_engine_cfg& c = e->c;
+    UMOE_REQUIRE(c.ep_size == 1, "%s: admission is not supported expert parallel (ep_size %d)", who, c.ep_size);
+    UMOE_REQUIRE(io->row_clock, "%s: the batch has no per-row clocks (umoe_decode_io.row_clock)", who);
+    UMOE_REQUIRE(e->reserved_tok > 0, "%s: umoe_engine_reserve first", who);
+    UMOE_REQUIRE(P >= 1, "%s: a prefix of %d tokens (need 1 <= P)", who, P);
+    UMOE_REQUIRE(P <= e->reserved_tok, "%s: a prefix of %d tokens is larger than the reservation (%d tokens)", who, P, e->reserved_tok);
+    UMOE_REQUIRE(P < c.Lmax && P <= e->max_pos, "%s: a prefix of %d tokens does not fit Lmax %d / the rope table (%d)", who, P, c.Lmax, e->max_pos);
+    UMOE_REQUIRE(b >= 0 && b < c.rows / 2, "%s: row %d outside the batch of %d", who, b, c.rows / 2);
+    UMOE_REQUIRE(!e->probe_on(), "%s: not with the per-layer probe", who);
+    UMOE_REQUIRE(c.head_dim % 8 == 0, "%s: head_dim %d is no multiple of 8", who, c.head_dim);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = fp8_only_check(e, P))) return rc;       // (an admission pass is never the dense layout)
+    if ((rc = w12_only_check(e, P))) return rc;
+    e->prefill_fp8 = 0;
+    e->prefill_w12 = 0;
+    std::vector<int32_t> pos((size_t)3 * P), kvp(P);
+    for (int t = 0; t < P; ++t) {
+        pos[t] = pos[(size_t)P + t] = pos[(size_t)2 * P + t] = t;
+        kvp[t] = t;
+    }
+    const int32_t start = 0;
+    if ((rc = admission_pass(e, 2 * b, 1, P, x_prefix, pos, kvp, &start, nullptr, s))) return rc;
+    const int32_t job[4] = {2 * b, 0, 0, P};
+    if ((rc = umoe_kv_prefix_copy(e->k_cache, e->v_cache, store, c.layers, c.rows, c.kv_heads, c.Lmax, c.head_dim, P, job, 1, 1, s))) return rc;
+    UMOE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int umoe_engine_admit_prefix(umoe_engine* e, const umoe_decode_io* io, int b, const uint16_t* store, int P, const uint16_t* x_suffix,
+                                        const uint8_t* valid_host, int T, int prefill_step, int prefix_len, umoe_stream_t stream) {
+    const char* who = "umoe_engine_admit_prefix";
     int32_t start[2], vc[2];
-    if (int rc = admit_check(e, io, b, valid_host, T, prefill_step, prefix_len, start, vc, "umoe_engine_admit_external")) return rc;
-    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, (hipStream_t)stream);
+    int rc;
+    if ((rc = admit_check(e, io, b, valid_host, T, prefill_step, prefix_len, start, vc, who, true, P, store))) return rc;
+    UMOE_REQUIRE(x_suffix, "%s: null prompt", who);
+    const umoe_engine_cfg& c = e->c;
+    UMOE_REQUIRE(c.head_dim % 8 == 0, "%s: head_dim %d is no multiple of 8", who, c.head_dim);
+    hipStream_t s = (hipStream_t)stream;
+    const int Tq = T - P, n_tok = 2 * Tq;
+    if ((rc = fp8_only_check(e, n_tok))) return rc;
+    if ((rc = w12_only_check(e, n_tok))) return rc;
+    e->prefill_fp8 = 0;
+    e->prefill_w12 = 0;
+    // positions of columns [P, T) from the FULL mask: cumsum(mask) - 1, masked -> 1; kv slot = the column
+    std::vector<int32_t> pos((size_t)3 * n_tok), kvp(n_tok);
+    int32_t jobs[8];
+    for (int r = 0; r < 2; ++r) {
+        int cnt = 0;
+        for (int t = 0; t < T; ++t) {
+            const int v = valid_host[(size_t)r * T + t] != 0;
+            cnt += v;
+            if (t < P) continue;
+            const int p = v ? cnt - 1 : 1, j = t - P;
+            for (int k = 0; k < 3; ++k) pos[(size_t)k * n_tok + r * Tq + j] = p;
+            kvp[r * Tq + j] = t;
+        }
+        jobs[4 * r] = 2 * b + r; jobs[4 * r + 1] = 0; jobs[4 * r + 2] = start[r]; jobs[4 * r + 3] = P > start[r] ? P - start[r] : 0;
+    }
+    if ((rc = umoe_kv_prefix_copy(e->k_cache, e->v_cache, const_cast<uint16_t*>(store), c.layers, c.rows, c.kv_heads, c.Lmax, c.head_dim, P, jobs, 2, 0, s)))
+        return rc;
+    const int32_t q0[2] = {P, P};
+    if ((rc = admission_pass(e, 2 * b, 2, Tq, x_suffix, pos, kvp, start, q0, s))) return rc;
+    return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, s);
 }
 
 // An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch (moe_form: MOE_FLAT) or, with the
@@ -1871,6 +2038,14 @@ extern "C" int umoe_engine_set_probe(umoe_engine* e, const uint16_t* teach_x, ui
     UMOE_REQUIRE(e, "umoe_engine_set_probe: null engine");
     UMOE_REQUIRE(e->c.ep_size == 1 || !(teach_x || dump_x1 || dump_x || dump_logits), "umoe_engine_set_probe: not with expert parallel engines");
     e->probe_teach = teach_x; e->probe_x1 = dump_x1; e->probe_x = dump_x; e->probe_logits = dump_logits;
+    return 0;
+}
+
+extern "C" int umoe_engine_set_admit_dump(umoe_engine* e, int32_t* mask_out, uint16_t* logits_out, int cap_tok) {
+    UMOE_REQUIRE(e && cap_tok >= 0, "umoe_engine_set_admit_dump: bad argument");
+    e->adm_dump_mask = cap_tok ? mask_out : nullptr;
+    e->adm_dump_logits = cap_tok ? logits_out : nullptr;
+    e->adm_dump_cap = cap_tok;
     return 0;
 }
 

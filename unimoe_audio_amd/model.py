@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
@@ -402,7 +403,7 @@ class UniAudioRVQQwen2_5VLMoEForConditionalGeneration(nn.Module):
             if e is not None:
                 e.close()
             self._engine = DecodeEngine(self, batch, Lmax=need_L, Tmax=max_tokens + 64, attn_splits=attn_splits, ep=ep, expert_weights=fmt,
-                                        fp8_wide=fp8_wide, w12_wide=w12_wide)
+                                        fp8_wide=fp8_wide, w12_wide=w12_wide).owned_by_model()
         return self._engine
 
     def quantize_experts_(self, fmt: str = "fp8", keep_bf16: bool = True):
@@ -577,7 +578,12 @@ class DecodeEngine:
         dev = model.device
         if dev.type != "cuda":
             raise L.UmoeError("DecodeEngine needs the model on a ROCm device; there is no CPU path in the product")
-        self.model, self.cfg, self.dev = model, cfg, dev
+        # the engine reads weights through raw pointers: it keeps every tensor it points to in self.keep (_pack_weights), so whatever
+        # it enqueues reads live memory whether or not the module is still there.  The module itself is only needed to build the engine
+        # and for a sharded prefill (text_forward).  An engine the model owns (model.engine() -> owned_by_model()) refers to it weakly:
+        # model and engine then form no cycle, and dropping the model frees both at once, not at some later cyclic collection
+        self._model, self._model_ref = model, weakref.ref(model)
+        self.cfg, self.dev = cfg, dev
         self.batch, self.rows, self.Lmax, self.Tmax = batch, 2 * batch, int(Lmax), int(Tmax)
         sec = list(cfg.mrope_section)
         c = L.EngineCfg(hidden=cfg.hidden_size, layers=cfg.num_hidden_layers, heads=cfg.num_attention_heads,
@@ -616,6 +622,18 @@ class DecodeEngine:
         self.row_clock = None
         self.reserved_prompt = 0
         self.captured = False
+
+    @property
+    def model(self):
+        m = self._model if self._model is not None else self._model_ref()
+        if m is None:
+            raise L.UmoeError("decode engine: the model that owns this engine is gone (this call runs the module's own forward)")
+        return m
+
+    def owned_by_model(self):
+        """model.engine() keeps the engine in model._engine: the engine then refers to its model weakly (see __init__)"""
+        self._model = None
+        return self
 
     def _k(self, t):
         self.keep.append(t)
@@ -658,6 +676,8 @@ class DecodeEngine:
             rm = [p for mods in (ex, sh) for m_ in mods for p in (m_.gate_proj.weight, m_.up_proj.weight, m_.down_proj.weight)]
             if not all(p.is_contiguous() for p in rm + [layer.self_attn.o_proj.weight]):
                 raise L.UmoeError("engine weights must be contiguous")
+            # the module's own parameters the engine points to (tensors hold no reference to their module)
+            self._k(rm + [layer.self_attn.o_proj.weight, layer.input_layernorm.weight, layer.post_attention_layernorm.weight, layer.mlp.gate.weight])
             if sharded or only:
                 reg = reu = red = None
             else:
@@ -682,6 +702,7 @@ class DecodeEngine:
         cos, sin = ops.rope_tables(max_pos, cfg.head_dim, cfg.rope_theta, self.dev)
         self._k(cos), self._k(sin)
         delay = (C.c_int32 * cfg.codec_channels)(*cfg.codec_delay_pattern)
+        self._k(m.language_model.norm.weight)
         L.check(lib.umoe_engine_set_globals(self.h, m.language_model.norm.weight.data_ptr(), emb.data_ptr(), head.data_ptr(),
                                             cos.data_ptr(), sin.data_ptr(), max_pos, delay), "umoe_engine_set_globals")
         torch.cuda.synchronize()
@@ -987,16 +1008,48 @@ class DecodeEngine:
         self.captured = False
         self.steps_run = 0
 
+    def prefix_store_shape(self, P: int):
+        """[layers][2 (K, V)][kv_heads][P][head_dim]: the roped keys and the values of P prefix tokens (umoe.h "Prefix reuse")"""
+        cfg = self.cfg
+        return (cfg.num_hidden_layers, 2, cfg.num_key_value_heads, int(P), cfg.head_dim)
+
+    def build_prefix(self, b: int, x_prefix: torch.Tensor) -> torch.Tensor:
+        """The prefix store of x_prefix [P, D] (the embeddings of the first P tokens of a prompt, e.g. a voice prompt): the prefix runs
+        ALONE as one row at positions 0 .. P - 1 through cache row 2b of the FREE batch entry b, and its K / V are extracted.  The
+        store depends on the prefix and the weights only; admit(..., prefix=store, prefix_len=P) installs it into any row later."""
+        self._refuse_clock("build_prefix")
+        if self.row_clock is None or not self.reserved_prompt:
+            raise L.UmoeError("build_prefix: start_serving first")
+        D = self.cfg.hidden_size
+        if not 0 <= b < self.batch:
+            raise L.UmoeError(f"build_prefix: row {b} outside the batch of {self.batch}")
+        if x_prefix.dim() != 2 or x_prefix.shape[1] != D or x_prefix.dtype != torch.bfloat16 or x_prefix.device != self.dev:
+            raise L.UmoeError(f"build_prefix: x_prefix is [P, {D}] bfloat16 prefix embeddings on the engine's device")
+        P = int(x_prefix.shape[0])
+        if P < 1 or P > self.reserved_prompt:
+            raise L.UmoeError(f"build_prefix: a prefix of {P} tokens (need 1 <= P; larger than the reservation of start_serving beyond {self.reserved_prompt})")
+        store = torch.empty(self.prefix_store_shape(P), dtype=torch.bfloat16, device=self.dev)
+        L.check(L.lib().umoe_engine_prefix_build(self.h, C.byref(self.io), b, x_prefix.contiguous().data_ptr(), P, store.data_ptr(), self._stream()),
+                "umoe_engine_prefix_build")
+        return store
+
     def admit(self, b: int, x: Optional[torch.Tensor], attention_mask: torch.Tensor, prefill_tokens: torch.Tensor, prefill_step: int, *,
               max_tokens: int, min_tokens, cfg_scale, temperature, top_p, top_k, eos_mul, do_sample, seed=0, position_ids=None,
-              external: bool = False):
+              external: bool = False, prefix: Optional[torch.Tensor] = None, prefix_len: int = 0):
         """One request into row b of a batch that is decoding: x [2 * T, D] the CFG pair's prompt embeddings (negative, positive),
         attention_mask [2, T] left padded, prefill_tokens [P, C] the row's token prefix as prepare_audio_prompt lays it out (P >=
         prefill_step; -1 = to be generated), the request's own settings.
         The pair is prefilled into cache rows 2b, 2b + 1 and the row is reset on the device at the step the stream has reached; no
         other row changes, and a captured step stays valid.  external=True: the caller has written the pair's K / V slabs
-        (write_buffer); only the state is set.  Every refusal is raised before anything is enqueued."""
+        (write_buffer); only the state is set.  Every refusal is raised before anything is enqueued.
+        prefix (build_prefix) with prefix_len = P: both rows begin with the store's P tokens.  x is then [2 * (T - P), D], columns
+        [P, T) of the pair's embeddings; the store is installed behind each row's pads and only those columns are prefilled
+        (prefix_plan.prefix_plan is the layout).  attention_mask stays the FULL pair's."""
         self._refuse_clock("admit")
+        split = prefix is not None or bool(prefix_len)
+        Pn = int(prefix_len)
+        if split and (external or position_ids is not None):
+            raise L.UmoeError("admit: a prefix store goes with neither external slabs nor 3-D positions")
         if self.row_clock is None or not self.reserved_prompt:
             raise L.UmoeError("admit: start_serving first")
         if position_ids is not None:
@@ -1009,22 +1062,38 @@ class DecodeEngine:
         T = int(attention_mask.shape[1])
         if T > self.reserved_prompt:
             raise L.UmoeError(f"admit: a prompt of {T} tokens is larger than the reservation of start_serving ({self.reserved_prompt})")
+        valid = attention_mask.to(torch.uint8).cpu().contiguous()
+        if split:      # every check of the split on the host first (prefix_plan restates the engine's)
+            from .prefix_plan import prefix_plan
+            if prefix is None:
+                raise L.UmoeError("admit: prefix_len without a prefix store (build_prefix)")
+            prefix_plan(valid, Pn)                       # raises for P < 1, T - P < 2, a row that is not left padded
+            if (tuple(prefix.shape) != self.prefix_store_shape(Pn) or prefix.dtype != torch.bfloat16 or prefix.device != self.dev
+                    or not prefix.is_contiguous()):
+                raise L.UmoeError(f"admit: the prefix store of {Pn} tokens is a contiguous bfloat16 {self.prefix_store_shape(Pn)} on the engine's device "
+                                  f"(got {tuple(prefix.shape)})")
         prefill_step, max_tokens = int(prefill_step), int(max_tokens)
         if prefill_step < 1 or prefill_tokens.dim() != 2 or prefill_tokens.shape[0] < prefill_step or prefill_tokens.shape[1] != Cc:
             raise L.UmoeError("admit: prefill_tokens is [P, C] with P >= prefill_step >= 1")
         if max_tokens + 2 > self.Tmax or prefill_tokens.shape[0] > self.Tmax or T + max_tokens + 1 > self.Lmax:
             raise L.UmoeError("admit: engine buffers too small for max_tokens")
-        if not external and (x is None or tuple(x.shape) != (2 * T, D) or x.dtype != torch.bfloat16 or x.device != self.dev):
+        n_x = 2 * (T - Pn) if split else 2 * T           # rows of x: the columns this admission prefills
+        if not external and (x is None or tuple(x.shape) != (n_x, D) or x.dtype != torch.bfloat16 or x.device != self.dev):
+            if split:
+                raise L.UmoeError(f"admit: behind a prefix of {Pn} tokens x is the [2 * {T - Pn}, {D}] bfloat16 embeddings of columns [{Pn}, {T}) on the "
+                                  "engine's device")
             raise L.UmoeError(f"admit: x is the pair's [2 * T, {D}] bfloat16 prompt embeddings on the engine's device")
         rec = RP.pack_row_params(1, cfg_scale=[cfg_scale], temperature=temperature, top_p=top_p, top_k=top_k, eos_mul=eos_mul, do_sample=do_sample,
                                  seed=seed, min_tokens=min_tokens, max_tokens=max_tokens)
-        valid = attention_mask.to(torch.uint8).cpu().contiguous()
         self.row_params[b].copy_(ops.row_params_tensor(rec, self.dev)[0])
         P = int(prefill_tokens.shape[0])
         self.tokens[b, :P] = prefill_tokens.to(self.dev, torch.int32)
         if external:
             L.check(L.lib().umoe_engine_admit_external(self.h, C.byref(self.io), b, valid.data_ptr(), T, prefill_step, P, self._stream()),
                     "umoe_engine_admit_external")
+        elif split:
+            L.check(L.lib().umoe_engine_admit_prefix(self.h, C.byref(self.io), b, prefix.data_ptr(), Pn, x.contiguous().data_ptr(), valid.data_ptr(), T,
+                                                     prefill_step, P, self._stream()), "umoe_engine_admit_prefix")
         else:
             L.check(L.lib().umoe_engine_admit(self.h, C.byref(self.io), b, x.contiguous().data_ptr(), valid.data_ptr(), T, prefill_step, P,
                                               self._stream()), "umoe_engine_admit")
@@ -1114,6 +1183,19 @@ class DecodeEngine:
         L.check(L.lib().umoe_engine_set_probe(self.h, ptr("teach"), ptr("x1"), ptr("x"), ptr("logits")), "umoe_engine_set_probe")
         self._probe = out            # (keeps the tensors alive while the engine holds their addresses)
         self.captured = False
+        return out
+
+    def set_admit_dump(self, cap_tok: int = 0):
+        """Router dump of admission passes for the parity tests (umoe_engine_set_admit_dump): the returned dict holds "mask" [layers,
+        cap_tok, E] int32 and "logits" [layers, cap_tok, E] bf16, which every following admit / build_prefix pass of at most cap_tok
+        tokens fills for its own tokens.  set_admit_dump() switches it off."""
+        cfg, out = self.cfg, {}
+        if cap_tok > 0:
+            out["mask"] = torch.zeros(cfg.num_hidden_layers, cap_tok, cfg.num_experts, dtype=torch.int32, device=self.dev)
+            out["logits"] = torch.zeros(cfg.num_hidden_layers, cap_tok, cfg.num_experts, dtype=torch.bfloat16, device=self.dev)
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None      # noqa: E731
+        L.check(L.lib().umoe_engine_set_admit_dump(self.h, ptr("mask"), ptr("logits"), int(cap_tok)), "umoe_engine_set_admit_dump")
+        self._admit_dump = out       # (keeps the tensors alive while the engine holds their addresses)
         return out
 
     def close(self):

@@ -16,8 +16,9 @@ DecodeEngine (through the adapter of UniMoEAudio.serve) is one; tests/test_serve
 """
 from __future__ import annotations
 
-from collections import deque
-from typing import Any, Deque, Dict, Iterable, Iterator, List, Tuple
+import weakref
+from collections import OrderedDict, deque
+from typing import Any, Callable, Deque, Dict, Iterable, Iterator, List, Tuple
 
 MAX_SLOTS = 8          # the default ceiling: the rows of the 16-row decode step
 MAX_SLOTS_WIDE = 32    # the most a caller may raise it to: the rows of the wide decode step
@@ -69,6 +70,53 @@ class Scheduler:
                     self.free.append(row)
                     self.free.sort()
                     yield index, result
+
+
+class VoicePrompt:
+    """What every request in one voice shares (UniMoEAudio.voice): the reference audio's codes as the codec gave them
+    (`codec`) and as the prompt takes them (`pc`, preprocess_codec), the token ids of the prompt up to and including <|SPEECH_START|>
+    (`ids`), their embeddings (`x` [len(ids), D]) and, per engine object and prefix length, the prefix store an admission installs.
+    Plain host bookkeeping: the tensors are whatever the caller put in."""
+
+    def __init__(self, prompt_transcription: str, codec=None, pc=None, ids=(), x=None):
+        self.prompt_transcription = prompt_transcription
+        self.codec, self.pc, self.ids, self.x = codec, pc, [int(i) for i in ids], x
+        self.stores: Dict[Tuple[int, int], Any] = {}        # (id(engine), P) -> (weak reference to the engine, store)
+
+    def store_for(self, engine, P: int, build: Callable[[int], Any]) -> Tuple[Any, bool]:
+        """(the store of the first P prefix tokens on `engine`, whether it was there already); build(P) makes it on a miss"""
+        key = (id(engine), int(P))
+        held = self.stores.get(key)
+        hit = held is not None and held[0]() is engine       # (an id may come back with another engine object)
+        if not hit:
+            self.stores = {k: v for k, v in self.stores.items() if v[0]() is not None}      # stores of engines that are gone
+            self.stores[key] = (weakref.ref(engine), build(int(P)))
+        return self.stores[key][1], hit
+
+    def drop(self):
+        self.stores.clear()
+
+
+class VoiceLRU:
+    """The voices serve(prefix_cache=True) keeps: at most `cap`, the least recently used dropped first (with its stores)."""
+
+    def __init__(self, cap: int = 8):
+        if cap < 1:
+            raise ValueError(f"prefix_cache_voices must be >= 1 (got {cap})")
+        self.cap = int(cap)
+        self.voices: "OrderedDict[Any, VoicePrompt]" = OrderedDict()
+        self.evicted = 0
+
+    def get(self, key, make: Callable[[], VoicePrompt]) -> VoicePrompt:
+        if key in self.voices:
+            self.voices.move_to_end(key)
+            return self.voices[key]
+        v = self.voices[key] = make()
+        while len(self.voices) > self.cap:
+            _, old = self.voices.popitem(last=False)
+            old.drop()
+            self.evicted += 1
+        return v
 
 
 def makespan_steps(lengths: Iterable[int], slots: int, poll_every: int, max_slots: int = MAX_SLOTS) -> int:
