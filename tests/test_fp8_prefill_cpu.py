@@ -21,7 +21,7 @@ KS = [32, 96, 352, 1376, 2048]
 # ------------------------------------------------------------------------------------------------ granule addressing
 def granule_offset(n, k, K, swiglu_half=None, j0_bug=False, swap_gate_up=False, quarter_bug=False):
     """Byte offset in the WP8 blocks of the 8-element granule at column k of weight row n, and the index of the row's exponent -- what
-    tgemm_wp8_kernel computes (umoe_tgemm_wp8.hip).  swiglu_half 0 / 1: gate / up row n of an interleaved pair."""
+    tgemm_wp8_kernel computes (umoe_tgemm_packed.hip).  swiglu_half 0 / 1: gate / up row n of an interleaved pair."""
     assert K % 32 == 0 and k % 8 == 0 and k < K
     Q, KB2 = K // 4, (K + 63) // 64
     h = k // Q
@@ -193,9 +193,9 @@ def test_wp8_tile_kernels_compile_for_gfx950_without_scratch(tmp_path):
     csrc = os.path.join(ROOT, "unimoe_audio_amd", "csrc")
     hipcc = "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "hipcc not found"
-    out = str(tmp_path / "umoe_tgemm_wp8.s")
+    out = str(tmp_path / "umoe_tgemm_packed.s")
     subprocess.check_call([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "--offload-arch=gfx950",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S", os.path.join(csrc, "umoe_tgemm_wp8.hip"),
+                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S", os.path.join(csrc, "umoe_tgemm_packed.hip"),
                            "-o", out], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     txt = open(out).read()
     recs = re.findall(r"\.name:\s+(\S*tgemm_wp8_kernel\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)"

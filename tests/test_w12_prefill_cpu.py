@@ -22,7 +22,7 @@ SHAPES = [(32, 64), (48, 1376), (64, 2048)]      # KB 2 (2-step chunks), 43 (1-s
 
 # ------------------------------------------------------------------------------------------------ granule addressing
 def granule(n, k, K, swiglu_half=None, swap_steps=False, force_cs=None, quarter_bug=False):
-    """What tgemm_w12_kernel computes (umoe_tgemm_w12.hip) for the 8-element granule at column k of weight row n: (byte offset of its 8
+    """What tgemm_w12_kernel computes (umoe_tgemm_packed.hip) for the 8-element granule at column k of weight row n: (byte offset of its 8
     low bytes, byte offset of its code word, word index of its block's window base).  swiglu_half 0 / 1: gate / up row n of an
     interleaved pair.  The nibble of element j of the granule: byte (0, 1, 0, 1, 2, 3, 2, 3)[j] of the code word, high half for j in
     (2, 3, 6, 7) (nibble())."""
@@ -308,17 +308,21 @@ def test_w12_tile_kernels_compile_for_gfx950_without_scratch_or_predicated_mfma(
     csrc = os.path.join(ROOT, "unimoe_audio_amd", "csrc")
     hipcc = "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "hipcc not found"
-    out = str(tmp_path / "umoe_tgemm_w12.s")
+    out = str(tmp_path / "umoe_tgemm_packed.s")
     r = subprocess.run([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "--offload-arch=gfx950",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S", os.path.join(csrc, "umoe_tgemm_w12.hip"),
+                        "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S", os.path.join(csrc, "umoe_tgemm_packed.hip"),
                         "-Rpass-analysis=kernel-resource-usage", "-o", out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
     assert r.returncode == 0, r.stdout[-2000:]
-    # the compiler's own resource remarks: four kernels, no scratch, no spill, two workgroups of 4 waves per CU
-    names = re.findall(r"Function Name: (\S*tgemm_w12_kernel\S*)", r.stdout)
-    assert len(set(names)) == 4, names                       # SwiGLU and BF16 epilogues x 128- and 256-token tiles
-    assert [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stdout)] == [0] * 4
-    assert [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", r.stdout)] == [0] * 4 and [int(x) for x in re.findall(r"SGPRs Spill: (\d+)", r.stdout)] == [0] * 4
-    assert all(int(x) >= 2 for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", r.stdout))
+    # the compiler's own resource remarks, one block per kernel of the file (the WP8 kernels live beside the WP12 ones): four kernels of
+    # each family, no scratch, no spill, two workgroups of 4 waves per CU
+    blocks = {b.split()[0]: b for b in r.stdout.split("Function Name: ")[1:]}
+    assert sum(bool(re.search(r"\dtgemm_w12_kernelI", n)) for n in blocks) == 4, sorted(blocks)     # SwiGLU and BF16 epilogues x 128- and 256-token tiles
+    assert sum(bool(re.search(r"\dtgemm_wp8_kernelI", n)) for n in blocks) == 4 and len(blocks) == 8, sorted(blocks)
+    for n, b in blocks.items():
+        assert [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", b)] == [0], (n, b)
+        assert [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", b)] == [0] and [int(x) for x in re.findall(r"SGPRs Spill: (\d+)", b)] == [0], (n, b)
+        occ = re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", b)
+        assert len(occ) == 1 and int(occ[0]) >= 2, (n, b)
     txt = open(out).read()
     recs = re.findall(r"\.name:\s+(\S*tgemm_w12_kernel\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)"
                       r"(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", txt)
@@ -329,4 +333,7 @@ def test_w12_tile_kernels_compile_for_gfx950_without_scratch_or_predicated_mfma(
     # the rebuild is byte permutes, the tile goes into LDS as 16-byte writes, an exception as a 2-byte one
     assert "v_perm_b32" in txt and ("ds_write_b128" in txt or "ds_store_b128" in txt) and ("ds_write_b16" in txt or "ds_store_b16" in txt)
     scan = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "scan_mfma_exec.py"), out], stdout=subprocess.PIPE, text=True, timeout=120)
-    assert scan.returncode == 0 and " 0 under s_and_saveexec" in scan.stdout and "128 MFMA" in scan.stdout, scan.stdout
+    # (32 MFMAs per kernel: 128 in the four WP12 kernels, as many in the four WP8 kernels of the file)
+    assert scan.returncode == 0 and " 0 under s_and_saveexec" in scan.stdout and "256 MFMA" in scan.stdout, scan.stdout
+    for name in kern:
+        assert txt.split("\n" + name + ":")[1].split(".Lfunc_end")[0].count("v_mfma") == 32, name

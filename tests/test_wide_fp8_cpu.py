@@ -46,8 +46,10 @@ def test_wide_kernels_do_not_spill_and_guard_every_mfma_with_a_scalar_branch(tmp
     # the kernel records of the code object's metadata: name and scratch bytes of every kernel
     recs = re.findall(r"\.name:\s+(\S*wstream_wide\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", open(out).read())
     wide = {name: int(scratch) for name, scratch in recs}
-    assert len(wide) > 28, len(wide)                 # the 28 bf16 instantiations and the fp8 form's
-    assert sum("wstream_wide_f8" in n for n in wide) >= 4 and sum("wstream_wide_f8" not in n for n in wide) == 28
+    # the instantiations of each family, by the whole kernel name (wstream_wide is a prefix of the other two): the mangled name carries the
+    # name's length in front and the template arguments' "I" behind
+    family = {f: sum(bool(re.search(r"\d" + f + "I", n)) for n in wide) for f in ("wstream_wide", "wstream_wide_f8", "wstream_wide_w12")}
+    assert family == {"wstream_wide": 28, "wstream_wide_f8": 8, "wstream_wide_w12": 8} and len(wide) == 44, (family, len(wide))
     assert all(v == 0 for v in wide.values()), {n: v for n, v in wide.items() if v}
     n, bad = scan(out)
     assert n > 0 and not bad, bad[:3]

@@ -44,9 +44,9 @@ def test_w12_wide_kernels_have_no_scratch_no_spill_and_guard_every_mfma_with_a_s
     csrc = os.path.join(ROOT, "unimoe_audio_amd", "csrc")
     hipcc = "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "hipcc not found"
-    out = str(tmp_path / "umoe_gemm_wide_w12.s")
+    out = str(tmp_path / "umoe_gemm_wide.s")
     subprocess.check_call([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "--offload-arch=gfx950",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S", os.path.join(csrc, "umoe_gemm_wide_w12.hip"),
+                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S", os.path.join(csrc, "umoe_gemm_wide.hip"),
                            "-o", out], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     # the kernel records of the code object's metadata: name, scratch bytes, VGPRs and spilled VGPRs of every kernel
     recs = re.findall(r"\.name:\s+(\S*wstream_wide_w12\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"

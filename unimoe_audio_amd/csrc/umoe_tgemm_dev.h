@@ -1,4 +1,4 @@
-// Device pieces shared by the tiled MFMA GEMM kernels (umoe_tgemm.hip: bf16 weights; umoe_tgemm_wp8.hip: WP8 weights): the group pack
+// Device pieces shared by the tiled MFMA GEMM kernels (umoe_tgemm.hip: bf16 weights; umoe_tgemm_packed.hip: WP8 and WP12 weights): the group pack
 // that travels in the kernel arguments, the swizzled LDS image and the epilogue.  One definition, so the kernels that promise
 // bit-identical results share the code that decides the bits behind the staging.
 #pragma once
