@@ -844,13 +844,41 @@ int umoe_engine_set_fp8_wide(umoe_engine* e, int on);
  * prefill or admission ran experts on WP12), "expert_bf16_resident" (0 only when no layer holds bf16 expert weights). */
 int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_t* const* gu12, const uint32_t* const* gu_m, const uint8_t* const* dn12,
                               const uint32_t* const* dn_m);
-/* on != 0: the wide form of a decode step of 17..64 rows (wide_mode and its size table are untouched: the switch changes which kernel a
+/* on != 0: the wide form of a decode step of 17..64 rows (whether a step is wide, and the size table behind that, are untouched: the switch changes which kernel a
  * wide step runs, not whether the step is wide) runs the gate/up and down launches of every layer that has WP12 copies
  * (umoe_engine_set_layer_w12 stores them at any row count) through umoe_gemm_wide_w12: the same outputs bit for bit, 0.75 of the expert
  * bytes.  A layer without copies (not packable) and an fp8 engine keep their launches.  UMOE_WIDE_W12=0, read per enqueue, forces the WP16
  * launches on such an engine.  umoe_engine_info(e, "expert_w12") = 1 when the last layer's wide expert launches ran on WP12;
  * "expert_launch" stays 4 and "row_tiles" the tile count.  Default off. */
 int umoe_engine_set_w12_wide(umoe_engine* e, int on);
+/* What the engine decides per layer of a pass -- the launch form of the MoE half, the weight format its expert launches stream, how the
+ * attention GEMMs run -- is one pure function of this POD (csrc/umoe_engine_plan.h).  The engine fills it once per pass, before anything
+ * is enqueued, and refuses the pass when a layer does not hold the format it would stream. */
+enum { UMOE_PASS_PREFILL = 0, UMOE_PASS_ADMISSION = 1, UMOE_PASS_DECODE = 2 };       /* umoe_plan_in.kind */
+enum { UMOE_FMT_WP16 = 0, UMOE_FMT_WP8 = 1, UMOE_FMT_WP12 = 2, UMOE_FMT_RM = 3 };    /* umoe_plan_out.format; RM: row-major bf16 (the bf16 tiled form) */
+enum { UMOE_ATTN_STREAM = 0, UMOE_ATTN_TILED = 1, UMOE_ATTN_WIDE = 2 };              /* umoe_plan_out.attn */
+/* what a layer holds (umoe_plan_in.holds[layer]): the WP16 expert packs, the row-major expert / attention tensors, WP8 blocks, WP12 copies */
+enum { UMOE_HOLD_SET = 1, UMOE_HOLD_BF16 = 2, UMOE_HOLD_RM_EXP = 4, UMOE_HOLD_RM_ATTN = 8, UMOE_HOLD_WP8 = 16, UMOE_HOLD_WP12 = 32 };
+typedef struct umoe_plan_in {
+    int32_t rows, hidden, inter_dyn, inter_shared, n_dyn, n_real, n_fix, ep_size;    /* of umoe_engine_cfg */
+    int32_t n_cu;                                           /* compute units (UMOE_FAKE_CUS overrides) */
+    int32_t tiled_prefill, fuse_router, dense_min_rows;     /* UMOE_TILED_PREFILL, UMOE_FUSE_ROUTER, UMOE_DENSE_MIN_ROWS: read when the engine is created */
+    int32_t fp8_wide, w12_wide;                             /* umoe_engine_set_fp8_wide, umoe_engine_set_w12_wide */
+    int32_t flat_moe, flat_w12, wide_w12, wide_decode;      /* UMOE_FLAT_MOE, UMOE_FLAT_W12, UMOE_WIDE_W12, UMOE_WIDE_DECODE, read once per pass: -1 unset, 0, 1 */
+    int32_t kind, n_tok;                                    /* the pass: UMOE_PASS_*, and its token count (a decode step: rows) */
+    int32_t n_layers;
+    const uint8_t* holds;                                   /* [n_layers] masks of UMOE_HOLD_* */
+} umoe_plan_in;
+typedef struct umoe_plan_out {
+    int32_t form;        /* 0 tiled, 1 ragged, 2 flat, 3 launch per kernel with router riders, 4 launch per kernel with the router launch, 5 wide,
+                          * 6 the expert-parallel decode half (outside the decision) */
+    int32_t format;      /* UMOE_FMT_* of the expert launches */
+    int32_t attn;        /* UMOE_ATTN_* */
+} umoe_plan_out;
+/* test hook (no GPU needed): the decision for every layer of a caller-filled pass.  in_bytes = sizeof(umoe_plan_in) as the caller sees it;
+ * rc [n_layers]: 0, or -1 = the pass is refused for this layer with the reason in msg + layer * msg_len (out still names what the pass
+ * would have run).  Returns 0, or -1 for a bad argument. */
+int umoe_engine_plan_probe(const umoe_plan_in* in, int in_bytes, umoe_plan_out* out, int32_t* rc, char* msg, int msg_len);
 /* test hook: the fp8 launch's conversion path over a row-major e4m3 matrix q [N][K] (K % 8 == 0) with one exponent per row:
  * out[r][k] = bf16 bits of q[r][k] * 2^e[r] */
 int umoe_fp8_convert_probe(const uint8_t* q, const int8_t* e, int N, int K, uint16_t* out, umoe_stream_t stream);

@@ -140,7 +140,19 @@ class DecodeIO(C.Structure):
                 ("eos_mul", f32), ("top_k", i32), ("do_sample", i32), ("min_tokens", i32), ("seed", u64), ("row_clock", vp), ("row_params", vp)]
 
 
+class PlanIn(C.Structure):
+    """umoe_plan_in: what the engine's per-layer decision (form, weight format, refusal) may depend on; umoe_engine_plan_probe checks the size"""
+    _fields_ = [(n, i32) for n in ("rows", "hidden", "inter_dyn", "inter_shared", "n_dyn", "n_real", "n_fix", "ep_size", "n_cu", "tiled_prefill",
+                                   "fuse_router", "dense_min_rows", "fp8_wide", "w12_wide", "flat_moe", "flat_w12", "wide_w12", "wide_decode",
+                                   "kind", "n_tok", "n_layers")] + [("holds", C.POINTER(C.c_uint8))]
+
+
+class PlanOut(C.Structure):
+    _fields_ = [("form", i32), ("format", i32), ("attn", i32)]
+
+
 EXPORTS = [
+    "umoe_engine_plan_probe",
     "umoe_last_error", "umoe_abi_version", "umoe_packed_elems", "umoe_pack_weight", "umoe_pack_gate_up",
     "umoe_router_fwd", "umoe_router_dispatch_fwd", "umoe_dispatch_build", "umoe_transpose_slots_compact", "umoe_aux_loss_fwd", "umoe_aux_loss_fwd_ws", "umoe_aux_loss_workspace_floats", "umoe_permute_fwd", "umoe_grouped_gemm", "umoe_grouped_swiglu_fwd", "umoe_shared_swiglu_fwd", "umoe_attn_prefill_fwd",
     "umoe_unpermute_combine_fwd", "umoe_rmsnorm_residual_fwd", "umoe_qkv_mrope_kvappend", "umoe_attn_decode",
@@ -302,6 +314,9 @@ def lib():
         L.umoe_gemm_wide_w12.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp), C.POINTER(vp), i32, i32,
                                          i32, i32, i32, vp]
         L.umoe_engine_set_w12_wide.argtypes = [vp, i32]
+        if not hasattr(L, "umoe_engine_plan_probe"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_engine_plan_probe): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_engine_plan_probe.argtypes = [C.POINTER(PlanIn), i32, C.POINTER(PlanOut), C.POINTER(i32), C.c_char_p, i32]
         if not hasattr(L, "umoe_tiled_gemm_w12"):
             raise UmoeError(f"{_SO} predates this package (no umoe_tiled_gemm_w12): rebuild it (`make -C unimoe_audio_amd/csrc`)")
         L.umoe_tiled_gemm_w12.argtypes = [C.POINTER(TGemmArgs), C.POINTER(vp), C.POINTER(vp), vp]

@@ -240,16 +240,14 @@ struct umoe_rider_pub {
 // static, byte-balanced schedule (umoe_moe_flat.hip; decode engine only): `n_wg` workgroups (<= the device's CU count: every workgroup
 // must be resident), the router riders are the first S of them.  `gu` as for umoe_grouped_gemm with fused_router and rider_pub (any nt);
 // `dn` with dn->a == gu->out; `flags`: >= n_wg device words.  Returns 1 (nothing launched) when the shapes or n_wg do not allow a
-// schedule: umoe_moe_flat_feasible answers that beforehand.
+// schedule: umoe_flat_feasible (umoe_engine_plan.h) answers that beforehand, for each weight format.
 int umoe_moe_flat(const umoe_gemm_args* gu, const umoe_gemm_args* dn, uint32_t* flags, int flag_words, int n_wg, hipStream_t s);
-bool umoe_moe_flat_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
 // The same launch on WP8 (fp8 e4m3) expert weights: the groups' `w` are WP8 blocks (include/umoe.h), e_gu / e_dn [num_groups] their
 // per-row exponents in the same group order.  Returns 1 (nothing launched) like umoe_moe_flat; the caller has no other fp8 path.
 int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const int8_t* const* e_gu, const int8_t* const* e_dn, uint32_t* flags,
                       int flag_words, int n_wg, hipStream_t s);
-bool umoe_moe_flat_fp8_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix);
 // The same launch on WP12 expert weights (bf16 in 12 bits, lossless: include/umoe.h): the groups' `w` are WP12 blocks, m_gu / m_dn
-// [num_groups] their block records.  Returns 1 (nothing launched) like umoe_moe_flat: the caller then runs umoe_moe_flat on the WP16 packs.
+// [num_groups] their block records.  Returns 1 (nothing launched) like umoe_moe_flat.
 int umoe_moe_flat_w12(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const uint32_t* const* m_gu, const uint32_t* const* m_dn, uint32_t* flags,
                       int flag_words, int n_wg, hipStream_t s);
 

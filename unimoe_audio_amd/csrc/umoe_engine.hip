@@ -12,29 +12,29 @@
 #include <vector>
 
 #include "umoe_common.h"
+#include "umoe_engine_plan.h"
 #include "umoe_riders_dev.h"
 
 namespace {
 
+// One expert-weight format of a layer, [routed experts (expert parallel: the local ones), then the n_fix shared] in every format.
+// UMOE_FMT_WP16: the packs.  WP8: blocks (their addresses in the groups' `w` slots) + per-row exponents (int8).  WP12: blocks + block
+// records (uint32).  RM (row-major bf16, the tiled prefill path): gu = gate, gu_aux = up, dn = down.
+struct Holding {
+    std::vector<const uint16_t*> gu, dn;
+    std::vector<const void*> gu_aux, dn_aux;
+    bool has = false;
+};
+
 struct LayerDev {
     umoe_layer_weights w;
-    std::vector<const uint16_t*> exp_gu, exp_dn, sh_gu, sh_dn;
-    std::vector<const uint16_t*> rm_eg, rm_eu, rm_ed, rm_sg, rm_su, rm_sd;   // row-major copies (tiled prefill path)
-    bool has_rm = false;             // has_rm_attn && has_rm_exp
+    Holding fmt[4];                  // by UMOE_FMT_*; fmt[WP16].has false: a layer without bf16 expert weights (fp8-only, w12-only)
     bool has_rm_attn = false;        // rm_qkv, rm_o: the attention GEMMs of a prefill of >= 64 rows run tiled
-    bool has_rm_exp = false;         // the row-major expert tensors: MOE_TILED on bf16 weights
-    bool exp_bf16 = true;            // the WP16 expert packs were given; false: an fp8-only layer (WP8 blocks and nothing else)
     bool set = false;
-    // fp8 expert weights (umoe_engine_set_layer_fp8): WP8 blocks + per-row exponents, [n_real routed, then n_fix shared]
-    std::vector<const uint16_t*> f8_gu, f8_dn;       // (WP8 addresses in the groups' `w` slots)
-    std::vector<const int8_t*> f8e_gu, f8e_dn;
-    bool has_f8 = false;
-    // WP12 copies of the bf16 expert weights (umoe_engine_set_layer_w12): blocks + block records, [n_real routed, then n_fix shared]
-    std::vector<const uint16_t*> w12_gu, w12_dn;
-    std::vector<const uint32_t*> w12m_gu, w12m_dn;
-    bool has_w12 = false;
-    // a w12-only layer: umoe_engine_set_layer without any bf16 expert weight, then umoe_engine_set_layer_w12 -- the WP12 copies and nothing else
-    bool w12_only() const { return set && !exp_bf16 && has_w12 && !has_f8; }
+    uint8_t holds() const {          // umoe_plan_in.holds
+        return (set ? UMOE_HOLD_SET : 0) | (fmt[UMOE_FMT_WP16].has ? UMOE_HOLD_BF16 : 0) | (fmt[UMOE_FMT_RM].has ? UMOE_HOLD_RM_EXP : 0) |
+               (has_rm_attn ? UMOE_HOLD_RM_ATTN : 0) | (fmt[UMOE_FMT_WP8].has ? UMOE_HOLD_WP8 : 0) | (fmt[UMOE_FMT_WP12].has ? UMOE_HOLD_WP12 : 0);
+    }
 };
 
 struct Carver {
@@ -113,8 +113,10 @@ struct umoe_engine {
                                  // fewer microseconds than the ragged path's four extra launches -- 2.91 vs 3.33 ms/step
     int expert_launch = 0;       // what the last dense decode layer enqueued for its experts: 0 launch per GEMM, 2 flat, 3 the one-launch
                                  // expert-parallel MoE half (umoe_engine_info; 1 was the removed box-grid launch)
-    bool fp8 = false;            // fp8 expert weights (umoe_engine_set_layer_fp8): every dense decode layer runs moe_flat_fp8_kernel, and a
-                                 // step that cannot is refused before anything is enqueued -- the other expert paths stream bf16 weights
+    // the running pass as the decision sees it (plan_pass fills it before anything is enqueued; run_layer decides from the same POD)
+    umoe_plan_in plan{};
+    umoe_plan_facts plan_facts{};
+    std::vector<uint8_t> plan_holds;
     int prefill_w12 = 0;         // the last prefill / admission ran experts on the WP12 copies (umoe_engine_info "prefill_w12")
     int prefill_fp8 = 0;         // the last prefill / admission ran its experts on the WP8 blocks (umoe_engine_info "prefill_fp8")
     int expert_w12 = 0;          // the last layer of the last decode step ran its expert launches on the WP12 copies: the flat launch, or the wide form's (umoe_engine_info "expert_w12")
@@ -142,15 +144,61 @@ struct umoe_engine {
     // wide decode (17..64 rows on one GPU, umoe_gemm_wide.hip): operand-order tiles of the row-major GEMM inputs and of silu(g)*u
     uint16_t *wide_in = nullptr, *wide_h = nullptr;
     int row_tiles = 1;                    // 16-row tiles per weight pass of the last decode step (umoe_engine_info "row_tiles")
-    bool in_decode_step = false;          // set while enqueue_step runs: a prefill of one-token prompts has n_tok == rows too and is no decode step
     // the MoE half of an expert-parallel decode layer as ONE launch with the exchange inside (umoe_moe_ep.hip); prepared at connect time
     bool ep_flat = true;                  // UMOE_EP_FLAT=0: the launch-per-kernel exchange below (also taken when the shape has no plan)
     bool epf_ready = false;
     umoe_epf_desc epf{};
     uint32_t* epf_tasks = nullptr;
-    bool ep_decode(int n_tok) const { return c.ep_size > 1 && n_tok == c.rows; }
     int groups_per_layer() const { return 2 + 2 * (c.n_real + c.n_fix); }
 };
+
+// ------------------------------------------------------------------------------------ the decision (umoe_engine_plan.h) and its input
+static int env_switch(const char* name) {      // -1 unset, else 0 / 1
+    const char* v = getenv(name);
+    return v ? (atoi(v) != 0 ? 1 : 0) : -1;
+}
+
+// The ONE place that fills the decision's input: the configuration, what every layer holds, the switches read per enqueue (the step
+// graph captures the choice, A/B scripts toggle them on a live engine) and the pass, given explicitly.
+static umoe_plan_in plan_input(const umoe_engine* e, int kind, int n_tok, std::vector<uint8_t>* holds) {
+    const umoe_engine_cfg& c = e->c;
+    umoe_plan_in p{};
+    p.rows = c.rows; p.hidden = c.hidden; p.inter_dyn = c.inter_dyn; p.inter_shared = c.inter_shared;
+    p.n_dyn = c.n_dyn; p.n_real = c.n_real; p.n_fix = c.n_fix; p.ep_size = c.ep_size;
+    p.n_cu = e->n_cu;
+    p.tiled_prefill = e->tiled_prefill; p.fuse_router = e->fuse_router; p.dense_min_rows = e->dense_min_rows;
+    p.fp8_wide = e->fp8_wide; p.w12_wide = e->w12_wide;
+    p.flat_moe = env_switch("UMOE_FLAT_MOE"); p.flat_w12 = env_switch("UMOE_FLAT_W12");
+    p.wide_w12 = env_switch("UMOE_WIDE_W12"); p.wide_decode = env_switch("UMOE_WIDE_DECODE");
+    p.kind = kind; p.n_tok = n_tok;
+    holds->resize(e->layers.size());
+    for (size_t l = 0; l < e->layers.size(); ++l) (*holds)[l] = e->layers[l].holds();
+    p.n_layers = (int)e->layers.size(); p.holds = holds->data();
+    return p;
+}
+
+// Runs the decision for every layer of the pass BEFORE anything is enqueued or any state word is reset: a pass that would stream a weight
+// some layer does not hold is refused here, on the host, with a message that names it.  run_layer decides again from the POD kept here.
+static int plan_pass(umoe_engine* e, int kind, int n_tok) {
+    e->plan = plan_input(e, kind, n_tok, &e->plan_holds);
+    e->plan_facts = umoe_plan_engine_facts(e->plan);
+    char msg[768];
+    umoe_plan_out o;
+    for (int l = 0; l < e->c.layers; ++l)
+        UMOE_REQUIRE(umoe_plan_layer(e->plan, e->plan_facts, l, &o, msg, sizeof(msg)) == 0, "%s", msg);
+    return 0;
+}
+
+extern "C" int umoe_engine_plan_probe(const umoe_plan_in* in, int in_bytes, umoe_plan_out* out, int32_t* rc, char* msg, int msg_len) {
+    UMOE_REQUIRE(in && out && rc && msg && msg_len > 0 && in->holds && in->n_layers > 0, "umoe_engine_plan_probe: bad argument");
+    UMOE_REQUIRE(in_bytes == (int)sizeof(umoe_plan_in), "umoe_engine_plan_probe: umoe_plan_in has %zu bytes here, the caller's %d", sizeof(umoe_plan_in), in_bytes);
+    const umoe_plan_facts f = umoe_plan_engine_facts(*in);
+    for (int l = 0; l < in->n_layers; ++l) {
+        msg[(size_t)l * msg_len] = 0;
+        rc[l] = umoe_plan_layer(*in, f, l, out + l, msg + (size_t)l * msg_len, (size_t)msg_len);
+    }
+    return 0;
+}
 
 static size_t carve(umoe_engine* e, int n_tok, char* base) {
     const umoe_engine_cfg& c = e->c;
@@ -179,7 +227,7 @@ static size_t carve(umoe_engine* e, int n_tok, char* base) {
     // wide decode: [tiles][16 * max(D, HD)] for hin / attn_out / the post-attention norm rows, [G][tiles][16 * Imax] for silu(g)*u.
     // Sized by the engine's rows, not by n_tok.  Like every buffer carved here they move when the workspace grows: umoe_engine_reserve is what
     // keeps them (and a captured step graph) fixed across admissions
-    const int wt = (c.ep_size == 1 && c.rows > 16 && c.rows <= 64) ? ceil_div(c.rows, 16) : 0;
+    const int wt = (c.ep_size == 1 && c.rows > 16 && c.rows <= 64) ? ceil_div(c.rows, 16) : 0;      // (a superset of umoe_plan_wide_shape: sized by the rows alone)
     e->wide_in = k.take<uint16_t>((size_t)wt * 16 * (D > HD ? D : HD));
     e->wide_h = k.take<uint16_t>((size_t)wt * 16 * Imax * G);
     e->part_o = k.take<float>((size_t)n_tok * c.heads * splits * c.head_dim);
@@ -225,57 +273,14 @@ static int ensure_workspace(umoe_engine* e, int n_tok) {
     return 0;
 }
 
-// group table for a pass over n_tok tokens
-static bool dense_mode(const umoe_engine* e, int n_tok) {
-    if (e->ep_decode(n_tok)) return true;   // expert parallel decode IS the dense layout: every rank's rows visit every expert
-    if (e->adm_row0 >= 0) return false;     // an admission prefill of rows tokens is a prefill: ragged dispatch, never the decode launches
-    return n_tok == e->c.rows && n_tok <= 16 && n_tok >= e->dense_min_rows;
-}
-
-// UMOE_WIDE_DECODE=0: decode steps of more than 16 rows take the ragged path (router + dispatch tables, a weight pass per 16 rows); =1: the
-// wide form at every size its shapes allow; unset: the wide form at the sizes where it was MEASURED faster than the ragged path of the same
-// process by more than the run-to-run spread (profiles/wide_decode.json).  Read per enqueue like UMOE_FLAT_MOE.
-static bool wide_measured_faster(int rows) {
-    // measured (ms/step ragged | wide, 36 layers): batch 9 4.554 | 4.553 and 12 4.625 | 4.619 inside the spread -> ragged; 16 5.072 | 4.661,
-    // 24 6.099 | 5.544, 32 8.122 | 5.929 -> wide.  Between the measured sizes only what the figures bound: 4 tiles (batch 25..32) cost at most
-    // the 5.929 of 32 and the ragged path at least the 6.099 of 24; batch 13..15 and 17..23 have no such bound and stay ragged
-    return rows == 32 || (rows >= 48 && rows <= 64);
-}
-static bool wide_on(int rows) {
-    const char* v = getenv("UMOE_WIDE_DECODE");
-    if (!v) return wide_measured_faster(rows);
-    return atoi(v) != 0;
-}
-// A decode step (enqueue_step: T == 1; never a prefill, whatever its token count) of 17..64 rows (batch 9..32) in the dense layout with every weight streamed ONCE for all row tiles (umoe_gemm_wide.hip): QKV,
-// o_proj, gate/up, down and the codec head.  One GPU, bf16 weights, the router shapes of the 16-row step; an admission prefill is a prefill.
-// Takes precedence over the tiled kernels at 64 rows.  Expert-parallel engines never take it; fp8 engines only with the switch
-// umoe_engine_set_fp8_wide, and then at EVERY size (wide_measured_faster compares two bf16 paths; an fp8 engine has no other path above 16
-// rows, so only UMOE_WIDE_DECODE=0 keeps it from the wide form -- and its step is refused, fp8_step_check).
-static bool wide_shapes(const umoe_engine* e, int n_tok) {
-    const umoe_engine_cfg& c = e->c;
-    return e->adm_row0 < 0 && n_tok == c.rows && n_tok > 16 && n_tok <= 64 && c.ep_size == 1 && c.n_dyn == 9 && c.n_fix == 2 && c.hidden == 2048 &&
-           c.n_real + c.n_fix <= 12;
-}
-static bool fp8_wide_on() {
-    const char* v = getenv("UMOE_WIDE_DECODE");
-    return !v || atoi(v) != 0;
-}
-static int w12_only_layers(const umoe_engine* e) {
-    int n = 0;
-    for (const LayerDev& L : e->layers) n += L.w12_only() ? 1 : 0;
-    return n;
-}
-static bool wide_mode(const umoe_engine* e, int n_tok) {
-    if (!e->in_decode_step || !wide_shapes(e, n_tok)) return false;
-    if (w12_only_layers(e)) return true;      // at EVERY size, on the WP12 copies: a w12-only layer has no other path above 16 rows (w12_only_check saw the switches)
-    return e->fp8 ? e->fp8_wide && fp8_wide_on() : wide_on(n_tok);
-}
-
+// group table for a pass (UMOE_PASS_*) over n_tok tokens
 // (the wide form reads no group table: its launches take the layers' weight pointers; the table built here serves UMOE_WIDE_DECODE=0)
-static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
+static int build_groups(umoe_engine* e, int kind, int n_tok, hipStream_t s) {
     if (e->groups_for_tok == n_tok) return 0;
     const umoe_engine_cfg& c = e->c;
-    const bool dense = dense_mode(e, n_tok);
+    std::vector<uint8_t> holds;      // (the table's shape depends on the pass alone; the POD plan_pass kept is not touched)
+    const umoe_plan_in pass = plan_input(e, kind, n_tok, &holds);
+    const bool dense = umoe_plan_dense(pass);
     const int G = c.n_real + c.n_fix, GPL = e->groups_per_layer();
     std::vector<umoe_group_t>& h = e->h_groups;
     h.assign((size_t)c.layers * GPL + 1, umoe_group_t{});
@@ -283,6 +288,8 @@ static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
     for (int l = 0; l < c.layers; ++l) {
         const LayerDev& L = e->layers[l];
         UMOE_REQUIRE(L.set, "umoe_engine: layer %d has no weights", l);
+        const Holding& W = L.fmt[UMOE_FMT_WP16];      // (all NULL in a layer without bf16 expert weights: no pass that reads them is enqueued)
+        const int sh0 = e->E_loc;                     // the shared experts behind the (local) routed ones
         umoe_group_t* g = &h[(size_t)l * GPL];
         memset(g, 0, sizeof(umoe_group_t) * GPL);
         // qkv
@@ -292,7 +299,7 @@ static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
         g[1].w = L.w.o_w; g[1].static_count = n_tok; g[1].n_blocks = c.hidden / 16; g[1].k = c.heads * c.head_dim;
         umoe_group_t* gu = g + 2;
         umoe_group_t* dn = g + 2 + G;
-        if (e->ep_decode(n_tok)) {
+        if (umoe_plan_ep_decode(pass)) {
             // expert parallel decode: one group per (local expert x, source rank t) over the gathered rows xg[t][row]; h rows
             // (x*ep + t)*rows; outputs for rank t's rows at ybuf rows yloc0 + (t*E_loc + x)*rows (shipped by the return push),
             // the own rank's straight into the dense layout row (global expert)*rows the combine reads (peer modes)
@@ -301,26 +308,26 @@ static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
             for (int x = 0; x < El; ++x)
                 for (int t = 0; t < ep; ++t) {
                     const int q = x * ep + t;
-                    gu[q].w = L.exp_gu[x]; gu[q].n_blocks = 2 * c.inter_dyn / 16; gu[q].k = c.hidden;
+                    gu[q].w = W.gu[x]; gu[q].n_blocks = 2 * c.inter_dyn / 16; gu[q].k = c.hidden;
                     gu[q].static_count = n_tok; gu[q].a_row_base = t * n_tok; gu[q].out_row_base = q * n_tok;
-                    dn[q].w = L.exp_dn[x]; dn[q].n_blocks = c.hidden / 16; dn[q].k = c.inter_dyn;
+                    dn[q].w = W.dn[x]; dn[q].n_blocks = c.hidden / 16; dn[q].k = c.inter_dyn;
                     dn[q].static_count = n_tok; dn[q].a_row_base = q * n_tok;
                     dn[q].out_row_base = (t == c.ep_rank && own_direct) ? (c.ep_rank * El + x) * n_tok : yloc0 + (t * El + x) * n_tok;
                 }
             for (int i = 0; i < c.n_fix; ++i) {
                 const int x = c.n_real + i;
-                gu[x].w = L.sh_gu[i]; gu[x].static_count = n_tok;
+                gu[x].w = W.gu[sh0 + i]; gu[x].static_count = n_tok;
                 gu[x].a_row_base = own_direct ? 0 : c.ep_rank * n_tok;   // peer modes: the row-major h2; RCCL mode: own tile of xg
                 gu[x].out_row_base = slots_routed + i * n_tok; gu[x].n_blocks = 2 * c.inter_shared / 16; gu[x].k = c.hidden;
-                dn[x].w = L.sh_dn[i]; dn[x].static_count = n_tok; dn[x].a_row_base = slots_routed + i * n_tok;
+                dn[x].w = W.dn[sh0 + i]; dn[x].static_count = n_tok; dn[x].a_row_base = slots_routed + i * n_tok;
                 dn[x].out_row_base = slots_routed + i * n_tok; dn[x].n_blocks = c.hidden / 16; dn[x].k = c.inter_shared;
             }
             continue;
         }
         const int n_packed = c.ep_size > 1 ? 0 : c.n_real;   // expert parallel prefill: tiled kernels on the row-major tensors only
         for (int x = 0; x < c.n_real; ++x) {
-            gu[x].w = x < n_packed ? L.exp_gu[x] : nullptr; gu[x].n_blocks = 2 * c.inter_dyn / 16; gu[x].k = c.hidden;
-            dn[x].w = x < n_packed ? L.exp_dn[x] : nullptr; dn[x].n_blocks = c.hidden / 16; dn[x].k = c.inter_dyn;
+            gu[x].w = x < n_packed ? W.gu[x] : nullptr; gu[x].n_blocks = 2 * c.inter_dyn / 16; gu[x].k = c.hidden;
+            dn[x].w = x < n_packed ? W.dn[x] : nullptr; dn[x].n_blocks = c.hidden / 16; dn[x].k = c.inter_dyn;
             if (dense) {   // expert x owns rows [x*n_tok, (x+1)*n_tok) of the h / y buffers, token order
                 gu[x].static_count = n_tok; gu[x].out_row_base = x * n_tok;
                 dn[x].static_count = n_tok; dn[x].a_row_base = x * n_tok; dn[x].out_row_base = x * n_tok;
@@ -331,9 +338,9 @@ static int build_groups(umoe_engine* e, int n_tok, hipStream_t s) {
         }
         for (int i = 0; i < c.n_fix; ++i) {
             const int x = c.n_real + i;
-            gu[x].w = L.sh_gu[i]; gu[x].static_count = n_tok; gu[x].out_row_base = slots_routed + i * n_tok;
+            gu[x].w = W.gu[sh0 + i]; gu[x].static_count = n_tok; gu[x].out_row_base = slots_routed + i * n_tok;
             gu[x].n_blocks = 2 * c.inter_shared / 16; gu[x].k = c.hidden;
-            dn[x].w = L.sh_dn[i]; dn[x].static_count = n_tok; dn[x].a_row_base = slots_routed + i * n_tok;
+            dn[x].w = W.dn[sh0 + i]; dn[x].static_count = n_tok; dn[x].a_row_base = slots_routed + i * n_tok;
             dn[x].out_row_base = slots_routed + i * n_tok; dn[x].n_blocks = c.hidden / 16; dn[x].k = c.inter_shared;
         }
     }
@@ -446,83 +453,71 @@ extern "C" void umoe_engine_destroy(umoe_engine* e) {
 extern "C" int umoe_engine_set_layer(umoe_engine* e, int layer, const umoe_layer_weights* w) {
     UMOE_REQUIRE(e && w && layer >= 0 && layer < e->c.layers, "umoe_engine_set_layer: bad layer %d", layer);
     LayerDev& L = e->layers[layer];
+    const int n_fix = e->c.n_fix;
     L.w = *w;
-    // an fp8-only layer: no bf16 expert weight at all, neither the WP16 packs nor the row-major tensors (umoe_engine_set_layer_fp8
-    // follows with the WP8 blocks; every path that would stream a bf16 expert weight is refused, fp8_only_check)
+    // a layer without bf16 expert weights: neither the WP16 packs nor the row-major tensors (umoe_engine_set_layer_fp8 or
+    // umoe_engine_set_layer_w12 follows; every pass that would stream a bf16 expert weight is refused, umoe_engine_plan.h)
     const bool any_exp = w->exp_gu || w->exp_dn || w->sh_gu || w->sh_dn || w->rm_exp_gate || w->rm_exp_up || w->rm_exp_down || w->rm_sh_gate ||
                          w->rm_sh_up || w->rm_sh_down;
-    L.exp_bf16 = any_exp;
+    Holding& W = L.fmt[UMOE_FMT_WP16];
+    W.has = any_exp;
+    W.gu.assign(e->E_loc + n_fix, nullptr); W.dn.assign(e->E_loc + n_fix, nullptr);
     if (any_exp) {
-        UMOE_REQUIRE(w->exp_gu && w->exp_dn && (e->c.n_fix == 0 || (w->sh_gu && w->sh_dn)),
+        UMOE_REQUIRE(w->exp_gu && w->exp_dn && (n_fix == 0 || (w->sh_gu && w->sh_dn)),
                      "umoe_engine_set_layer: layer %d: exp_gu / exp_dn / sh_gu / sh_dn go together (all NULL with every rm_exp_* / rm_sh_*: an fp8-only layer)", layer);
-        L.exp_gu.assign(w->exp_gu, w->exp_gu + e->E_loc);     // expert parallel: the LOCAL experts' packed weights only
-        L.exp_dn.assign(w->exp_dn, w->exp_dn + e->E_loc);
-        L.sh_gu.assign(w->sh_gu, w->sh_gu + e->c.n_fix);
-        L.sh_dn.assign(w->sh_dn, w->sh_dn + e->c.n_fix);
+        for (int x = 0; x < e->E_loc; ++x) { W.gu[x] = w->exp_gu[x]; W.dn[x] = w->exp_dn[x]; }     // expert parallel: the LOCAL experts' packed weights only
+        for (int i = 0; i < n_fix; ++i) { W.gu[e->E_loc + i] = w->sh_gu[i]; W.dn[e->E_loc + i] = w->sh_dn[i]; }
     } else {
         UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer: layer %d: an fp8-only layer (no bf16 expert weights) is not supported expert parallel", layer);
-        L.exp_gu.assign(e->E_loc, nullptr); L.exp_dn.assign(e->E_loc, nullptr);
-        L.sh_gu.assign(e->c.n_fix, nullptr); L.sh_dn.assign(e->c.n_fix, nullptr);
     }
     L.has_rm_attn = w->rm_qkv && w->rm_o;
-    L.has_rm_exp = w->rm_exp_gate && w->rm_exp_up && w->rm_exp_down && (e->c.n_fix == 0 || (w->rm_sh_gate && w->rm_sh_up && w->rm_sh_down));
-    L.has_rm = L.has_rm_attn && L.has_rm_exp;
-    L.rm_eg.clear(); L.rm_eu.clear(); L.rm_ed.clear(); L.rm_sg.clear(); L.rm_su.clear(); L.rm_sd.clear();
-    if (L.has_rm) {
-        L.rm_eg.assign(w->rm_exp_gate, w->rm_exp_gate + e->c.n_real);
-        L.rm_eu.assign(w->rm_exp_up, w->rm_exp_up + e->c.n_real);
-        L.rm_ed.assign(w->rm_exp_down, w->rm_exp_down + e->c.n_real);
-        if (e->c.n_fix) {
-            L.rm_sg.assign(w->rm_sh_gate, w->rm_sh_gate + e->c.n_fix);
-            L.rm_su.assign(w->rm_sh_up, w->rm_sh_up + e->c.n_fix);
-            L.rm_sd.assign(w->rm_sh_down, w->rm_sh_down + e->c.n_fix);
-        }
+    Holding& R = L.fmt[UMOE_FMT_RM];
+    R.has = w->rm_exp_gate && w->rm_exp_up && w->rm_exp_down && (n_fix == 0 || (w->rm_sh_gate && w->rm_sh_up && w->rm_sh_down));
+    R.gu.clear(); R.gu_aux.clear(); R.dn.clear();
+    if (R.has) {
+        R.gu.assign(w->rm_exp_gate, w->rm_exp_gate + e->c.n_real); R.gu.insert(R.gu.end(), w->rm_sh_gate, w->rm_sh_gate + (w->rm_sh_gate ? n_fix : 0));
+        R.gu_aux.assign(w->rm_exp_up, w->rm_exp_up + e->c.n_real); R.gu_aux.insert(R.gu_aux.end(), w->rm_sh_up, w->rm_sh_up + (w->rm_sh_up ? n_fix : 0));
+        R.dn.assign(w->rm_exp_down, w->rm_exp_down + e->c.n_real); R.dn.insert(R.dn.end(), w->rm_sh_down, w->rm_sh_down + (w->rm_sh_down ? n_fix : 0));
     }
     L.set = true;
     e->groups_for_tok = -1;
     return 0;
 }
 
+// packed expert weights of one layer in `format` (WP8: blocks + per-row exponents; WP12: blocks + block records): the body of
+// umoe_engine_set_layer_fp8 and umoe_engine_set_layer_w12
+template <typename Aux>
+static int set_layer_packed(umoe_engine* e, int layer, int format, const char* who, const char* what, const uint8_t* const* gu, const Aux* const* gu_aux,
+                            const uint8_t* const* dn, const Aux* const* dn_aux) {
+    UMOE_REQUIRE(e && gu && gu_aux && dn && dn_aux && layer >= 0 && layer < e->c.layers, "%s: bad argument (layer %d)", who, layer);
+    UMOE_REQUIRE(e->c.ep_size == 1, "%s: %s expert weights run on the flat expert launch only, not expert parallel (ep_size %d)", who, what, e->c.ep_size);
+    LayerDev& L = e->layers[layer];
+    if (format == UMOE_FMT_WP8) {
+        UMOE_REQUIRE(L.set, "%s: umoe_engine_set_layer(%d) first", who, layer);
+    } else {      // (a layer that umoe_engine_set_layer received with every bf16 expert pointer NULL becomes a w12-only layer here)
+        UMOE_REQUIRE(L.set && !L.fmt[UMOE_FMT_WP8].has, "%s: umoe_engine_set_layer(%d) with the WP16 packs first (and no fp8 weights)", who, layer);
+    }
+    const int G = e->c.n_real + e->c.n_fix;
+    for (int i = 0; i < G; ++i) UMOE_REQUIRE(gu[i] && gu_aux[i] && dn[i] && dn_aux[i], "%s: layer %d group %d: null pointer", who, layer, i);
+    Holding& H = L.fmt[format];
+    H.gu.resize(G); H.dn.resize(G);
+    for (int i = 0; i < G; ++i) {      // (the blocks' addresses travel in the groups' `w` slots)
+        H.gu[i] = reinterpret_cast<const uint16_t*>(gu[i]);
+        H.dn[i] = reinterpret_cast<const uint16_t*>(dn[i]);
+    }
+    H.gu_aux.assign(gu_aux, gu_aux + G); H.dn_aux.assign(dn_aux, dn_aux + G);
+    H.has = true;
+    return 0;
+}
+
 extern "C" int umoe_engine_set_layer_fp8(umoe_engine* e, int layer, const uint8_t* const* gu8, const int8_t* const* gu_e, const uint8_t* const* dn8,
                                          const int8_t* const* dn_e) {
-    UMOE_REQUIRE(e && gu8 && gu_e && dn8 && dn_e && layer >= 0 && layer < e->c.layers, "umoe_engine_set_layer_fp8: bad argument (layer %d)", layer);
-    UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer_fp8: fp8 expert weights run on the flat expert launch only, not expert parallel (ep_size %d)",
-                 e->c.ep_size);
-    LayerDev& L = e->layers[layer];
-    UMOE_REQUIRE(L.set, "umoe_engine_set_layer_fp8: umoe_engine_set_layer(%d) first", layer);
-    const int G = e->c.n_real + e->c.n_fix;
-    for (int i = 0; i < G; ++i)
-        UMOE_REQUIRE(gu8[i] && gu_e[i] && dn8[i] && dn_e[i], "umoe_engine_set_layer_fp8: layer %d group %d: null pointer", layer, i);
-    L.f8_gu.assign(G, nullptr); L.f8_dn.assign(G, nullptr);
-    for (int i = 0; i < G; ++i) {
-        L.f8_gu[i] = reinterpret_cast<const uint16_t*>(gu8[i]);
-        L.f8_dn[i] = reinterpret_cast<const uint16_t*>(dn8[i]);
-    }
-    L.f8e_gu.assign(gu_e, gu_e + G); L.f8e_dn.assign(dn_e, dn_e + G);
-    L.has_f8 = true;
-    e->fp8 = true;
-    return 0;
+    return set_layer_packed(e, layer, UMOE_FMT_WP8, "umoe_engine_set_layer_fp8", "fp8", gu8, gu_e, dn8, dn_e);
 }
 
 extern "C" int umoe_engine_set_layer_w12(umoe_engine* e, int layer, const uint8_t* const* gu12, const uint32_t* const* gu_m, const uint8_t* const* dn12,
                                          const uint32_t* const* dn_m) {
-    UMOE_REQUIRE(e && gu12 && gu_m && dn12 && dn_m && layer >= 0 && layer < e->c.layers, "umoe_engine_set_layer_w12: bad argument (layer %d)", layer);
-    UMOE_REQUIRE(e->c.ep_size == 1, "umoe_engine_set_layer_w12: WP12 expert weights run on the flat expert launch only, not expert parallel (ep_size %d)",
-                 e->c.ep_size);
-    LayerDev& L = e->layers[layer];
-    // (a layer that umoe_engine_set_layer received with every bf16 expert pointer NULL becomes a w12-only layer here)
-    UMOE_REQUIRE(L.set && !L.has_f8, "umoe_engine_set_layer_w12: umoe_engine_set_layer(%d) with the WP16 packs first (and no fp8 weights)", layer);
-    const int G = e->c.n_real + e->c.n_fix;
-    for (int i = 0; i < G; ++i)
-        UMOE_REQUIRE(gu12[i] && gu_m[i] && dn12[i] && dn_m[i], "umoe_engine_set_layer_w12: layer %d group %d: null pointer", layer, i);
-    L.w12_gu.assign(G, nullptr); L.w12_dn.assign(G, nullptr);
-    for (int i = 0; i < G; ++i) {
-        L.w12_gu[i] = reinterpret_cast<const uint16_t*>(gu12[i]);
-        L.w12_dn[i] = reinterpret_cast<const uint16_t*>(dn12[i]);
-    }
-    L.w12m_gu.assign(gu_m, gu_m + G); L.w12m_dn.assign(dn_m, dn_m + G);
-    L.has_w12 = true;
-    return 0;
+    return set_layer_packed(e, layer, UMOE_FMT_WP12, "umoe_engine_set_layer_w12", "WP12", gu12, gu_m, dn12, dn_m);
 }
 
 extern "C" int umoe_engine_set_w12_wide(umoe_engine* e, int on) {
@@ -767,7 +762,8 @@ static int run_moe_ep_flat(umoe_engine* e, int l, int n_tok, hipStream_t s) {
     umoe_epf_desc d = e->epf;
     d.router = &ra; d.pub = &pub; d.rank = rank; d.loopback = e->ep_mode == UMOE_EP_LOOPBACK;
     d.peer_base = e->ep_peers; d.disp_off = UMOE_EP_FLAG_BYTES; d.ret_off = UMOE_EP_FLAG_BYTES + (size_t)ep * tile;
-    d.w_lgu = L.exp_gu.data(); d.w_ldn = L.exp_dn.data(); d.w_sgu = L.sh_gu.data(); d.w_sdn = L.sh_dn.data();
+    const Holding& W = L.fmt[UMOE_FMT_WP16];
+    d.w_lgu = W.gu.data(); d.w_ldn = W.dn.data(); d.w_sgu = W.gu.data() + El; d.w_sdn = W.dn.data() + El;
     d.xgp = e->xgp; d.hpk = e->hpk;
     d.h_sh = e->hbuf; d.ldh = Imax; d.h_row0 = c.n_real * n_tok;
     d.y_sh = e->ybuf; d.ldy = D; d.y_row0 = c.n_real * n_tok;
@@ -852,7 +848,7 @@ static int run_moe_ep(umoe_engine* e, int l, int n_tok, hipStream_t s) {
     PROF(K_DISPATCH);
     // ---- local experts over every rank's rows: one pass over each expert's weights
     umoe_mt_args gu{};
-    for (int q = 0; q < El; ++q) gu.w[q] = L.exp_gu[q];
+    for (int q = 0; q < El; ++q) gu.w[q] = L.fmt[UMOE_FMT_WP16].gu[q];
     gu.num_groups = El; gu.n_blocks = 2 * c.inter_dyn / 16; gu.k = D; gu.tiles = ep; gu.n_rows = n_tok;
     gu.b = e->xgp; gu.b_group_tiles = 0; gu.h_out = e->hpk; gu.epilogue = UMOE_EPI_SWIGLU;
     gu.fused_router = e->fuse_router ? &ra : nullptr;
@@ -864,7 +860,7 @@ static int run_moe_ep(umoe_engine* e, int l, int n_tok, hipStream_t s) {
     uint16_t* yloc = e->ybuf + (size_t)G * n_tok * D;                        // [dest rank][local expert][row][D]
     uint16_t* slab_ret = reinterpret_cast<uint16_t*>(e->ep_region + UMOE_EP_FLAG_BYTES + (size_t)ep * tile);   // [global expert][row][D]
     umoe_mt_args dn{};
-    for (int q = 0; q < El; ++q) dn.w[q] = L.exp_dn[q];
+    for (int q = 0; q < El; ++q) dn.w[q] = L.fmt[UMOE_FMT_WP16].dn[q];
     dn.num_groups = El; dn.n_blocks = D / 16; dn.k = c.inter_dyn; dn.tiles = ep; dn.n_rows = n_tok;
     dn.b = e->hpk; dn.b_group_tiles = ep; dn.ldo = D; dn.epilogue = UMOE_EPI_BF16;
     for (int q = 0; q < El; ++q)
@@ -897,53 +893,59 @@ static int run_moe_ep(umoe_engine* e, int l, int n_tok, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------ the MoE half of one layer (ep_size 1)
-// What a layer's router and experts are enqueued as: decided ONCE per layer on the host, from the shape and the switches, and each
-// form is one block of run_layer with no fall-through into another.
-#define W12_ONLY_MISSING "this engine holds no bf16 expert weights for its w12-only layers (exp_gu / exp_dn / sh_gu / sh_dn and rm_exp_* / rm_sh_* were not given: the WP12 copies are all there is)"
-extern "C" int umoe_moe_flat_plan_w12_probe(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix, double* out, int out_len);
-enum MoeForm {
-    MOE_TILED,     // >= 64 rows (prefill): router + dispatch tables, tiled MFMA GEMMs on the row-major weights
-    MOE_RAGGED,    // router + dispatch tables, weight-streaming GEMMs over the experts' ragged row lists
-    MOE_FLAT,      // dense decode, ONE launch: router riders, RMSNorm, gate/up and down, one workgroup per CU (umoe_moe_flat.hip)
-    MOE_RIDERS,    // dense decode, launch per kernel: RMSNorm | gate/up with the router riding in it | down
-    MOE_ROUTER,    // dense decode, launch per kernel: router | gate/up | down
-    MOE_WIDE,      // dense decode of 17..64 rows: router | RMSNorm + re-lay | gate/up | down, each weight streamed once for all row tiles
-};
+// Which form a layer takes and which format its expert launches stream is decided in umoe_engine_plan.h; the three launch families
+// below take the format and dispatch to the exports of include/umoe.h / umoe_common.h.  `w`: the holding's blocks (their addresses as the
+// groups' `w` slots carry them), `aux`: its exponents (WP8) or block records (WP12), both in the launch's group order.
+template <typename T, typename U>
+static void typed(const U* const* src, int n, const T** dst) {
+    for (int i = 0; i < n; ++i) dst[i] = reinterpret_cast<const T*>(src[i]);
+}
 
-// UMOE_FLAT_MOE=0: never the flat expert launch.  Read per enqueue: the step graph captures the choice, A/B scripts toggle it on a live engine.
-static bool flat_w12_on() {      // UMOE_FLAT_W12=0: the flat launch on the WP16 packs although the layer has WP12 copies (A/B, tests)
-    const char* v = getenv("UMOE_FLAT_W12");
-    return !v || atoi(v) != 0;
-}
-static bool wide_w12_on() {      // UMOE_WIDE_W12=0: the wide step's expert launches on the WP16 packs although the switch is on (A/B, escape hatch)
-    const char* v = getenv("UMOE_WIDE_W12");
-    return !v || atoi(v) != 0;
-}
-static bool flat_moe_on() {
-    const char* v = getenv("UMOE_FLAT_MOE");
-    return !v || atoi(v) != 0;
-}
-// workgroups of the flat expert launch: one per CU.  Its in-launch hand-offs need every workgroup RESIDENT at once (a waiting workgroup
-// never yields its CU), so a device that exposes fewer CUs than a schedule needs (partition, CU mask, UMOE_FAKE_CUS) takes the
-// launch-per-kernel form instead of discovering it by a timeout.
-static int flat_wgs(const umoe_engine* e) { return e->n_cu < 256 ? e->n_cu : 256; }
-
-static MoeForm moe_form(const umoe_engine* e, const LayerDev& L, int n_tok) {
-    const umoe_engine_cfg& c = e->c;
-    if (wide_mode(e, n_tok)) return MOE_WIDE;
-    if (!dense_mode(e, n_tok)) {
-        // an fp8-only layer: the tiled kernel on the WP8 blocks at EVERY row count (nothing else reads e4m3 outside the decode launches;
-        // fp8_only_check refused UMOE_TILED_PREFILL=0 and more than 12 groups before anything was enqueued)
-        // (a w12-only layer likewise: the tiled kernel on the WP12 copies, umoe_tiled_gemm_w12; w12_only_check refused the same switches)
-        if (!L.exp_bf16) return MOE_TILED;
-        return (L.has_rm && n_tok >= 64 && e->tiled_prefill && c.n_real + c.n_fix <= 12) ? MOE_TILED : MOE_RAGGED;
+static int tiled_launch(int format, const umoe_tgemm_args* ta, const uint16_t* const* w, const void* const* aux, hipStream_t s) {
+    if (format == UMOE_FMT_RM) return umoe_tiled_gemm(ta, s);      // (reads the groups' w / w2)
+    const uint8_t* w8[12];
+    typed(w, ta->num_groups, w8);
+    if (format == UMOE_FMT_WP8) {
+        const int8_t* ex[12];
+        typed(aux, ta->num_groups, ex);
+        return umoe_tiled_gemm_wp8(ta, w8, ex, s);
     }
-    // the shapes the router riders are written for (router4_body<9, 2>; dense_mode: <= 16 rows)
-    if (!(e->fuse_router && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096))) return MOE_ROUTER;
-    const int n_wg = flat_wgs(e);
-    if (flat_moe_on() && n_wg > 0 && umoe_moe_flat_feasible(n_wg, n_tok, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix)) return MOE_FLAT;
-    return MOE_RIDERS;
+    const uint32_t* wm[12];
+    typed(aux, ta->num_groups, wm);
+    return umoe_tiled_gemm_w12(ta, w8, wm, s);
 }
+
+static int wide_launch(int format, const uint16_t* const* w, const void* const* aux, const int* nb, const int* k, int G, int n_tok, const uint16_t* const* b,
+                       void* const* out, int ldo, int n_valid, int epilogue, int u, hipStream_t s) {
+    if (format == UMOE_FMT_WP16) return umoe_gemm_wide(w, nb, k, G, n_tok, b, out, ldo, n_valid, nullptr, nullptr, epilogue, 8, u, s);
+    const uint8_t* w8[12];
+    typed(w, G, w8);
+    if (format == UMOE_FMT_WP8) {
+        const int8_t* ex[12];
+        typed(aux, G, ex);
+        return umoe_gemm_wide_fp8(w8, ex, nb, k, G, n_tok, b, out, ldo, n_valid, epilogue, 8, u, s);
+    }
+    const uint32_t* wm[12];
+    typed(aux, G, wm);
+    return umoe_gemm_wide_w12(w8, wm, nb, k, G, n_tok, b, out, ldo, n_valid, epilogue, 8, u, s);
+}
+
+// (gu / dn: the launch arguments with groups_host already carrying the format's blocks)
+static int flat_launch(int format, const umoe_gemm_args* gu, const umoe_gemm_args* dn, const void* const* aux_gu, const void* const* aux_dn, uint32_t* flags,
+                       int flag_words, int n_wg, hipStream_t s) {
+    if (format == UMOE_FMT_WP16) return umoe_moe_flat(gu, dn, flags, flag_words, n_wg, s);
+    if (format == UMOE_FMT_WP8) {
+        const int8_t *eu[UMOE_MAXE], *ed[UMOE_MAXE];
+        typed(aux_gu, gu->num_groups, eu); typed(aux_dn, gu->num_groups, ed);
+        return umoe_moe_flat_fp8(gu, dn, eu, ed, flags, flag_words, n_wg, s);
+    }
+    const uint32_t *mu[UMOE_MAXE], *md[UMOE_MAXE];
+    typed(aux_gu, gu->num_groups, mu); typed(aux_dn, gu->num_groups, md);
+    return umoe_moe_flat_w12(gu, dn, mu, md, flags, flag_words, n_wg, s);
+}
+
+// the flat launch's gate/up groups come the SHARED experts first (h_gu_pub); its down groups in the holdings' order
+static int flat_gu_index(const umoe_engine_cfg& c, int i) { return i < c.n_fix ? c.n_real + i : i - c.n_fix; }
 
 // gate/up SwiGLU, then the down projections: one weight-streaming launch each
 static int experts_two_launches(umoe_engine* e, const umoe_gemm_args* gu, const umoe_gemm_args* dn, hipStream_t s) {
@@ -955,60 +957,37 @@ static int experts_two_launches(umoe_engine* e, const umoe_gemm_args* gu, const 
     return 0;
 }
 
-// the same two GEMMs on the tiled MFMA kernel; gu_groups: the layer's gate/up groups, the down groups behind them (same row tables)
-static int experts_tiled(umoe_engine* e, const LayerDev& L, const umoe_group_t* gu_groups, int n_tok, hipStream_t s) {
+// the same two GEMMs on the tiled MFMA kernel over the layer's `format` holding (row-major bf16, or the WP8 blocks / WP12 copies of a
+// layer that holds nothing else); gu_groups: the layer's gate/up groups, the down groups behind them (same row tables)
+static int experts_tiled(umoe_engine* e, const LayerDev& L, int format, const umoe_group_t* gu_groups, int n_tok, hipStream_t s) {
     const umoe_engine_cfg& c = e->c;
     const int D = c.hidden, G = c.n_real + c.n_fix, Imax = c.inter_dyn > c.inter_shared ? c.inter_dyn : c.inter_shared;
+    const Holding& H = L.fmt[format];
+    const bool rm = format == UMOE_FMT_RM;
     int rc;
-    const bool w12 = L.w12_only();   // a w12-only layer: the same two launches on the WP12 copies (umoe_tiled_gemm_w12), [routed, then shared]
-    const bool f8 = !L.exp_bf16 && !w12;      // an fp8-only layer: the same two launches on the WP8 blocks (umoe_tiled_gemm_wp8), [routed, then shared]
-    const uint8_t* w8[12];
-    const int8_t* ex[12];
-    const uint32_t* wm[12];
     umoe_tgroup_t tg[12];
-    memset(tg, 0, sizeof(tg));
-    for (int x = 0; x < G; ++x) {
-        const umoe_group_t& src = gu_groups[x];
-        const bool sh = x >= c.n_real;
-        if (w12) {
-            w8[x] = reinterpret_cast<const uint8_t*>(L.w12_gu[x]); wm[x] = L.w12m_gu[x];
-        } else if (f8) {
-            w8[x] = reinterpret_cast<const uint8_t*>(L.f8_gu[x]); ex[x] = L.f8e_gu[x];
-        } else {
-            tg[x].w = sh ? L.rm_sg[x - c.n_real] : L.rm_eg[x];
-            tg[x].w2 = sh ? L.rm_su[x - c.n_real] : L.rm_eu[x];
+    for (int down = 0; down < 2; ++down) {
+        memset(tg, 0, sizeof(tg));
+        for (int x = 0; x < G; ++x) {
+            const umoe_group_t& src = gu_groups[down * G + x];
+            const int I = x >= c.n_real ? c.inter_shared : c.inter_dyn;
+            if (rm) {
+                tg[x].w = down ? H.dn[x] : H.gu[x];
+                tg[x].w2 = down ? nullptr : static_cast<const uint16_t*>(H.gu_aux[x]);
+            }
+            tg[x].rows = down ? nullptr : src.rows; tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
+            tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
+            tg[x].n = down ? D : I; tg[x].k = down ? I : D; tg[x].ldw = tg[x].k;
         }
-        tg[x].rows = src.rows; tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
-        tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
-        tg[x].n = sh ? c.inter_shared : c.inter_dyn; tg[x].k = D; tg[x].ldw = D;
+        umoe_tgemm_args ta{};
+        ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok;
+        ta.a = down ? e->hbuf : e->h2; ta.lda = down ? Imax : D; ta.out = down ? e->ybuf : e->hbuf; ta.ldo = down ? D : Imax;
+        ta.epilogue = down ? UMOE_EPI_BF16 : UMOE_EPI_SWIGLU;
+        if ((rc = tiled_launch(format, &ta, down ? H.dn.data() : H.gu.data(), rm ? nullptr : (down ? H.dn_aux.data() : H.gu_aux.data()), s))) return rc;
+        PROF(down ? K_DOWN : K_GATEUP);
     }
-    umoe_tgemm_args ta{};
-    ta.groups = tg; ta.num_groups = G; ta.max_rows = n_tok; ta.a = e->h2; ta.lda = D; ta.out = e->hbuf; ta.ldo = Imax;
-    ta.epilogue = UMOE_EPI_SWIGLU;
-    if ((rc = w12 ? umoe_tiled_gemm_w12(&ta, w8, wm, s) : f8 ? umoe_tiled_gemm_wp8(&ta, w8, ex, s) : umoe_tiled_gemm(&ta, s))) return rc;
-    PROF(K_GATEUP);
-    memset(tg, 0, sizeof(tg));
-    for (int x = 0; x < G; ++x) {
-        const umoe_group_t& src = gu_groups[G + x];
-        const bool sh = x >= c.n_real;
-        if (w12) {
-            w8[x] = reinterpret_cast<const uint8_t*>(L.w12_dn[x]); wm[x] = L.w12m_dn[x];
-        } else if (f8) {
-            w8[x] = reinterpret_cast<const uint8_t*>(L.f8_dn[x]); ex[x] = L.f8e_dn[x];
-        } else {
-            tg[x].w = sh ? L.rm_sd[x - c.n_real] : L.rm_ed[x];
-        }
-        tg[x].row_off = src.row_off; tg[x].count = src.count; tg[x].static_count = src.static_count;
-        tg[x].a_row_base = src.a_row_base; tg[x].out_row_base = src.out_row_base;
-        tg[x].n = D; tg[x].k = sh ? c.inter_shared : c.inter_dyn; tg[x].ldw = tg[x].k;
-    }
-    umoe_tgemm_args td{};
-    td.groups = tg; td.num_groups = G; td.max_rows = n_tok; td.a = e->hbuf; td.lda = Imax; td.out = e->ybuf; td.ldo = D;
-    td.epilogue = UMOE_EPI_BF16;
-    if ((rc = w12 ? umoe_tiled_gemm_w12(&td, w8, wm, s) : f8 ? umoe_tiled_gemm_wp8(&td, w8, ex, s) : umoe_tiled_gemm(&td, s))) return rc;
-    PROF(K_DOWN);
-    if (f8) e->prefill_fp8 = 1;
-    if (w12) e->prefill_w12 = 1;
+    if (format == UMOE_FMT_WP8) e->prefill_fp8 = 1;
+    if (format == UMOE_FMT_WP12) e->prefill_w12 = 1;
     return 0;
 }
 
@@ -1025,40 +1004,21 @@ static int wide_dense(umoe_engine* e, const uint16_t* a, int K, const uint16_t* 
     return 0;      // (the caller books the GEMM under its class)
 }
 
-// post-attention RMSNorm + re-lay, gate/up over all routed and shared experts, down: three launches, every expert computes every row
-static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_t s) {
+// post-attention RMSNorm + re-lay, gate/up over all routed and shared experts, down: three launches, every expert computes every row.
+// On the layer's WP8 blocks or WP12 copies: the same two launches (WP12: the same outputs bit for bit, 0.75 of the bytes)
+static int experts_wide(umoe_engine* e, const LayerDev& L, int format, int n_tok, hipStream_t s) {
     const umoe_engine_cfg& c = e->c;
     const int D = c.hidden, G = c.n_real + c.n_fix, Imax = c.inter_dyn > c.inter_shared ? c.inter_dyn : c.inter_shared;
     const int tiles = ceil_div(n_tok, 16);
+    const Holding& H = L.fmt[format];
     int rc;
     if ((rc = umoe_pack_rows(e->x1, D, n_tok, D, L.w.post_norm, c.rms_eps, e->wide_in, s))) return rc;
     PROF(K_DISPATCH);
-    const bool f8 = e->fp8;      // (wide_mode admitted the step: the switch is on and fp8_step_check saw every layer's WP8 weights)
-    UMOE_REQUIRE(!f8 || L.has_f8, "umoe_engine: fp8 expert weights: a layer has none (umoe_engine_set_layer_fp8)");
-    const uint16_t *wgu[12], *wdn[12], *bx[12], *bh[12];
-    const uint8_t *wgu8[12], *wdn8[12];
-    const int8_t *egu[12], *edn[12];
-    // the layer's WP12 copies ([routed, then shared], as umoe_engine_set_layer_w12 stored them): the same two launches, the same outputs
-    // bit for bit, 0.75 of the bytes.  A layer without copies (not packable) runs the WP16 launches
-    const bool w12 = !f8 && e->w12_wide && L.has_w12 && wide_w12_on();
-    UMOE_REQUIRE(w12 || L.exp_bf16 || f8, "umoe_engine: the wide form of a w12-only layer runs on its WP12 copies only, and " W12_ONLY_MISSING);
-    const uint8_t *wgu12[12], *wdn12[12];
-    const uint32_t *mgu[12], *mdn[12];
+    const uint16_t *bx[12], *bh[12];
     void *oh[12], *oy[12];
     int nb_gu[12], nb_dn[12], k_gu[12], k_dn[12];
     for (int x = 0; x < G; ++x) {
-        const bool sh = x >= c.n_real;
-        const int I = sh ? c.inter_shared : c.inter_dyn;
-        wgu[x] = sh ? L.sh_gu[x - c.n_real] : L.exp_gu[x];
-        wdn[x] = sh ? L.sh_dn[x - c.n_real] : L.exp_dn[x];
-        if (f8) {                // [routed, then shared], as umoe_engine_set_layer_fp8 stored them
-            wgu8[x] = reinterpret_cast<const uint8_t*>(L.f8_gu[x]); egu[x] = L.f8e_gu[x];
-            wdn8[x] = reinterpret_cast<const uint8_t*>(L.f8_dn[x]); edn[x] = L.f8e_dn[x];
-        }
-        if (w12) {
-            wgu12[x] = reinterpret_cast<const uint8_t*>(L.w12_gu[x]); mgu[x] = L.w12m_gu[x];
-            wdn12[x] = reinterpret_cast<const uint8_t*>(L.w12_dn[x]); mdn[x] = L.w12m_dn[x];
-        }
+        const int I = x >= c.n_real ? c.inter_shared : c.inter_dyn;
         bx[x] = e->wide_in;
         oh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;      // [tiles][16 * I] in operand order
         bh[x] = e->wide_h + (size_t)x * tiles * 16 * Imax;
@@ -1066,17 +1026,10 @@ static int experts_wide(umoe_engine* e, const LayerDev& L, int n_tok, hipStream_
         nb_gu[x] = 2 * I / 16; k_gu[x] = D;
         nb_dn[x] = D / 16; k_dn[x] = I;
     }
-    if (f8) rc = umoe_gemm_wide_fp8(wgu8, egu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, UMOE_EPI_SWIGLU, 8, 1, s);
-    else if (w12) rc = umoe_gemm_wide_w12(wgu12, mgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, UMOE_EPI_SWIGLU, 8, 1, s);
-    else rc = umoe_gemm_wide(wgu, nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, nullptr, nullptr, UMOE_EPI_SWIGLU, 8, 1, s);
-    if (rc) return rc;
+    if ((rc = wide_launch(format, H.gu.data(), H.gu_aux.data(), nb_gu, k_gu, G, n_tok, bx, oh, 0, 0, UMOE_EPI_SWIGLU, 1, s))) return rc;
     PROF(K_GATEUP);
-    if (f8) rc = umoe_gemm_wide_fp8(wdn8, edn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, UMOE_EPI_BF16, 8, 2, s);
-    else if (w12) rc = umoe_gemm_wide_w12(wdn12, mdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, UMOE_EPI_BF16, 8, 2, s);
-    else rc = umoe_gemm_wide(wdn, nb_dn, k_dn, G, n_tok, bh, oy, D, D, nullptr, nullptr, UMOE_EPI_BF16, 8, 2, s);
-    if (rc) return rc;
+    if ((rc = wide_launch(format, H.dn.data(), H.dn_aux.data(), nb_dn, k_dn, G, n_tok, bh, oy, D, D, UMOE_EPI_BF16, 2, s))) return rc;
     PROF(K_DOWN);
-    e->expert_w12 = w12 ? 1 : 0;
     return 0;
 }
 
@@ -1092,15 +1045,19 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     const bool adm = e->adm_row0 >= 0;       // admission prefill: cache rows [adm_row0, adm_row0 + adm_rows) only
     const size_t kv_l = ((size_t)l * c.rows + (adm ? e->adm_row0 : 0)) * c.kv_heads * c.Lmax * c.head_dim;
     int rc;
-    // 1. RMSNorm + QKV (+bias)                                   model.py:227, Qwen2_5_VLAttention q/k/v_proj
+    // the decision, again, from the POD of this pass: plan_pass refused the pass before anything was enqueued if any layer's answer is a refusal
+    umoe_plan_out plan;
+    char refusal[768] = "no plan_pass for this token count";
+    UMOE_REQUIRE(e->plan.n_tok == n_tok && umoe_plan_layer(e->plan, e->plan_facts, l, &plan, refusal, sizeof(refusal)) == 0,
+                 "umoe_engine: internal: layer %d enqueued in a pass that was not planned (%s)", l, refusal);
+    // 1. RMSNorm + QKV (+bias)                                  model.py:227, Qwen2_5_VLAttention q/k/v_proj
     umoe_gemm_args a{};
     a.groups = g; a.groups_host = gh; a.num_groups = 1; a.max_rows = n_tok; a.max_n_blocks = QKV / 16; a.max_k = D;
     a.a = e->hin; a.lda = D; a.out = e->qkv; a.ldo = QKV; a.n_valid = QKV;   // hin = RMSNorm(x) from the previous combine
     a.prologue = UMOE_PRO_PLAIN; a.epilogue = UMOE_EPI_BF16;
     PROF(-1);
     // many rows (prefill): the compute-bound tiled MFMA kernel on the row-major weights; decode: weight streaming
-    const bool wide = wide_mode(e, n_tok);
-    const bool tiled = !wide && (L.exp_bf16 ? L.has_rm : L.has_rm_attn) && n_tok >= 64 && e->tiled_prefill;     // (an fp8-only layer has no rm_exp_*)
+    const bool wide = plan.attn == UMOE_ATTN_WIDE, tiled = plan.attn == UMOE_ATTN_TILED;
     if (wide) {
         rc = wide_dense(e, e->hin, D, L.w.qkv_w, QKV / 16, L.w.qkv_b, nullptr, e->qkv, QKV, QKV, UMOE_EPI_BF16, 16, n_tok, s);
     } else if (tiled) {
@@ -1184,19 +1141,15 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     PROF(K_OPROJ);
     if (e->probe_x1 && n_tok == c.rows && !adm)
         UMOE_HIP(hipMemcpyAsync(e->probe_x1 + (size_t)l * c.rows * D, e->x1, (size_t)c.rows * D * 2, hipMemcpyDeviceToDevice, s));
-    if (e->ep_decode(n_tok)) return run_moe_ep(e, l, n_tok, s);
+    const int form = plan.form, format = plan.format;
+    if (form == MOE_EP) return run_moe_ep(e, l, n_tok, s);
     // 5.-8. RMSNorm + router, experts                             model.py:240, core.py:246-291,406-416,344-351
-    const MoeForm form = moe_form(e, L, n_tok);
     const bool dense = form == MOE_FLAT || form == MOE_RIDERS || form == MOE_ROUTER || form == MOE_WIDE;
+    const bool step = e->plan.kind == UMOE_PASS_DECODE;
     if (form != MOE_WIDE && n_tok == c.rows && n_tok > 16 && !adm) {     // a decode step the wide form did not take
         e->expert_launch = 0;
         e->row_tiles = 1;
     }
-    UMOE_REQUIRE(!(e->fp8 && dense && form != MOE_FLAT && form != MOE_WIDE), "umoe_engine: fp8 expert weights need the flat expert launch (layer %d)", l);
-    UMOE_REQUIRE(!L.w12_only() || form == MOE_TILED || form == MOE_FLAT || form == MOE_WIDE,
-                 "umoe_engine: layer %d: this pass would stream bf16 expert weights, and " W12_ONLY_MISSING, l);
-    UMOE_REQUIRE(L.exp_bf16 || L.w12_only() || (L.has_f8 && (form == MOE_TILED || form == MOE_FLAT || form == MOE_WIDE)),
-                 "umoe_engine: layer %d holds no bf16 expert weights (fp8-only) and this pass would stream them", l);
     umoe_router_args ra{};
     ra.x = e->x1; ra.gate_w = L.w.gate_w; ra.norm_w = L.w.post_norm; ra.h_out = e->h2; ra.S = n_tok; ra.D = D;
     ra.n_dyn = c.n_dyn; ra.n_real = c.n_real; ra.n_fix = c.n_fix; ra.logits_bf16 = 1; ra.top_p = c.top_p;
@@ -1219,12 +1172,12 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
     dn.max_k = Imax;
     dn.a = e->hbuf; dn.lda = Imax; dn.out = e->ybuf; dn.ldo = D; dn.n_valid = D;
     dn.prologue = UMOE_PRO_PLAIN; dn.epilogue = UMOE_EPI_BF16; dn.nt = dense ? 6 : 0;
-    if (e->in_decode_step) e->expert_w12 = 0;      // (a decode step's word: an admission prefill between two replays of the step graph leaves it)
+    if (step) e->expert_w12 = 0;      // (a decode step's word: an admission prefill between two replays of the step graph leaves it)
     switch (form) {
         case MOE_TILED:
             if ((rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s))) return rc;
             PROF(K_ROUTER);
-            if ((rc = experts_tiled(e, L, gh + 2, n_tok, s))) return rc;
+            if ((rc = experts_tiled(e, L, format, gh + 2, n_tok, s))) return rc;
             break;
         case MOE_RAGGED:
             if ((rc = umoe_router_dispatch_fwd(&ra, e->counts, e->offsets, e->slot_token, e->slot_of, s))) return rc;
@@ -1239,46 +1192,25 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             gu.fused_router = &ra;
             gu.rider_pub = &rpub;
             gu.groups_host = e->h_gu_pub.data() + (size_t)l * G;
-            const int n_wg = flat_wgs(e);
-            bool w12 = false;
-            if (e->fp8) {        // the same launch on the WP8 blocks -- and nothing else (no bf16 path streams these weights)
-                UMOE_REQUIRE(L.has_f8 && G <= UMOE_MAXE, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
-                umoe_group_t g8u[UMOE_MAXE], g8d[UMOE_MAXE];
-                const int8_t* e8u[UMOE_MAXE];
-                const int8_t* e8d[UMOE_MAXE];
-                for (int i = 0; i < G; ++i) {
-                    const int x = i < c.n_fix ? c.n_real + i : i - c.n_fix;     // gu groups: the shared experts first (h_gu_pub)
-                    g8u[i] = gu.groups_host[i]; g8u[i].w = L.f8_gu[x]; e8u[i] = L.f8e_gu[x];
-                    g8d[i] = dn.groups_host[i]; g8d[i].w = L.f8_dn[i]; e8d[i] = L.f8e_dn[i];
-                }
-                umoe_gemm_args gu8 = gu, dn8 = dn;
-                gu8.groups_host = g8u; dn8.groups_host = g8d;
-                rc = umoe_moe_flat_fp8(&gu8, &dn8, e8u, e8d, e->ep_words + 64, 512 - 64, n_wg, s);
-            } else {
-                rc = 1;
-                if (L.has_w12 && G <= UMOE_MAXE && flat_w12_on()) {      // the same launch on the WP12 copies: the same outputs, 0.75 of the bytes
-                    umoe_group_t g12u[UMOE_MAXE], g12d[UMOE_MAXE];
-                    const uint32_t* m12u[UMOE_MAXE];
-                    const uint32_t* m12d[UMOE_MAXE];
-                    for (int i = 0; i < G; ++i) {
-                        const int x = i < c.n_fix ? c.n_real + i : i - c.n_fix;     // gu groups: the shared experts first (h_gu_pub)
-                        g12u[i] = gu.groups_host[i]; g12u[i].w = L.w12_gu[x]; m12u[i] = L.w12m_gu[x];
-                        g12d[i] = dn.groups_host[i]; g12d[i].w = L.w12_dn[i]; m12d[i] = L.w12m_dn[i];
-                    }
-                    umoe_gemm_args gu12 = gu, dn12 = dn;
-                    gu12.groups_host = g12u; dn12.groups_host = g12d;
-                    rc = umoe_moe_flat_w12(&gu12, &dn12, m12u, m12d, e->ep_words + 64, 512 - 64, n_wg, s);
-                    w12 = rc == 0;
-                }
-                UMOE_REQUIRE(rc != 1 || L.exp_bf16, "umoe_engine: layer %d: the flat expert launch on the WP12 copies cannot run (UMOE_FLAT_W12, schedule), and "
-                                                    W12_ONLY_MISSING, l);
-                if (rc == 1) rc = umoe_moe_flat(&gu, &dn, e->ep_words + 64, 512 - 64, n_wg, s);      // (no WP12 copies, or no schedule at their byte cost)
+            // the same launch on the WP16 packs, the WP8 blocks or the WP12 copies (the same outputs as WP16, 0.75 of the bytes)
+            const Holding& H = L.fmt[format];
+            const int n_wg = umoe_plan_flat_wgs(e->plan);
+            UMOE_REQUIRE(G <= UMOE_MAXE, "umoe_engine: internal: the flat expert launch with %d groups", G);
+            umoe_group_t fgu[UMOE_MAXE], fdn[UMOE_MAXE];
+            const void *aux_gu[UMOE_MAXE], *aux_dn[UMOE_MAXE];
+            for (int i = 0; i < G; ++i) {
+                const int x = flat_gu_index(c, i);
+                fgu[i] = gu.groups_host[i]; fgu[i].w = H.gu[x]; aux_gu[i] = format == UMOE_FMT_WP16 ? nullptr : H.gu_aux[x];
+                fdn[i] = dn.groups_host[i]; fdn[i].w = H.dn[i]; aux_dn[i] = format == UMOE_FMT_WP16 ? nullptr : H.dn_aux[i];
             }
-            UMOE_REQUIRE(rc != 1, "umoe_engine: the %sflat expert launch has no schedule for this shape on %d workgroups (layer %d)", e->fp8 ? "fp8 " : "", n_wg, l);
+            gu.groups_host = fgu; dn.groups_host = fdn;
+            rc = flat_launch(format, &gu, &dn, aux_gu, aux_dn, e->ep_words + 64, 512 - 64, n_wg, s);
+            UMOE_REQUIRE(rc != 1, "umoe_engine: internal: the flat expert launch (weight format %d) has no schedule for this shape on %d workgroups although "
+                                  "the plan found one (layer %d)", format, n_wg, l);
             if (rc) return rc;
             e->expert_launch = 2;
-            e->expert_fp8 = e->fp8 ? 1 : 0;
-            e->expert_w12 = w12 ? 1 : 0;
+            e->expert_fp8 = format == UMOE_FMT_WP8;
+            e->expert_w12 = format == UMOE_FMT_WP12;
             PROF(K_GATEUP);      // (booked as gate/up: zero down launches tell the reader which form ran)
             break;
         }
@@ -1311,9 +1243,10 @@ static int run_layer(umoe_engine* e, int l, int n_tok, int T, int splits, hipStr
             ra.h_out = nullptr;      // (the experts read the operand-order tiles of the RMSNorm + re-lay launch)
             if ((rc = umoe_router_fwd(&ra, s))) return rc;      // all rows, no dispatch tables: the combine reads the mask
             PROF(K_ROUTER);
-            if ((rc = experts_wide(e, L, n_tok, s))) return rc;
+            if ((rc = experts_wide(e, L, format, n_tok, s))) return rc;
             e->expert_launch = 4;
-            e->expert_fp8 = e->fp8 ? 1 : 0;
+            e->expert_fp8 = format == UMOE_FMT_WP8;
+            e->expert_w12 = format == UMOE_FMT_WP12;
             e->row_tiles = ceil_div(n_tok, 16);
             break;
     }
@@ -1393,10 +1326,6 @@ static int prefill_state(umoe_engine* e, const uint8_t* valid_host, int T, const
     return 0;
 }
 
-static int fp8_step_check(umoe_engine* e);
-static int fp8_only_check(umoe_engine* e, int prefill_tok);
-static int w12_only_check(umoe_engine* e, int prefill_tok);
-
 extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const uint8_t* valid_host, int T, const int32_t* pos3_host,
                                        const int32_t* next_pos_host, umoe_stream_t stream) {
     UMOE_REQUIRE(e && x && valid_host && T > 0, "umoe_engine_prefill: bad argument");
@@ -1406,19 +1335,16 @@ extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const 
     UMOE_REQUIRE(c.ep_size == 1 || e->ep_mode >= 0, "umoe_engine_prefill: expert parallel engine is not connected (umoe_engine_ep_connect)");
     UMOE_REQUIRE(c.ep_size == 1 || (c.rows * T >= 64 && e->tiled_prefill), "umoe_engine_prefill: expert parallel prefill runs replicated on the tiled path: needs rows*T >= 64 (got %d)", c.rows * T);
     for (int l = 0; l < c.layers && c.ep_size > 1; ++l)
-        UMOE_REQUIRE(e->layers[l].has_rm, "umoe_engine_prefill: this expert parallel engine holds its LOCAL experts only (no row-major tensors of the others): "
+        UMOE_REQUIRE(e->layers[l].has_rm_attn && e->layers[l].fmt[UMOE_FMT_RM].has, "umoe_engine_prefill: this expert parallel engine holds its LOCAL experts only (no row-major tensors of the others): "
                                           "prefill outside the engine and hand the KV cache over (umoe_engine_prefill_external)");
     hipStream_t s = (hipStream_t)stream;
     const int n_tok = c.rows * T;
     int rc;
-    // a one-token prompt takes the dense decode layout, i.e. the fp8 flat launch on an fp8 engine: refused up front like a decode step
-    if (e->fp8 && dense_mode(e, n_tok) && (rc = fp8_step_check(e))) return rc;
-    if ((rc = fp8_only_check(e, dense_mode(e, n_tok) ? 0 : n_tok))) return rc;
-    if ((rc = w12_only_check(e, dense_mode(e, n_tok) ? 0 : n_tok))) return rc;
+    if ((rc = plan_pass(e, UMOE_PASS_PREFILL, n_tok))) return rc;
     e->prefill_fp8 = 0;
     e->prefill_w12 = 0;
     if ((rc = ensure_workspace(e, n_tok))) return rc;
-    if ((rc = build_groups(e, n_tok, s))) return rc;
+    if ((rc = build_groups(e, UMOE_PASS_PREFILL, n_tok, s))) return rc;
     if ((rc = prefill_state(e, valid_host, T, pos3_host, next_pos_host, s))) return rc;
     UMOE_HIP(hipMemcpyAsync(e->x, x, (size_t)n_tok * c.hidden * 2, hipMemcpyDeviceToDevice, s));
     if ((rc = umoe_rmsnorm_residual_fwd(e->x, nullptr, e->layers[0].w.in_norm, c.rms_eps, n_tok, c.hidden, nullptr, e->hin, s)))
@@ -1430,7 +1356,7 @@ extern "C" int umoe_engine_prefill_pos(umoe_engine* e, const uint16_t* x, const 
         if ((rc = run_layer(e, l, n_tok, T, 1, s))) return rc;
     e->T_prompt = T;
     // switch the group table to decode shape now, outside any later graph capture
-    if ((rc = build_groups(e, c.rows, s))) return rc;
+    if ((rc = build_groups(e, UMOE_PASS_DECODE, c.rows, s))) return rc;
     return 0;
 }
 
@@ -1450,7 +1376,7 @@ extern "C" int umoe_engine_prefill_external(umoe_engine* e, const uint8_t* valid
     if ((rc = prefill_state(e, valid_host, T, pos3_host, next_pos_host, s))) return rc;
     e->cb_pending = false;
     e->T_prompt = T;
-    if ((rc = build_groups(e, c.rows, s))) return rc;
+    if ((rc = build_groups(e, UMOE_PASS_DECODE, c.rows, s))) return rc;
     return 0;
 }
 
@@ -1491,11 +1417,6 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     const umoe_engine_cfg& c = e->c;
     const int B = c.rows / 2, C = c.codec_channels, V = c.codec_vocab;
     int rc;
-    struct StepFlag {
-        bool& f;
-        explicit StepFlag(bool& b) : f(b) { f = true; }
-        ~StepFlag() { f = false; }
-    } in_step(e->in_decode_step);
     PROF(-1);
     step_prep_kernel<<<dim3((unsigned)c.rows), 64, 0, s>>>(io->tokens, io->state, B, C, c.Tmax, e->T_prompt, c.Lmax,
                                                            e->valid_count, e->tok_in, e->pos3, e->kv_pos, e->q_pos0, e->ep_words,
@@ -1524,7 +1445,7 @@ static int enqueue_step(umoe_engine* e, const umoe_decode_io* io, hipStream_t s)
     h.max_n_blocks = ceil_div(C * V, 16); h.max_k = c.hidden; h.a = e->hin; h.lda = c.hidden;   // hin = final norm(x)
     h.out = e->logits; h.ldo = C * V; h.n_valid = C * V;
     h.prologue = UMOE_PRO_PLAIN; h.epilogue = UMOE_EPI_F32;
-    if (wide_mode(e, c.rows)) {
+    if (umoe_plan_wide(e->plan, e->plan_facts)) {
         // the K split the 16-row head launch takes (auto_nt / launch_gemm_nt in umoe_gemm.hip at hidden 2048: blocks per workgroup 8 / 2 / 1)
         const int nb = ceil_div(C * V, 16), u = nb >= 1024 ? 2 : (nb >= 512 ? 8 : 16);
         if ((rc = wide_dense(e, e->hin, c.hidden, e->codec_head_w, nb, nullptr, nullptr, e->logits, C * V, C * V, UMOE_EPI_F32, u, c.rows, s))) return rc;
@@ -1577,7 +1498,7 @@ extern "C" int umoe_engine_reserve(umoe_engine* e, int n_tok) {
         UMOE_HIP(hipMemset(e->adm_q0, 0, 4 * sizeof(int32_t)));
     }
     e->cb_pending = false;
-    if ((rc = build_groups(e, e->c.rows, nullptr))) return rc;
+    if ((rc = build_groups(e, UMOE_PASS_DECODE, e->c.rows, nullptr))) return rc;
     e->reserved_tok = e->cap_tok;
     return 0;
 }
@@ -1649,8 +1570,7 @@ extern "C" int umoe_engine_admit(umoe_engine* e, const umoe_decode_io* io, int b
     UMOE_REQUIRE(x, "umoe_engine_admit: null prompt");
     hipStream_t s = (hipStream_t)stream;
     const int n_tok = 2 * T;
-    if ((rc = fp8_only_check(e, n_tok))) return rc;       // (an admission prefill is never the dense layout)
-    if ((rc = w12_only_check(e, n_tok))) return rc;
+    if ((rc = plan_pass(e, UMOE_PASS_ADMISSION, n_tok))) return rc;
     e->prefill_fp8 = 0;
     e->prefill_w12 = 0;
     // positions cumsum(mask) - 1, masked -> 1; kv slot = t (prefill_state, for the pair)
@@ -1740,7 +1660,7 @@ static int admission_pass(umoe_engine* e, int row0, int n_rows, int T, const uin
     e->adm_rows = n_rows;
     e->adm_q = q0_host ? e->adm_q0 + 2 : e->adm_q0;
     e->groups_for_tok = -1;              // (a table of the same token count in decode shape is not this pass's table)
-    int rc = build_groups(e, n_tok, s);
+    int rc = build_groups(e, UMOE_PASS_ADMISSION, n_tok, s);
     if (!rc) {
         rc = [&]() -> int {
             UMOE_HIP(hipMemcpyAsync(e->pos3, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
@@ -1763,7 +1683,7 @@ static int admission_pass(umoe_engine* e, int row0, int n_rows, int T, const uin
     e->adm_q = nullptr;
     e->cb_pending = false;
     e->groups_for_tok = -1;
-    const int rg = build_groups(e, c.rows, s);      // back to decode shape (synchronises: the host vectors stay alive until here)
+    const int rg = build_groups(e, UMOE_PASS_DECODE, c.rows, s);      // back to decode shape (synchronises: the host vectors stay alive until here)
     return rc ? rc : rg;
 }
 
@@ -1784,8 +1704,7 @@ extern "C" int umoe_engine_prefix_build(umoe_engine* e, const umoe_decode_io* io
     UMOE_REQUIRE(c.head_dim % 8 == 0, "%s: head_dim %d is no multiple of 8", who, c.head_dim);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if ((rc = fp8_only_check(e, P))) return rc;       // (an admission pass is never the dense layout)
-    if ((rc = w12_only_check(e, P))) return rc;
+    if ((rc = plan_pass(e, UMOE_PASS_ADMISSION, P))) return rc;
     e->prefill_fp8 = 0;
     e->prefill_w12 = 0;
     std::vector<int32_t> pos((size_t)3 * P), kvp(P);
@@ -1812,8 +1731,7 @@ extern "C" int umoe_engine_admit_prefix(umoe_engine* e, const umoe_decode_io* io
     UMOE_REQUIRE(c.head_dim % 8 == 0, "%s: head_dim %d is no multiple of 8", who, c.head_dim);
     hipStream_t s = (hipStream_t)stream;
     const int Tq = T - P, n_tok = 2 * Tq;
-    if ((rc = fp8_only_check(e, n_tok))) return rc;
-    if ((rc = w12_only_check(e, n_tok))) return rc;
+    if ((rc = plan_pass(e, UMOE_PASS_ADMISSION, n_tok))) return rc;
     e->prefill_fp8 = 0;
     e->prefill_w12 = 0;
     // positions of columns [P, T) from the FULL mask: cumsum(mask) - 1, masked -> 1; kv slot = the column
@@ -1838,130 +1756,11 @@ extern "C" int umoe_engine_admit_prefix(umoe_engine* e, const umoe_decode_io* io
     return admit_state(e, io, b, T, prefill_step, prefix_len, start, vc, s);
 }
 
-// An fp8 engine enqueues a decode step only when every dense decode layer will take the fp8 flat launch (moe_form: MOE_FLAT) or, with the
-// switch umoe_engine_set_fp8_wide, the wide form on the WP8 weights (17..64 rows): the launch-per-kernel forms would stream bf16 expert
-// weights it does not run on.  Checked on the host before anything is enqueued.
-// An engine with fp8-only layers (umoe_engine_set_layer without any bf16 expert weight) holds its experts as WP8 blocks and nothing else:
-// every pass that would stream a bf16 expert weight is refused HERE, on the host, before anything is enqueued, with a message that names
-// the missing weights.  prefill_tok > 0: a prefill / admission of that many tokens outside the dense layout (MOE_TILED on the WP8 blocks,
-// umoe_tiled_gemm_wp8, at every row count -- MOE_RAGGED streams WP16); 0: a pass in the dense decode layout (fp8_step_check's rules, with
-// the launch-per-kernel forms MOE_RIDERS / MOE_ROUTER and the bf16 wide form named as what they are here).
-#define FP8_ONLY_MISSING "this engine holds no bf16 expert weights (fp8-only: exp_gu / exp_dn / sh_gu / sh_dn and rm_exp_* / rm_sh_* were not given)"
-static bool fp8_only(const umoe_engine* e) {
-    for (const LayerDev& L : e->layers)
-        if (L.set && !L.exp_bf16 && !L.w12_only()) return true;
-    return false;
-}
-static int fp8_only_check(umoe_engine* e, int prefill_tok) {
-    if (!fp8_only(e)) return 0;
-    const umoe_engine_cfg& c = e->c;
-    UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: " FP8_ONLY_MISSING ": not supported expert parallel (ep_size %d)", c.ep_size);
-    for (int l = 0; l < c.layers; ++l)
-        UMOE_REQUIRE(!e->layers[l].set || e->layers[l].exp_bf16 || e->layers[l].has_f8,
-                     "umoe_engine: layer %d has no expert weights at all: " FP8_ONLY_MISSING " and umoe_engine_set_layer_fp8 was not called", l);
-    if (prefill_tok > 0) {
-        UMOE_REQUIRE(e->tiled_prefill, "umoe_engine: UMOE_TILED_PREFILL=0 runs the experts of a prefill on the weight-streaming GEMM (MOE_RAGGED) over WP16 packs, and "
-                                       FP8_ONLY_MISSING);
-        UMOE_REQUIRE(c.n_real + c.n_fix <= 12, "umoe_engine: a prefill of %d experts per layer takes MOE_RAGGED over WP16 packs (the tiled launch has 12 groups), and "
-                                               FP8_ONLY_MISSING, c.n_real + c.n_fix);
-        UMOE_REQUIRE(c.hidden % 32 == 0 && c.inter_dyn % 32 == 0 && (c.n_fix == 0 || c.inter_shared % 32 == 0),
-                     "umoe_engine: the tiled GEMM on WP8 weights needs hidden and intermediate sizes that are multiples of 32 (%d, %d, %d), and " FP8_ONLY_MISSING,
-                     c.hidden, c.inter_dyn, c.inter_shared);
-        return 0;
-    }
-    if (e->fp8_wide && fp8_wide_on() && wide_shapes(e, c.rows)) return 0;      // the wide form on the WP8 weights
-    UMOE_REQUIRE(!wide_shapes(e, c.rows), "umoe_engine: a decode step of %d rows without the fp8 wide form (umoe_engine_set_fp8_wide, UMOE_WIDE_DECODE) takes the bf16 "
-                                          "wide form or MOE_RAGGED, and " FP8_ONLY_MISSING, c.rows);
-    UMOE_REQUIRE(flat_moe_on(), "umoe_engine: UMOE_FLAT_MOE=0 selects the launch-per-kernel forms (MOE_RIDERS / MOE_ROUTER) over WP16 packs, and " FP8_ONLY_MISSING);
-    UMOE_REQUIRE(e->fuse_router, "umoe_engine: UMOE_FUSE_ROUTER=0 selects the launch-per-kernel form MOE_ROUTER over WP16 packs, and " FP8_ONLY_MISSING);
-    UMOE_REQUIRE(dense_mode(e, c.rows), "umoe_engine: a decode step of %d rows outside the dense layout takes MOE_RAGGED over WP16 packs, and " FP8_ONLY_MISSING, c.rows);
-    return 0;
-}
-
-// The same for w12-only layers (umoe_engine_set_layer without any bf16 expert weight, then umoe_engine_set_layer_w12): their experts are
-// the WP12 copies and nothing else.  A prefill / admission of any row count runs them MOE_TILED on umoe_tiled_gemm_w12; a decode step is
-// the WP12 flat launch up to 16 rows and the WP12 wide form at EVERY row count 17..64.  Whatever would stream a bf16 expert weight of
-// such a layer is refused here, before anything is enqueued.  Layers may be mixed: a layer that was not packable keeps its bf16 weights
-// and its paths; the passes and switches below reach every layer, so one w12-only layer is enough to refuse them.
-static bool flat_w12_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix) {
-    static int key[7] = {-1, -1, -1, -1, -1, -1, -1};
-    static bool ans = false;
-    const int k[7] = {n_wg, S, D, I_dyn, I_sh, n_real, n_fix};
-    if (memcmp(k, key, sizeof(k)) == 0) return ans;      // (asked before every step: a plan search costs the host milliseconds)
-    bool ok = false;
-    if (n_wg >= 1 && n_wg <= 256) {
-        std::vector<double> out(3 + 9 * (size_t)n_wg);
-        ok = umoe_moe_flat_plan_w12_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out.data(), (int)out.size()) == 0 && out[0] != 0.0;
-    }
-    memcpy(key, k, sizeof(k));
-    ans = ok;
-    return ans;
-}
-static int w12_only_check(umoe_engine* e, int prefill_tok) {
-    if (!w12_only_layers(e)) return 0;
-    const umoe_engine_cfg& c = e->c;
-    UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: " W12_ONLY_MISSING ": not supported expert parallel (ep_size %d)", c.ep_size);
-    if (prefill_tok > 0) {
-        UMOE_REQUIRE(e->tiled_prefill, "umoe_engine: UMOE_TILED_PREFILL=0 runs the experts of a prefill on the weight-streaming GEMM (MOE_RAGGED) over WP16 packs, and "
-                                       W12_ONLY_MISSING);
-        UMOE_REQUIRE(c.n_real + c.n_fix <= 12, "umoe_engine: a prefill of %d experts per layer takes MOE_RAGGED over WP16 packs (the tiled launch has 12 groups), and "
-                                               W12_ONLY_MISSING, c.n_real + c.n_fix);
-        UMOE_REQUIRE(c.hidden % 32 == 0 && c.inter_dyn % 32 == 0 && (c.n_fix == 0 || c.inter_shared % 32 == 0) && c.hidden / 32 < 127 && c.inter_dyn / 32 < 127 &&
-                         c.inter_shared / 32 < 127,
-                     "umoe_engine: the tiled GEMM on WP12 weights needs hidden and intermediate sizes that are multiples of 32 below 4064 (%d, %d, %d), and "
-                     W12_ONLY_MISSING, c.hidden, c.inter_dyn, c.inter_shared);
-        return 0;
-    }
-    if (wide_shapes(e, c.rows)) {      // 17..64 rows: the wide form on the WP12 copies, at every size
-        UMOE_REQUIRE(fp8_wide_on(), "umoe_engine: UMOE_WIDE_DECODE=0 sends a decode step of %d rows to MOE_RAGGED over WP16 packs, and " W12_ONLY_MISSING, c.rows);
-        UMOE_REQUIRE(e->w12_wide && wide_w12_on(), "umoe_engine: UMOE_WIDE_W12=0 (or umoe_engine_set_w12_wide off) runs the wide form of %d rows on the WP16 packs, and "
-                                                   W12_ONLY_MISSING, c.rows);
-        return 0;
-    }
-    UMOE_REQUIRE(dense_mode(e, c.rows), "umoe_engine: a decode step of %d rows outside the dense layout takes MOE_RAGGED over WP16 packs, and " W12_ONLY_MISSING, c.rows);
-    UMOE_REQUIRE(flat_moe_on(), "umoe_engine: UMOE_FLAT_MOE=0 selects the launch-per-kernel forms (MOE_RIDERS / MOE_ROUTER) over WP16 packs, and " W12_ONLY_MISSING);
-    UMOE_REQUIRE(e->fuse_router, "umoe_engine: UMOE_FUSE_ROUTER=0 selects the launch-per-kernel form MOE_ROUTER over WP16 packs, and " W12_ONLY_MISSING);
-    UMOE_REQUIRE(flat_w12_on(), "umoe_engine: UMOE_FLAT_W12=0 runs the flat expert launch on the WP16 packs, and " W12_ONLY_MISSING);
-    UMOE_REQUIRE(c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096) && c.n_real + c.n_fix <= UMOE_MAXE,
-                 "umoe_engine: this shape selects the launch-per-kernel form MOE_ROUTER over WP16 packs (the flat expert launch is written for 9 + 2 experts at "
-                 "hidden 2048 / 4096), and " W12_ONLY_MISSING);
-    const int n_wg = flat_wgs(e);
-    UMOE_REQUIRE(n_wg > 0 && umoe_moe_flat_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix) &&
-                     flat_w12_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix),
-                 "umoe_engine: the flat expert launch on the WP12 copies has no schedule on %d compute units (MOE_RIDERS would stream WP16 packs), and " W12_ONLY_MISSING,
-                 e->n_cu);
-    return 0;
-}
-
-static int fp8_step_check(umoe_engine* e) {
-    if (int rc = fp8_only_check(e, 0)) return rc;
-    if (int rc = w12_only_check(e, 0)) return rc;
-    if (!e->fp8) return 0;
-    const umoe_engine_cfg& c = e->c;
-    UMOE_REQUIRE(c.ep_size == 1, "umoe_engine: fp8 expert weights are not supported expert parallel (ep_size %d)", c.ep_size);
-    if (e->fp8_wide && fp8_wide_on() && wide_shapes(e, c.rows)) {      // the step wide_mode will admit
-        for (int l = 0; l < c.layers; ++l)
-            UMOE_REQUIRE(e->layers[l].has_f8, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
-        return 0;
-    }
-    UMOE_REQUIRE(flat_moe_on(), "umoe_engine: fp8 expert weights need the flat expert launch (UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 is the bf16 launch-per-kernel form)");
-    UMOE_REQUIRE(e->fuse_router, "umoe_engine: fp8 expert weights need the flat expert launch with its router riders (UMOE_FUSE_ROUTER=0 selects a bf16 path)");
-    UMOE_REQUIRE(dense_mode(e, c.rows) && c.n_dyn == 9 && c.n_fix == 2 && (c.hidden == 2048 || c.hidden == 4096),
-                 "umoe_engine: fp8 expert weights need the dense decode layout of the flat expert launch (rows %d)", c.rows);
-    const int n_wg = flat_wgs(e);
-    UMOE_REQUIRE(n_wg > 0 && umoe_moe_flat_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix) &&
-                     umoe_moe_flat_fp8_feasible(n_wg, c.rows, c.hidden, c.inter_dyn, c.inter_shared, c.n_real, c.n_fix),
-                 "umoe_engine: fp8 expert weights: the flat expert launch has no schedule on %d compute units", e->n_cu);
-    for (int l = 0; l < c.layers; ++l)
-        UMOE_REQUIRE(e->layers[l].has_f8, "umoe_engine: fp8 expert weights: layer %d has none (umoe_engine_set_layer_fp8)", l);
-    return 0;
-}
-
 extern "C" int umoe_engine_decode_step(umoe_engine* e, const umoe_decode_io* io, umoe_stream_t stream) {
     UMOE_REQUIRE(e && io && io->tokens && io->state, "umoe_engine_decode_step: null argument");
     UMOE_REQUIRE(e->T_prompt > 0 || (io->row_clock && e->reserved_tok > 0), "umoe_engine_decode_step: prefill first");
     UMOE_REQUIRE(!io->row_clock || e->c.ep_size == 1, "umoe_engine_decode_step: per-row clocks are not supported expert parallel");
-    if (int rc = fp8_step_check(e)) return rc;
+    if (int rc = plan_pass(e, UMOE_PASS_DECODE, e->c.rows)) return rc;
     return enqueue_step(e, io, (hipStream_t)stream);
 }
 
@@ -1971,7 +1770,7 @@ extern "C" int umoe_engine_profile_step(umoe_engine* e, const umoe_decode_io* io
                                         int* launches, int n) {
     UMOE_REQUIRE(e && io && ms && launches && n >= K_NUM, "umoe_engine_profile_step: need %d output slots", K_NUM);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = fp8_step_check(e)) return rc;
+    if (int rc = plan_pass(e, UMOE_PASS_DECODE, e->c.rows)) return rc;
     e->prof = true;
     e->ev_used = 0;
     const int rc = enqueue_step(e, io, s);
@@ -1994,7 +1793,7 @@ extern "C" int umoe_engine_capture(umoe_engine* e, const umoe_decode_io* io, umo
     UMOE_REQUIRE(e->T_prompt > 0 || (io->row_clock && e->reserved_tok > 0), "umoe_engine_capture: prefill first");
     UMOE_REQUIRE(!io->row_clock || e->c.ep_size == 1, "umoe_engine_capture: per-row clocks are not supported expert parallel");
     UMOE_REQUIRE(!e->probe_on(), "umoe_engine_capture: the per-layer probe works on eager steps only (umoe_engine_set_probe)");
-    if (int rc = fp8_step_check(e)) return rc;
+    if (int rc = plan_pass(e, UMOE_PASS_DECODE, e->c.rows)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (e->exec) { (void)hipGraphExecDestroy(e->exec); e->exec = nullptr; }
     if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
@@ -2023,13 +1822,16 @@ extern "C" int umoe_engine_info(umoe_engine* e, const char* key) {
     if (!strcmp(key, "expert_w12")) return e->expert_w12;
     if (!strcmp(key, "prefill_fp8")) return e->prefill_fp8;
     if (!strcmp(key, "prefill_w12")) return e->prefill_w12;
-    if (!strcmp(key, "w12_only_layers")) return w12_only_layers(e);
-    if (!strcmp(key, "expert_bf16_resident")) {      // (a mixed engine -- w12-only layers next to layers that kept their bf16 weights -- still holds some)
-        if (fp8_only(e)) return 0;
-        for (const LayerDev& L : e->layers)
-            if (L.set && L.exp_bf16) return 1;
-        return w12_only_layers(e) ? 0 : 1;
+    int n_w12_only = 0, n_bf16 = 0, n_other = 0;      // layers that hold the WP12 copies only / bf16 expert weights / neither (fp8-only)
+    for (const LayerDev& L : e->layers) {
+        const uint8_t h = L.holds();
+        if (plan_w12_only(h)) ++n_w12_only;
+        else if (h & UMOE_HOLD_BF16) ++n_bf16;
+        else if (h & UMOE_HOLD_SET) ++n_other;
     }
+    if (!strcmp(key, "w12_only_layers")) return n_w12_only;
+    // (a mixed engine -- w12-only layers next to layers that kept their bf16 weights -- still holds some)
+    if (!strcmp(key, "expert_bf16_resident")) return n_other ? 0 : n_bf16 ? 1 : n_w12_only ? 0 : 1;
     if (!strcmp(key, "n_cu")) return e->n_cu;
     return -1;
 }

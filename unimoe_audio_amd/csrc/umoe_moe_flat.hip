@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "umoe_common.h"
+#include "umoe_engine_plan.h"
 #include "umoe_router_dev.h"
 
 #include "umoe_flat_dev.h"
@@ -282,7 +283,6 @@ static void flat_plan(const FlatShape& sh, FlatPlan& out) {
     if (best.ok) out = best;
 }
 
-extern "C" int umoe_moe_flat_plan_probe(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix, double* out, int out_len);
 static unsigned long long* g_flat_dbg = nullptr;
 // diagnostics: copy the stamps of the last stamped launch to the host ([256][16] u64); -1 when none was taken
 extern "C" int umoe_moe_flat_stamps(unsigned long long* host_out) {
@@ -422,7 +422,8 @@ int umoe_moe_flat_fp8(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const 
 }
 
 // The same launch on WP12 weights: the groups' `w` are WP12 blocks (unimoe_audio_amd/w12.py), m_gu / m_dn their block records in the
-// same group order.  Returns 1 like umoe_moe_flat when no schedule exists (the caller then runs the bf16 launch: the same outputs).
+// same group order.  Returns 1 like umoe_moe_flat when no schedule exists (umoe_flat_feasible answers that beforehand: the engine then plans
+// the WP16 launch for the layer, the same outputs).
 int umoe_moe_flat_w12(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const uint32_t* const* m_gu, const uint32_t* const* m_dn, uint32_t* flags,
                       int flag_words, int n_wg, hipStream_t s) {
     UMOE_REQUIRE(m_gu && m_dn && gu && dn && gu->num_groups <= FLAT_MAXG, "umoe_moe_flat_w12: bad argument");
@@ -434,20 +435,6 @@ int umoe_moe_flat_w12(const umoe_gemm_args* gu, const umoe_gemm_args* dn, const 
         W.m_gu[i] = m_gu[i]; W.m_dn[i] = m_dn[i];
     }
     return moe_flat_launch(gu, dn, flags, flag_words, n_wg, s, nullptr, &W);
-}
-
-// Does a schedule exist for this decode shape on n_wg workgroups?  (the engine asks before it drops the RMSNorm launch)
-bool umoe_moe_flat_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix) {
-    static int key[7] = {-1, -1, -1, -1, -1, -1, -1};
-    static bool ans = false;
-    const int k[7] = {n_wg, S, D, I_dyn, I_sh, n_real, n_fix};
-    if (memcmp(k, key, sizeof(k)) == 0) return ans;
-    std::vector<double> out(3 + 9 * (size_t)std::max(n_wg, 1));
-    const int rc = (n_wg >= 1 && n_wg <= FLAT_MAXWG && I_dyn % 32 == 0 && I_sh % 32 == 0 && I_dyn / 16 >= 2 * FLAT_NP_MAX && I_sh / 16 >= 2 * FLAT_NP_MAX && D / 16 <= 255)
-                       ? umoe_moe_flat_plan_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out.data(), (int)out.size()) : -1;
-    memcpy(key, k, sizeof(k));
-    ans = rc == 0 && out[0] != 0.0;
-    return ans;
 }
 
 // test hook (tests/test_abi_cpu.py, no GPU needed): the plan for a decode shape on `n_wg` workgroups (group order of the engine's
@@ -493,22 +480,23 @@ extern "C" int umoe_moe_flat_plan_fp8_probe(int n_wg, int S, int D, int I_dyn, i
     return flat_plan_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out, out_len, 1);
 }
 
-// Does an fp8 schedule exist for this decode shape on n_wg workgroups?  (the fp8 engine refuses to enqueue a step otherwise)
-// (asked before every fp8 decode step: the answer is kept for the last shape, like umoe_moe_flat_feasible's -- a plan search per eager
-// step would cost the host several milliseconds)
-bool umoe_moe_flat_fp8_feasible(int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix) {
-    static int key[7] = {-1, -1, -1, -1, -1, -1, -1};
-    static bool ans = false;
+// Does a schedule exist for this decode shape on n_wg workgroups, streamed in `format` (0 WP16, 1 WP8, 2 WP12: FlatShape.fp8)?  The
+// engine's decision (umoe_engine_plan.h) asks before every layer of every step, eager steps included, so the answer is kept per format
+// for the last shape: a plan search costs the host milliseconds.  The conditions in front are moe_flat_launch's on the groups.
+bool umoe_flat_feasible(int format, int n_wg, int S, int D, int I_dyn, int I_sh, int n_real, int n_fix) {
+    static int key[3][7] = {{-1}, {-1}, {-1}};
+    static bool ans[3] = {false, false, false};
+    if (format < 0 || format > 2) return false;
     const int k[7] = {n_wg, S, D, I_dyn, I_sh, n_real, n_fix};
-    if (memcmp(k, key, sizeof(k)) == 0) return ans;
+    if (memcmp(k, key[format], sizeof(k)) == 0) return ans[format];
     bool ok = false;
     if (n_wg >= 1 && n_wg <= FLAT_MAXWG && I_dyn % 32 == 0 && I_sh % 32 == 0 && I_dyn / 16 >= 2 * FLAT_NP_MAX && I_sh / 16 >= 2 * FLAT_NP_MAX && D / 16 <= 255) {
         std::vector<double> out(3 + 9 * (size_t)n_wg);
-        ok = flat_plan_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out.data(), (int)out.size(), 1) == 0 && out[0] != 0.0;
+        ok = flat_plan_probe(n_wg, S, D, I_dyn, I_sh, n_real, n_fix, out.data(), (int)out.size(), format) == 0 && out[0] != 0.0;
     }
-    memcpy(key, k, sizeof(k));
-    ans = ok;
-    return ans;
+    memcpy(key[format], k, sizeof(k));
+    ans[format] = ok;
+    return ok;
 }
 
 // test hook (tests/test_gpu_fp8.py): the kernel's own conversion path (flat_f8_frag / flat_f8_scale) over a row-major e4m3 matrix q [N][K]
