@@ -1,7 +1,8 @@
 """CLI mirror of the reference's examples/inference.py (flags --task/-t --input/-i --ref-audio/-ra --ref-text/-rt
 --video/-v --output/-o --model/-m --device/-d --no-reuse; exit code 0/1, reference examples/inference.py:152-235).
 --requests FILE.json (not in the reference): speech and music requests with their own settings in ONE decode batch; with --serve the
-list is a queue served by --slots rows, each request admitted as soon as a row is free."""
+list is a queue served by --slots rows, each request admitted as soon as a row is free; --serve --stream prints every request's
+chunks as they arrive and writes the same wav files."""
 import argparse
 import json
 import os
@@ -60,6 +61,13 @@ def batch_inference(requests_file, model_path, output="./output", device=0, reus
             # continuous batching: `slots` rows decode together, a request takes a row as soon as one is free
             import time
             t0, paths = time.perf_counter(), {}
+            kw = dict(slots=slots, output_dir=output, max_audio_seconds=max(r.max_audio_seconds for r in reqs), prefix_cache=prefix_cache)
+            if stream:
+                # every request's audio in chunks as its frames become final, chunks of different requests interleaved
+                for ch in _MODEL.serve(reqs, stream=True, **kw):
+                    print(f"{time.perf_counter() - t0:8.3f} s  request {ch.row}  samples {ch.start_sample}..{ch.start_sample + ch.pcm.numel()}"
+                          f"{'  (last)' if ch.final else ''}", flush=True)
+                return [os.path.join(output, f"generated_{r.save_name}_{i}.wav") for i, r in enumerate(reqs)]
             for i, path in _MODEL.serve(reqs, slots=slots, output_dir=output, max_audio_seconds=max(r.max_audio_seconds for r in reqs),
                                         prefix_cache=prefix_cache):
                 hit, n = _MODEL.served_prefix.get(i, (False, 0))
@@ -126,8 +134,6 @@ def main():
                                                                 "prefilled voice prompt; each admission prefills only its sentence")
     a = ap.parse_args()
     if a.requests:
-        if a.serve and a.stream:
-            ap.error("--serve does not stream chunks")
         if a.prefix_cache and not a.serve:
             ap.error("--prefix-cache goes with --serve")
         out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream, a.serve, a.slots, a.prefix_cache)

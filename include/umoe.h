@@ -747,6 +747,41 @@ int umoe_dac_conv1d_win(const float* x, int x_off, int Lx, const float* w, const
 int umoe_dac_conv_transpose1d_win(const float* x, int x_off, int Lx, const float* w, const float* bias, const float* snake_alpha, int B,
                                   int Cin, int L, int Cout, int K, int stride, int pad, int out_pad, int t_begin, int n, float* y, int y_off,
                                   int Ly, umoe_stream_t stream);
+/* Per-row window tables (the per-row streaming decoder of dac.py: one launch per layer for rows that are each on a timeline of their
+ * own).  A table is a flat array of int64 words, a fixed number per row, built by the host (unimoe_audio_amd.dac.DAC_ROW_FIELDS and its
+ * siblings name the words in this order); it is no C struct.  Every entry point takes it twice: `host`, which the checks read, and
+ * `table`, the 8-byte aligned device copy the kernel reads (a caller uploads the tables of all layers of a read in one copy).
+ *
+ * UMOE_DAC_ROW_WORDS words per row of umoe_dac_conv1d_win_rows / umoe_dac_conv_transpose1d_win_rows:
+ *   0 x       plane [Cin][Lx] of the row's input window (a device address)
+ *   1 resid   plane [Cout][Lr] of its residual window, 0 = none (umoe_dac_conv_transpose1d_win_rows does not read it)
+ *   2 y       plane [Cout][Ly] of its output window
+ *   3 x_off   4 Lx   5 r_off   6 Lr   7 y_off   8 Ly   9 t_begin   10 n      as the arguments of the _win entries
+ *   11 L      the true length of the row's sequence at this layer's input
+ * Grid (ceil(max_n / 64), ceil(Cout / 64), rows); a workgroup whose tile starts at or past its row's n returns at once, so n = 0 makes a
+ * row idle (its other words are not read).  Every row with n > 0 passes the checks of the _win entry and has n <= max_n; nothing is
+ * enqueued unless all rows pass.  The kernels are the _win kernels' bodies, so an output is bit-identical to umoe_dac_conv1d_win /
+ * umoe_dac_conv_transpose1d_win on that row's window.
+ *
+ * UMOE_RVQ_ROW_WORDS words per row of umoe_rvq_from_delayed_rows (umoe_rvq_from_delayed with a record per z row):
+ *   0 row     the token row   1 f0   2 n   3 t_valid (the row's own: its local step + 1)
+ *   4 z       plane [Dl][Lz] (a device address)   5 col: frame f0's column   6 Lz   7 reserved
+ *
+ * UMOE_SHIFT_ROW_WORDS words per row of umoe_dac_shift_rows (the left context of a slab, moved in place):
+ *   0 plane   [C][W] (a device address)   1 W   2 shift   3 count: columns [shift, shift + count) move to [0, count); 0 = leave alone */
+#define UMOE_DAC_ROW_WORDS 12
+#define UMOE_RVQ_ROW_WORDS 8
+#define UMOE_SHIFT_ROW_WORDS 4
+int umoe_dac_conv1d_win_rows(const int64_t* host, const int64_t* table, int rows, int max_n, const float* w, const float* bias,
+                             const float* snake_alpha, int Cin, int Cout, int K, int stride, int dilation, int pad, int act,
+                             umoe_stream_t stream);
+int umoe_dac_conv_transpose1d_win_rows(const int64_t* host, const int64_t* table, int rows, int max_n, const float* w, const float* bias,
+                                       const float* snake_alpha, int Cin, int Cout, int K, int stride, int pad, int out_pad,
+                                       umoe_stream_t stream);
+int umoe_dac_shift_rows(const int64_t* host, const int64_t* table, int rows, int C, umoe_stream_t stream);
+int umoe_rvq_from_delayed_rows(const int32_t* tokens, int B, int Tmax, int NQ, const int32_t* prefill_step, const int32_t* delay, int pad,
+                               const int64_t* host, const int64_t* table, int rows, int max_n, const float* codebooks, const float* out_w,
+                               const float* out_b, int CB, int cd, int Dl, umoe_stream_t stream);
 /* windowed-sinc resampling to the codec's rate (torchaudio.transforms.Resample as used at utils.py:101-110, restated): with o / n =
  * orig / new frequency over their gcd, kern [n][2 width + o] the filter bank (built by the host from the published formula),
  * y[b][frame * n + phase] = sum_t kern[phase][t] * x[b][frame * o - width + t] (zero outside [0, L)). */

@@ -174,6 +174,7 @@ EXPORTS = [
     "umoe_tiled_gemm_w12",
     "umoe_kv_prefix_copy", "umoe_engine_prefix_build", "umoe_engine_admit_prefix",
     "umoe_engine_set_admit_dump",
+    "umoe_dac_conv1d_win_rows", "umoe_dac_conv_transpose1d_win_rows", "umoe_dac_shift_rows", "umoe_rvq_from_delayed_rows",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -229,6 +230,12 @@ def lib():
         L.umoe_dac_conv1d_win.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32] + [i32] * 9 + [i32, i32, vp, i32, i32, vp]
         L.umoe_dac_conv_transpose1d_win.argtypes = [vp, i32, i32, vp, vp, vp] + [i32] * 8 + [i32, i32, vp, i32, i32, vp]
         L.umoe_rvq_from_delayed.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]
+        if not hasattr(L, "umoe_dac_conv1d_win_rows"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_dac_conv1d_win_rows): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        L.umoe_dac_conv1d_win_rows.argtypes = [vp, vp, i32, i32, vp, vp, vp] + [i32] * 7 + [vp]
+        L.umoe_dac_conv_transpose1d_win_rows.argtypes = [vp, vp, i32, i32, vp, vp, vp] + [i32] * 6 + [vp]
+        L.umoe_dac_shift_rows.argtypes = [vp, vp, i32, i32, vp]
+        L.umoe_rvq_from_delayed_rows.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_rope.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_attn.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]
         L.umoe_swiglu_pair.argtypes = [vp, i32, i32, i32, vp, vp]

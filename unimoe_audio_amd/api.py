@@ -35,6 +35,11 @@ class AudioChunk(NamedTuple):
     final: bool
 
 
+# serve(stream=True): do the rows' DAC windows go through the per-row table kernels, one launch per layer (True), or through one
+# umoe_dac_*_win launch per layer and row (False)?  Decided by scripts/serve_stream_bench.py (profiles/serve_stream.json).
+SERVE_STREAM_RAGGED = True
+
+
 def _frame_codes(eng, row: int, f0: int, f1: int, t_valid: int) -> torch.Tensor:
     """codes [f1 - f0, C] (int64, CPU) of frames [f0, f1) of `row`, read from the engine's delayed token buffer as generate_output
     reverts them: tokens[row][prefill_step + t + delay_c][c], the pad code at positions >= t_valid (DecodeEngine.finish())"""
@@ -413,7 +418,7 @@ class UniMoEAudio:
     @torch.no_grad()
     def serve(self, requests, slots: int = 8, output_dir: Optional[str] = "./", poll_every: int = 16, max_prompt_tokens: int = 512,
               max_audio_seconds: int = 20, use_graph: bool = True, expert_weights: Optional[str] = None, w12_wide: Optional[bool] = None,
-              prefix_cache: bool = False, prefix_cache_voices: int = 8):
+              prefix_cache: bool = False, prefix_cache_voices: int = 8, stream: bool = False, stream_ragged: Optional[bool] = None):
         """Continuous batching: a generator that takes SpeechRequest / MusicRequest objects from any iterable (read lazily) and yields
         (index, wav path) as each request ends -- index = the request's position in `requests`, the file is
         `generated_<save_name>_<index>.wav`; output_dir=None yields (index, codes [len, C]) instead.  `slots` rows (1..32) decode together,
@@ -422,7 +427,14 @@ class UniMoEAudio:
         rows keep decoding (DecodeEngine.admit, unimoe_audio_amd/serve.py).  Each request's prompt pair is built as generate_batch builds it
         and keeps its own length.  The engine is sized once: max_prompt_tokens per prompt, max_audio_seconds per request; a request beyond
         either is refused when its turn comes.  `w12_wide`: above 8 slots, bf16 expert weights stream as their lossless 12-bit copies in the wide
-        step (model.engine).  Not for expert-parallel engines, video prompts or streamed chunks.
+        step (model.engine).  Not for expert-parallel engines or video prompts.
+        stream=True: the generator yields AudioChunk(row=<request index>, start_sample, pcm, final) instead, every `poll_every` steps for
+        every live request whose frames became final: chunks of different requests interleave, the chunks of one request are
+        contiguous, its `final` chunk carries the min_duration=1 pad, and concatenated they are the samples of the wav the non-streaming
+        path writes.  With output_dir set that wav is written when the final chunk is produced (output_dir=None is allowed: the chunks
+        are the result).  Every row decodes its audio on a timeline of its own (dac.DacRowStreamDecoder), queued on the decode stream
+        between two steps.  stream_ragged: True = one launch per DAC layer for all rows, False = one per layer and row with news;
+        None = SERVE_STREAM_RAGGED, the measured default.
         `prefix_cache`: speech requests with equal (prompt_transcription, prompt_wav or id(prompt_codec)) share a VoicePrompt: the voice's
         prompt prefix is prefilled once per engine, and every admission installs its K / V and prefills only the sentence behind it
         (DESIGN 4n); at most `prefix_cache_voices` voices are kept, least recently used first out.  A request that carries its own
@@ -437,6 +449,7 @@ class UniMoEAudio:
         app = self
         voices = VoiceLRU(prefix_cache_voices) if prefix_cache else None
         prefix_log = []                                    # (hit, P) per admission, in admission order
+        emitted = {}                                       # stream=True: row -> frames of its request handed out so far
 
         class Rows:
             """the engine as unimoe_audio_amd.serve.Scheduler drives it"""
@@ -473,13 +486,17 @@ class UniMoEAudio:
                     eng.admit(row, x.reshape(-1, x.shape[-1]).contiguous(), enc.attention_mask, prefill[0], steps[0], **settings)
                     prefix_log.append((False, 0))
                 self.held[row] = r
+                emitted[row] = 0
 
             def steps(self, n):
                 for _ in range(n):
                     eng.step(use_graph)
 
             def poll(self):
-                return eng.poll()
+                if not stream:
+                    return eng.poll()
+                state, self.clock = eng.poll_clock()       # the clocks of the same read: what serve.final_frames needs
+                return state
 
             def row_done(self, state, row):
                 return eng.row_done(state, row)
@@ -491,6 +508,10 @@ class UniMoEAudio:
         sched = Scheduler(Rows(), slots, poll_every, max_slots=MAX_SLOTS_WIDE)
         self.served_rows = {}                              # request index -> the row it decoded in (of the last / the running serve())
         self.served_prefix = {}                            # request index -> (prefix store hit, prefix tokens P)
+        if stream:
+            ragged = SERVE_STREAM_RAGGED if stream_ragged is None else bool(stream_ragged)
+            yield from self._serve_stream(sched, eng, requests, emitted, prefix_log, output_dir, ragged)
+            return
         for index, (r, codes, length) in sched.run(requests):
             self.served_rows.update({i: row for i, row, _ in sched.admitted})
             self.served_prefix.update({i: hp for (i, _, _), hp in zip(sched.admitted, prefix_log)})
@@ -502,6 +523,57 @@ class UniMoEAudio:
             path = os.path.join(output_dir, f"generated_{r.save_name}_{index}.wav")
             self.dac.decode(audio.transpose(0, 1).unsqueeze(0), save_path=path, min_duration=1)
             yield index, path
+
+    def _serve_stream(self, sched, eng, requests, emitted, prefix_log, output_dir, ragged):
+        """serve(stream=True): at every poll, before an ended row is taken and the next request admitted into it (Scheduler.run's
+        hook), the frames that became final on each row's own clock (serve.final_frames) go through umoe_rvq_from_delayed_rows and the
+        per-row DAC decoder; rows that ended are flushed (min_duration=1, as _finish pads) and reset for their next request."""
+        from .dac import DacRowStreamDecoder, DelayedRowsSource, write_wav_pcm16
+        from .serve import final_frames
+        dm = self.dac.model
+        md = max(self.model.config.codec_delay_pattern)
+        source = DelayedRowsSource(eng, dm)                # (refuses a DAC with fewer codebooks than codec channels)
+        decoder = DacRowStreamDecoder(dm, sched.slots, source, max_frames=sched.poll_every, ragged=ragged)
+        self.serve_decoder = decoder
+        start, kept = {}, {}
+
+        def hook(state):
+            frames = final_frames(state.tolist(), sched.engine.clock.tolist(), eng.prefill_steps, md, {row: emitted[row] for row in sched.live})
+            n_new = [0] * sched.slots
+            for fr in frames:
+                source.t_valid[fr.row], n_new[fr.row], emitted[fr.row] = fr.t_valid, fr.f1 - fr.f0, fr.f1
+            out = decoder.push(n_new)
+            ends = [fr.row for fr in frames if fr.complete]
+            tail = decoder.flush(ends, min_duration=1) if ends else {}
+            parts = [(fr, [t for t in (out.get(fr.row), tail.get(fr.row)) if t is not None]) for fr in frames]
+            flat = [t for _, ts in parts for t in ts]
+            host = torch.cat(flat).float().cpu() if flat else torch.zeros(0)      # one copy to the host per read
+            o, chunks = 0, []
+            for fr, ts in parts:
+                n = sum(t.numel() for t in ts)
+                pcm, o = host[o:o + n], o + n
+                if n == 0 and not fr.complete:
+                    continue
+                index = sched.live[fr.row]
+                chunks.append(AudioChunk(index, start.get(index, 0), pcm, fr.complete))
+                start[index] = start.get(index, 0) + n
+                if output_dir is not None:
+                    kept.setdefault(index, []).append(pcm)
+                if fr.complete:
+                    decoder.reset(fr.row)
+                    if output_dir is not None:
+                        os.makedirs(output_dir, exist_ok=True)
+                        name = sched.engine.held[fr.row].save_name
+                        write_wav_pcm16(os.path.join(output_dir, f"generated_{name}_{index}.wav"), torch.cat(kept.pop(index))[None], dm.sample_rate)
+            return chunks
+
+        for item in sched.run(requests, hook):
+            self.served_rows.update({i: row for i, row, _ in sched.admitted})
+            self.served_prefix.update({i: hp for (i, _, _), hp in zip(sched.admitted, prefix_log)})
+            if isinstance(item, AudioChunk):
+                yield item
+            elif item[1][2] != emitted[self.served_rows[item[0]]]:      # (index, (request, codes, length)): the row as take() has it
+                raise AssertionError(f"serve: request {item[0]} streamed {emitted[self.served_rows[item[0]]]} frames, take() has {item[1][2]}")
 
     def _split_point(self, enc, voice: VoicePrompt) -> int:
         """P of a request in `voice`: the longest common prefix of the pair's id rows and the voice's prefix ids, clamped to T - 2; 0 when

@@ -12,6 +12,9 @@
 // hold only a window of the input / residual / output.  Only the addressing differs: every output goes through the same loads
 // (zero outside [0, L)), the same accumulation order (channel chunk, channel, tap) and the same epilogue, so it depends on the
 // input values alone and never on the window or the tile start.
+// Per-row twins (umoe_dac_conv1d_win_rows / umoe_dac_conv_transpose1d_win_rows, the per-row streaming decoder of dac.py): the WIN
+// bodies a third time, each row of the launch on a window of its own read from a table (umoe.h "Per-row window tables").  The bodies
+// are include files (umoe_dac_conv1d_body.h, umoe_dac_convt1d_body.h) so that every kernel compiles the same token stream.
 #include "umoe_common.h"
 
 namespace {
@@ -38,66 +41,7 @@ __global__ __launch_bounds__(256) void dac_conv1d_kernel(const float* __restrict
     float* xl = sm;                       // [CC][XW]
     float* wl = sm + CC * XW;             // [CC][K][TO]
     const int t0 = (WIN ? win.t_begin : 0) + blockIdx.x * TP, co0 = blockIdx.y * TO, b = blockIdx.z, tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    const int Lx = WIN ? win.Lx : L, x_off = WIN ? win.x_off : 0;
-    const float* xb = x + (size_t)b * Cin * Lx;
-    const int in0 = t0 * stride - pad;    // input position of LDS column 0
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    for (int c0 = 0; c0 < Cin; c0 += CC) {
-        for (int i = tid; i < CC * XW; i += 256) {
-            const int c = i / XW, p = i % XW, ci = c0 + c, pos = in0 + p;
-            float v = 0.f;
-            // (WIN: a position outside the buffer feeds only outputs past the window; the entry point checks the window's own)
-            if (ci < Cin && pos >= 0 && pos < L && (!WIN || (pos >= x_off && pos < x_off + Lx))) {
-                v = xb[(size_t)ci * Lx + (pos - x_off)];
-                if (alpha) v = snake(v, alpha[ci]);
-            }
-            xl[i] = v;
-        }
-        for (int i = tid; i < CC * K * TO; i += 256) {
-            const int o = i % TO, k = (i / TO) % K, c = i / (TO * K), ci = c0 + c, co = co0 + o;
-            wl[i] = (ci < Cin && co < Cout) ? w[((size_t)co * Cin + ci) * K + k] : 0.f;
-        }
-        __syncthreads();
-        for (int c = 0; c < CC; ++c)
-            for (int k = 0; k < K; ++k) {
-                const float4 wv = *reinterpret_cast<const float4*>(wl + (c * K + k) * TO + ty * 4);
-                const float* xr = xl + c * XW + k * dil;
-                float xv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xv[j] = xr[(tx + 16 * j) * stride];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[0][j] += wv.x * xv[j];
-                    acc[1][j] += wv.y * xv[j];
-                    acc[2][j] += wv.z * xv[j];
-                    acc[3][j] += wv.w * xv[j];
-                }
-            }
-        __syncthreads();
-    }
-    const int t_end = WIN ? win.t_begin + win.n : Lout;
-    const int Ly = WIN ? win.Ly : Lout, y_off = WIN ? win.y_off : 0;
-    const int Lr = WIN ? win.Lr : Lout, r_off = WIN ? win.r_off : 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int co = co0 + ty * 4 + i;
-        if (co >= Cout) continue;
-        const float bv = bias ? bias[co] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int t = t0 + tx + 16 * j;
-            if (t >= t_end) continue;
-            float v = acc[i][j] + bv;
-            if (act == 1) v = tanhf(v);
-            if (resid) v += resid[((size_t)b * Cout + co) * Lr + (t - r_off)];
-            y[((size_t)b * Cout + co) * Ly + (t - y_off)] = v;
-        }
-    }
+#include "umoe_dac_conv1d_body.h"
 }
 
 // ConvTranspose1d, gather form: y[b][co][t] = bias[co] + sum_ci sum_{k == (t + pad) mod stride, k < K} snake?(x[b][ci][(t + pad - k) / stride]) * w[ci][co][k]
@@ -109,60 +53,67 @@ __global__ __launch_bounds__(256) void dac_convt1d_kernel(const float* __restric
     float* xl = sm;                       // [CC][XW]
     float* wl = sm + CC * XW;             // [CC][K][TO]
     const int t0 = (WIN ? win.t_begin : 0) + blockIdx.x * TP, co0 = blockIdx.y * TO, b = blockIdx.z, tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    const int Lx = WIN ? win.Lx : L, x_off = WIN ? win.x_off : 0;
-    const float* xb = x + (size_t)b * Cin * Lx;
-    const int M = (K + stride - 1) / stride;                 // taps per output position
-    const int ibase = (t0 + pad) / stride - (M - 1);         // input index of LDS column 0
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    for (int c0 = 0; c0 < Cin; c0 += CC) {
-        for (int i = tid; i < CC * XW; i += 256) {
-            const int c = i / XW, p = i % XW, ci = c0 + c, pos = ibase + p;
-            float v = 0.f;
-            if (ci < Cin && pos >= 0 && pos < L && (!WIN || (pos >= x_off && pos < x_off + Lx))) {
-                v = xb[(size_t)ci * Lx + (pos - x_off)];
-                if (alpha) v = snake(v, alpha[ci]);
-            }
-            xl[i] = v;
-        }
-        for (int i = tid; i < CC * K * TO; i += 256) {
-            const int o = i % TO, k = (i / TO) % K, c = i / (TO * K), ci = c0 + c, co = co0 + o;
-            wl[i] = (ci < Cin && co < Cout) ? w[((size_t)ci * Cout + co) * K + k] : 0.f;
-        }
-        __syncthreads();
-        for (int c = 0; c < CC; ++c)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int tp = t0 + tx + 16 * j + pad;
-                const int k0 = tp % stride, i0 = tp / stride - ibase;
-                for (int m = 0; m < M; ++m) {
-                    const int k = k0 + m * stride;
-                    if (k >= K) break;
-                    const float xv = xl[c * XW + i0 - m];
-                    const float4 wv = *reinterpret_cast<const float4*>(wl + (c * K + k) * TO + ty * 4);
-                    acc[0][j] += wv.x * xv;
-                    acc[1][j] += wv.y * xv;
-                    acc[2][j] += wv.z * xv;
-                    acc[3][j] += wv.w * xv;
-                }
-            }
-        __syncthreads();
-    }
-    const int t_end = WIN ? win.t_begin + win.n : Lout;
-    const int Ly = WIN ? win.Ly : Lout, y_off = WIN ? win.y_off : 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int co = co0 + ty * 4 + i;
-        if (co >= Cout) continue;
-        const float bv = bias ? bias[co] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int t = t0 + tx + 16 * j;
-            if (t < t_end) y[((size_t)b * Cout + co) * Ly + (t - y_off)] = acc[i][j] + bv;
+#include "umoe_dac_convt1d_body.h"
+}
+
+// ---- the WIN bodies once more, every row of the launch (blockIdx.z) on a window of its own: the row's plane pointers, its DacWin
+// and its L come from row blockIdx.z of a table (umoe.h "Per-row window tables").  Every word is read at an address that depends on
+// blockIdx.z alone, so the loads are scalar and the values wave-uniform.  A workgroup whose tile starts at or past its row's n
+// (n = 0: the row is idle in this launch) leaves before the first barrier; all threads of a workgroup take the same way.
+#define DAC_ROW_WIN(r) DacWin{(int)(r)[3], (int)(r)[4], (int)(r)[5], (int)(r)[6], (int)(r)[7], (int)(r)[8], (int)(r)[9], (int)(r)[10]}
+
+__global__ __launch_bounds__(256) void dac_conv1d_rows_kernel(const int64_t* __restrict__ table, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, const float* __restrict__ alpha, int Cin, int Cout,
+                                                              int K, int stride, int dil, int pad, int act, int XW) {
+    const int64_t* row = table + (size_t)blockIdx.z * UMOE_DAC_ROW_WORDS;
+    const DacWin win = DAC_ROW_WIN(row);
+    if ((int)(blockIdx.x * TP) >= win.n) return;
+    constexpr bool WIN = true;
+    const float* __restrict__ x = reinterpret_cast<const float*>(row[0]);
+    const float* __restrict__ resid = reinterpret_cast<const float*>(row[1]);
+    float* __restrict__ y = reinterpret_cast<float*>(row[2]);
+    const int L = (int)row[11], Lout = 0;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* xl = sm;                       // [CC][XW]
+    float* wl = sm + CC * XW;             // [CC][K][TO]
+    const int t0 = win.t_begin + blockIdx.x * TP, co0 = blockIdx.y * TO, b = 0, tid = threadIdx.x;      // (b: the planes are the row's own)
+#include "umoe_dac_conv1d_body.h"
+}
+
+__global__ __launch_bounds__(256) void dac_convt1d_rows_kernel(const int64_t* __restrict__ table, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, const float* __restrict__ alpha, int Cin, int Cout,
+                                                               int K, int stride, int pad, int XW) {
+    const int64_t* row = table + (size_t)blockIdx.z * UMOE_DAC_ROW_WORDS;
+    const DacWin win = DAC_ROW_WIN(row);
+    if ((int)(blockIdx.x * TP) >= win.n) return;
+    constexpr bool WIN = true;
+    const float* __restrict__ x = reinterpret_cast<const float*>(row[0]);
+    float* __restrict__ y = reinterpret_cast<float*>(row[2]);
+    const int L = (int)row[11], Lout = 0;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* xl = sm;                       // [CC][XW]
+    float* wl = sm + CC * XW;             // [CC][K][TO]
+    const int t0 = win.t_begin + blockIdx.x * TP, co0 = blockIdx.y * TO, b = 0, tid = threadIdx.x;
+#include "umoe_dac_convt1d_body.h"
+}
+#undef DAC_ROW_WIN
+
+// Left context of the per-row decoder's slabs, all rows of a layer in one launch: row r's plane [C][W] moves its columns
+// [shift, shift + count) to [0, count) in place.  One workgroup per (16 channels, row); a channel's columns go 256 at a time from the
+// left.  A batch is read by all threads before any of it is written (the barrier), and it lands left of everything still to be read
+// (shift > 0), so no column is overwritten before it was moved.
+__global__ __launch_bounds__(256) void dac_shift_rows_kernel(const int64_t* __restrict__ table, int C) {
+    const int64_t* r = table + (size_t)blockIdx.y * UMOE_SHIFT_ROW_WORDS;
+    float* plane = reinterpret_cast<float*>(r[0]);
+    const int W = (int)r[1], shift = (int)r[2], count = (int)r[3];
+    if (count <= 0 || shift <= 0) return;
+    for (int c = blockIdx.x * 16; c < min(C, (int)blockIdx.x * 16 + 16); ++c) {
+        float* p = plane + (size_t)c * W;
+        for (int j0 = 0; j0 < count; j0 += 256) {
+            const int j = j0 + threadIdx.x;
+            const float v = j < count ? p[j + shift] : 0.f;
+            __syncthreads();
+            if (j < count) p[j] = v;
         }
     }
 }
@@ -245,6 +196,44 @@ bool dac_needed(long long lo, long long hi, int L, long long* a, long long* b) {
     *b = hi > (long long)L - 1 ? (long long)L - 1 : hi;
     return *a <= *b;
 }
+
+// the checks of one window, shared by the _win entries (one window for all planes) and the _rows entries (one per row)
+int dac_conv1d_win_check(const char* who, int x_off, int Lx, bool has_resid, int r_off, int Lr, int L, int K, int stride, int dilation, int pad,
+                         int t_begin, int n, int y_off, int Ly) {
+    UMOE_REQUIRE(L > 0 && Lx > 0 && Ly > 0 && t_begin >= 0 && n > 0, "%s: bad argument", who);
+    const long long Lout = dac_conv_out_len(L, K, stride, dilation, pad);
+    UMOE_REQUIRE(Lout > 0, "%s: empty output (L=%d K=%d stride=%d dilation=%d pad=%d)", who, L, K, stride, dilation, pad);
+    UMOE_REQUIRE((long long)t_begin + n <= Lout, "%s: outputs [%d, %d) past the sequence's %lld", who, t_begin, t_begin + n, Lout);
+    long long a, b;
+    if (dac_needed((long long)t_begin * stride - pad, (long long)(t_begin + n - 1) * stride - pad + (long long)(K - 1) * dilation, L, &a, &b))
+        UMOE_REQUIRE(a >= x_off && b < (long long)x_off + Lx, "%s: outputs [%d, %d) read input [%lld, %lld], the buffer holds [%d, %d)", who,
+                     t_begin, t_begin + n, a, b, x_off, x_off + Lx);
+    UMOE_REQUIRE(t_begin >= y_off && (long long)t_begin + n <= (long long)y_off + Ly, "%s: output buffer [%d, %d) misses [%d, %d)", who, y_off,
+                 y_off + Ly, t_begin, t_begin + n);
+    if (has_resid)
+        UMOE_REQUIRE(Lr > 0 && t_begin >= r_off && (long long)t_begin + n <= (long long)r_off + Lr, "%s: residual buffer [%d, %d) misses [%d, %d)",
+                     who, r_off, r_off + Lr, t_begin, t_begin + n);
+    return 0;
+}
+
+int dac_convt1d_win_check(const char* who, int x_off, int Lx, int L, int K, int stride, int pad, int out_pad, int t_begin, int n, int y_off,
+                          int Ly) {
+    UMOE_REQUIRE(L > 0 && Lx > 0 && Ly > 0 && t_begin >= 0 && n > 0, "%s: bad argument", who);
+    const long long Lout = ((long long)L - 1) * stride - 2 * pad + K + out_pad;
+    UMOE_REQUIRE((long long)t_begin + n <= Lout, "%s: outputs [%d, %d) past the sequence's %lld", who, t_begin, t_begin + n, Lout);
+    // output t reads inputs i with i * stride + k == t + pad, 0 <= k < K
+    const long long lo = ((long long)t_begin + pad - K + stride + (long long)stride * K) / stride - K;   // ceil((t_begin + pad - K + 1) / stride)
+    long long a, b;
+    if (dac_needed(lo, ((long long)t_begin + n - 1 + pad) / stride, L, &a, &b))
+        UMOE_REQUIRE(a >= x_off && b < (long long)x_off + Lx, "%s: outputs [%d, %d) read input [%lld, %lld], the buffer holds [%d, %d)", who,
+                     t_begin, t_begin + n, a, b, x_off, x_off + Lx);
+    UMOE_REQUIRE(t_begin >= y_off && (long long)t_begin + n <= (long long)y_off + Ly, "%s: output buffer [%d, %d) misses [%d, %d)", who, y_off,
+                 y_off + Ly, t_begin, t_begin + n);
+    return 0;
+}
+
+// a table word that must be an int (offsets, lengths, positions)
+bool dac_word_is_int(int64_t v) { return v >= 0 && v <= 0x7fffffffLL; }
 }  // namespace
 
 extern "C" int umoe_dac_conv1d_win(const float* x, int x_off, int Lx, const float* w, const float* bias, const float* snake_alpha,
@@ -252,25 +241,15 @@ extern "C" int umoe_dac_conv1d_win(const float* x, int x_off, int Lx, const floa
                                    int dilation, int pad, int act, int t_begin, int n, float* y, int y_off, int Ly, umoe_stream_t stream) {
     UMOE_REQUIRE(x && w && y && B > 0 && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && dilation > 0 && pad >= 0 && L > 0 && Lx > 0 &&
                  Ly > 0 && t_begin >= 0 && n > 0, "umoe_dac_conv1d_win: bad argument");
-    const long long Lout = dac_conv_out_len(L, K, stride, dilation, pad);
-    UMOE_REQUIRE(Lout > 0, "umoe_dac_conv1d_win: empty output (L=%d K=%d stride=%d dilation=%d pad=%d)", L, K, stride, dilation, pad);
-    UMOE_REQUIRE((long long)t_begin + n <= Lout, "umoe_dac_conv1d_win: outputs [%d, %d) past the sequence's %lld", t_begin, t_begin + n, Lout);
-    long long a, b;
-    if (dac_needed((long long)t_begin * stride - pad, (long long)(t_begin + n - 1) * stride - pad + (long long)(K - 1) * dilation, L, &a, &b))
-        UMOE_REQUIRE(a >= x_off && b < (long long)x_off + Lx, "umoe_dac_conv1d_win: outputs [%d, %d) read input [%lld, %lld], the buffer holds [%d, %d)",
-                     t_begin, t_begin + n, a, b, x_off, x_off + Lx);
-    UMOE_REQUIRE(t_begin >= y_off && (long long)t_begin + n <= (long long)y_off + Ly, "umoe_dac_conv1d_win: output buffer [%d, %d) misses [%d, %d)",
-                 y_off, y_off + Ly, t_begin, t_begin + n);
-    if (resid)
-        UMOE_REQUIRE(Lr > 0 && t_begin >= r_off && (long long)t_begin + n <= (long long)r_off + Lr,
-                     "umoe_dac_conv1d_win: residual buffer [%d, %d) misses [%d, %d)", r_off, r_off + Lr, t_begin, t_begin + n);
+    if (int rc = dac_conv1d_win_check("umoe_dac_conv1d_win", x_off, Lx, resid != nullptr, r_off, Lr, L, K, stride, dilation, pad, t_begin, n, y_off, Ly))
+        return rc;
     const int XW = (TP - 1) * stride + (K - 1) * dilation + 1;
     const size_t lds = ((size_t)CC * XW + (size_t)CC * K * TO) * sizeof(float);
     UMOE_REQUIRE(lds <= 64 * 1024, "umoe_dac_conv1d_win: tile needs %zu bytes of LDS", lds);
     dim3 grid((unsigned)ceil_div(n, TP), (unsigned)ceil_div(Cout, TO), (unsigned)B);
     const DacWin win{x_off, Lx, r_off, Lr, y_off, Ly, t_begin, n};
     dac_conv1d_kernel<true><<<grid, 256, lds, (hipStream_t)stream>>>(x, w, bias, snake_alpha, resid, Cin, L, Cout, K, stride, dilation, pad,
-                                                                     (int)Lout, act, XW, y, win);
+                                                                     (int)dac_conv_out_len(L, K, stride, dilation, pad), act, XW, y, win);
     UMOE_LAUNCH_CHECK();
     return 0;
 }
@@ -280,18 +259,8 @@ extern "C" int umoe_dac_conv_transpose1d_win(const float* x, int x_off, int Lx, 
                                              float* y, int y_off, int Ly, umoe_stream_t stream) {
     UMOE_REQUIRE(x && w && y && B > 0 && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && pad >= 0 && out_pad >= 0 && L > 0 && Lx > 0 &&
                  Ly > 0 && t_begin >= 0 && n > 0, "umoe_dac_conv_transpose1d_win: bad argument");
+    if (int rc = dac_convt1d_win_check("umoe_dac_conv_transpose1d_win", x_off, Lx, L, K, stride, pad, out_pad, t_begin, n, y_off, Ly)) return rc;
     const long long Lout = ((long long)L - 1) * stride - 2 * pad + K + out_pad;
-    UMOE_REQUIRE((long long)t_begin + n <= Lout, "umoe_dac_conv_transpose1d_win: outputs [%d, %d) past the sequence's %lld", t_begin,
-                 t_begin + n, Lout);
-    // output t reads inputs i with i * stride + k == t + pad, 0 <= k < K
-    const long long lo = ((long long)t_begin + pad - K + stride + (long long)stride * K) / stride - K;   // ceil((t_begin + pad - K + 1) / stride)
-    long long a, b;
-    if (dac_needed(lo, ((long long)t_begin + n - 1 + pad) / stride, L, &a, &b))
-        UMOE_REQUIRE(a >= x_off && b < (long long)x_off + Lx,
-                     "umoe_dac_conv_transpose1d_win: outputs [%d, %d) read input [%lld, %lld], the buffer holds [%d, %d)", t_begin, t_begin + n,
-                     a, b, x_off, x_off + Lx);
-    UMOE_REQUIRE(t_begin >= y_off && (long long)t_begin + n <= (long long)y_off + Ly,
-                 "umoe_dac_conv_transpose1d_win: output buffer [%d, %d) misses [%d, %d)", y_off, y_off + Ly, t_begin, t_begin + n);
     const int M = (K + stride - 1) / stride;
     const int XW = (TP - 1 + stride - 1) / stride + M + 1;
     const size_t lds = ((size_t)CC * XW + (size_t)CC * K * TO) * sizeof(float);
@@ -299,6 +268,93 @@ extern "C" int umoe_dac_conv_transpose1d_win(const float* x, int x_off, int Lx, 
     dim3 grid((unsigned)ceil_div(n, TP), (unsigned)ceil_div(Cout, TO), (unsigned)B);
     const DacWin win{x_off, Lx, 0, 0, y_off, Ly, t_begin, n};
     dac_convt1d_kernel<true><<<grid, 256, lds, (hipStream_t)stream>>>(x, w, bias, snake_alpha, Cin, L, Cout, K, stride, pad, (int)Lout, XW, y, win);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- one window per row (the per-row streaming decoder of dac.py): `host` is the table the checks read, `table` the device copy the
+// kernel reads (the caller uploads the tables of all layers of a read in one copy).  Every row with n > 0 passes the checks of the _win
+// entry; a row with n == 0 is idle and only its n is read.  Nothing is enqueued unless every row passes.
+namespace {
+int dac_rows_common(const char* who, const int64_t* host, const int64_t* table, int rows, int max_n) {
+    UMOE_REQUIRE(host && table && rows > 0 && rows <= 65535 && max_n >= 0, "%s: bad argument", who);
+    UMOE_REQUIRE(((size_t)table & 7) == 0, "%s: the device table must be 8-byte aligned", who);
+    for (int r = 0; r < rows; ++r) {
+        const int64_t* d = host + (size_t)r * UMOE_DAC_ROW_WORDS;
+        UMOE_REQUIRE(d[10] >= 0 && d[10] <= max_n, "%s: row %d has n = %lld, max_n is %d", who, r, (long long)d[10], max_n);
+        if (d[10] == 0) continue;
+        UMOE_REQUIRE(d[0] && d[2], "%s: row %d has a null plane", who, r);
+        for (int k = 3; k < UMOE_DAC_ROW_WORDS; ++k)
+            UMOE_REQUIRE(dac_word_is_int(d[k]), "%s: row %d, word %d (%lld) is not a non-negative int", who, r, k, (long long)d[k]);
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int umoe_dac_conv1d_win_rows(const int64_t* host, const int64_t* table, int rows, int max_n, const float* w, const float* bias,
+                                        const float* snake_alpha, int Cin, int Cout, int K, int stride, int dilation, int pad, int act,
+                                        umoe_stream_t stream) {
+    const char* who = "umoe_dac_conv1d_win_rows";
+    UMOE_REQUIRE(w && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && dilation > 0 && pad >= 0, "%s: bad argument", who);
+    if (int rc = dac_rows_common(who, host, table, rows, max_n)) return rc;
+    for (int r = 0; r < rows; ++r) {
+        const int64_t* d = host + (size_t)r * UMOE_DAC_ROW_WORDS;
+        if (d[10] == 0) continue;
+        if (int rc = dac_conv1d_win_check(who, (int)d[3], (int)d[4], d[1] != 0, (int)d[5], (int)d[6], (int)d[11], K, stride, dilation, pad, (int)d[9],
+                                          (int)d[10], (int)d[7], (int)d[8]))
+            return rc;
+    }
+    if (max_n == 0) return 0;
+    const int XW = (TP - 1) * stride + (K - 1) * dilation + 1;
+    const size_t lds = ((size_t)CC * XW + (size_t)CC * K * TO) * sizeof(float);
+    UMOE_REQUIRE(lds <= 64 * 1024, "%s: tile needs %zu bytes of LDS", who, lds);
+    dim3 grid((unsigned)ceil_div(max_n, TP), (unsigned)ceil_div(Cout, TO), (unsigned)rows);
+    dac_conv1d_rows_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(table, w, bias, snake_alpha, Cin, Cout, K, stride, dilation, pad, act, XW);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int umoe_dac_conv_transpose1d_win_rows(const int64_t* host, const int64_t* table, int rows, int max_n, const float* w,
+                                                  const float* bias, const float* snake_alpha, int Cin, int Cout, int K, int stride, int pad,
+                                                  int out_pad, umoe_stream_t stream) {
+    const char* who = "umoe_dac_conv_transpose1d_win_rows";
+    UMOE_REQUIRE(w && Cin > 0 && Cout > 0 && K > 0 && stride > 0 && pad >= 0 && out_pad >= 0, "%s: bad argument", who);
+    if (int rc = dac_rows_common(who, host, table, rows, max_n)) return rc;
+    for (int r = 0; r < rows; ++r) {
+        const int64_t* d = host + (size_t)r * UMOE_DAC_ROW_WORDS;
+        if (d[10] == 0) continue;
+        if (int rc = dac_convt1d_win_check(who, (int)d[3], (int)d[4], (int)d[11], K, stride, pad, out_pad, (int)d[9], (int)d[10], (int)d[7], (int)d[8]))
+            return rc;
+    }
+    if (max_n == 0) return 0;
+    const int M = (K + stride - 1) / stride;
+    const int XW = (TP - 1 + stride - 1) / stride + M + 1;
+    const size_t lds = ((size_t)CC * XW + (size_t)CC * K * TO) * sizeof(float);
+    UMOE_REQUIRE(lds <= 64 * 1024, "%s: tile needs %zu bytes of LDS", who, lds);
+    dim3 grid((unsigned)ceil_div(max_n, TP), (unsigned)ceil_div(Cout, TO), (unsigned)rows);
+    dac_convt1d_rows_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(table, w, bias, snake_alpha, Cin, Cout, K, stride, pad, XW);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+// table rows of UMOE_SHIFT_ROW_WORDS words {plane, W, shift, count}: columns [shift, shift + count) of each row's [C][W] plane move to
+// [0, count); count == 0 or shift == 0: the row is left alone
+extern "C" int umoe_dac_shift_rows(const int64_t* host, const int64_t* table, int rows, int C, umoe_stream_t stream) {
+    const char* who = "umoe_dac_shift_rows";
+    UMOE_REQUIRE(host && table && rows > 0 && rows <= 65535 && C > 0, "%s: bad argument", who);
+    UMOE_REQUIRE(((size_t)table & 7) == 0, "%s: the device table must be 8-byte aligned", who);
+    bool any = false;
+    for (int r = 0; r < rows; ++r) {
+        const int64_t* d = host + (size_t)r * UMOE_SHIFT_ROW_WORDS;
+        UMOE_REQUIRE(dac_word_is_int(d[1]) && dac_word_is_int(d[2]) && dac_word_is_int(d[3]), "%s: row %d has a word that is not a non-negative int", who, r);
+        if (d[3] == 0 || d[2] == 0) continue;
+        UMOE_REQUIRE(d[0], "%s: row %d has a null plane", who, r);
+        UMOE_REQUIRE(d[2] + d[3] <= d[1], "%s: row %d moves columns [%lld, %lld) of a plane %lld wide", who, r, (long long)d[2],
+                     (long long)(d[2] + d[3]), (long long)d[1]);
+        any = true;
+    }
+    if (!any) return 0;
+    dac_shift_rows_kernel<<<dim3((unsigned)ceil_div(C, 16), (unsigned)rows), 256, 0, (hipStream_t)stream>>>(table, C);
     UMOE_LAUNCH_CHECK();
     return 0;
 }

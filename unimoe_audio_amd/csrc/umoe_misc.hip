@@ -969,6 +969,52 @@ extern "C" int umoe_rvq_from_delayed(const int32_t* tokens, int B, int Tmax, int
     return 0;
 }
 
+// from_delayed with a record per z row (umoe.h "Per-row window tables", UMOE_RVQ_ROW_WORDS words): {token row, f0, n, t_valid, z plane
+// [Dl][Lz], column of frame f0, Lz}.  The sums are rvq_sum's, so a frame's latents are those of umoe_rvq_from_delayed bit for bit.
+__global__ __launch_bounds__(256) void rvq_from_delayed_rows_kernel(const int32_t* __restrict__ tokens, int Tmax, int NQ,
+                                                                    const int32_t* __restrict__ prefill_step, const int32_t* __restrict__ delay,
+                                                                    int pad, const int64_t* __restrict__ table, const float* __restrict__ cb,
+                                                                    const float* __restrict__ ow, const float* __restrict__ ob, int CB, int cd,
+                                                                    int Dl) {
+    const int64_t* r = table + (size_t)blockIdx.y * UMOE_RVQ_ROW_WORDS;
+    const int row = (int)r[0], f0 = (int)r[1], n = (int)r[2], t_valid = (int)r[3], z_off = (int)r[5], Lz = (int)r[6];
+    if ((int)blockIdx.x >= n) return;
+    const int t = f0 + blockIdx.x;
+    const int32_t* tb = tokens + (size_t)row * Tmax * NQ;
+    const int p0 = prefill_step[row] + t;
+    float* zr = reinterpret_cast<float*>(r[4]) + (t - f0 + z_off);
+    for (int d = threadIdx.x; d < Dl; d += blockDim.x)
+        zr[(size_t)d * Lz] = rvq_sum(cb, ow, ob, NQ, CB, cd, Dl, d, [&](int q) {
+            const int p = p0 + delay[q];
+            return (p >= 0 && p < t_valid) ? tb[(size_t)p * NQ + q] : pad;
+        });
+}
+
+extern "C" int umoe_rvq_from_delayed_rows(const int32_t* tokens, int B, int Tmax, int NQ, const int32_t* prefill_step, const int32_t* delay,
+                                          int pad, const int64_t* host, const int64_t* table, int rows, int max_n, const float* codebooks,
+                                          const float* out_w, const float* out_b, int CB, int cd, int Dl, umoe_stream_t stream) {
+    const char* who = "umoe_rvq_from_delayed_rows";
+    UMOE_REQUIRE(tokens && prefill_step && delay && codebooks && out_w && host && table && B > 0 && Tmax > 0 && NQ > 0 && CB > 0 && cd > 0 &&
+                 Dl > 0 && rows > 0 && rows <= 65535 && max_n >= 0, "%s: bad argument", who);
+    UMOE_REQUIRE(((size_t)table & 7) == 0, "%s: the device table must be 8-byte aligned", who);
+    for (int r = 0; r < rows; ++r) {
+        const int64_t* d = host + (size_t)r * UMOE_RVQ_ROW_WORDS;
+        UMOE_REQUIRE(d[2] >= 0 && d[2] <= max_n, "%s: row %d has n = %lld, max_n is %d", who, r, (long long)d[2], max_n);
+        if (d[2] == 0) continue;
+        UMOE_REQUIRE(d[0] >= 0 && d[0] < B, "%s: row %d reads token row %lld of %d", who, r, (long long)d[0], B);
+        UMOE_REQUIRE(d[1] >= 0 && d[1] + d[2] <= 0x7fffffffLL && d[3] >= 0 && d[3] <= Tmax, "%s: row %d: frames [%lld, %lld), t_valid %lld of %d", who, r,
+                     (long long)d[1], (long long)(d[1] + d[2]), (long long)d[3], Tmax);
+        UMOE_REQUIRE(d[4], "%s: row %d has a null plane", who, r);
+        UMOE_REQUIRE(d[5] >= 0 && d[6] <= 0x7fffffffLL && d[5] + d[2] <= d[6], "%s: row %d: %lld frames at column %lld of a %lld-column plane", who, r,
+                     (long long)d[2], (long long)d[5], (long long)d[6]);
+    }
+    if (max_n == 0) return 0;
+    rvq_from_delayed_rows_kernel<<<dim3((unsigned)max_n, (unsigned)rows), 256, 0, (hipStream_t)stream>>>(tokens, Tmax, NQ, prefill_step, delay, pad,
+                                                                                                       table, codebooks, out_w, out_b, CB, cd, Dl);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
 // nearest: per level q: e = in_proj_q(resid) [cd]; code = argmax_j <normalize(e), normalize(cb_j)> (== arg-min of the
 // L2 distance between the normalised vectors; ties: lowest index); resid -= out_proj_q(cb[code]).
 // One workgroup per frame t; resid_ws [T][Dl] fp32 scratch.  z [Dl][T].

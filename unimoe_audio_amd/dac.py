@@ -17,7 +17,7 @@ import ctypes as C
 import math
 import os
 import wave
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -719,3 +719,320 @@ class DelayedTokenSource:
         _lib_call("umoe_rvq_from_delayed", C.c_void_p(eng.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(self.prefill.data_ptr()),
                   C.c_void_p(self.delay.data_ptr()), int(self.t_valid), self.pad, C.c_void_p(self._rows[key].data_ptr()), len(rows), f0, n,
                   _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2], ow.shape[1], _dev_f32(out), col, out.shape[2], _stream())
+
+
+# ----------------------------------------------------------------------------------------------- one timeline per row
+# A served batch (UniMoEAudio.serve) admits every request at a poll of its own, so R live rows are on up to R timelines and
+# DacStreamDecoder would part them into R groups: R launches per layer and read, each filling a small part of the GPU.
+# DacRowStreamDecoder keeps the same schedule PER ROW (have / keep / base / L per layer, from the same StreamPlan) over slabs
+# [slots][C][W] and hands every layer the windows of all rows at once: umoe_dac_conv1d_win_rows / umoe_dac_conv_transpose1d_win_rows
+# read each row's window from a table (umoe.h "Per-row window tables"), one launch per layer whatever the rows are doing.
+
+DAC_ROW_FIELDS = ("x", "resid", "y", "x_off", "Lx", "r_off", "Lr", "y_off", "Ly", "t_begin", "n", "L")      # umoe.h UMOE_DAC_ROW_WORDS
+RVQ_ROW_FIELDS = ("row", "f0", "n", "t_valid", "z", "col", "Lz", "reserved")                                  # UMOE_RVQ_ROW_WORDS
+SHIFT_ROW_FIELDS = ("plane", "W", "shift", "count")                                                           # UMOE_SHIFT_ROW_WORDS
+
+
+def dac_row_words(x=0, resid=0, y=0, x_off=0, Lx=0, r_off=0, Lr=0, y_off=0, Ly=0, t_begin=0, n=0, L=0) -> List[int]:
+    """one row of a window table, in the word order of umoe.h (a row that is all zeros is idle: n = 0)"""
+    v = dict(x=x, resid=resid, y=y, x_off=x_off, Lx=Lx, r_off=r_off, Lr=Lr, y_off=y_off, Ly=Ly, t_begin=t_begin, n=n, L=L)
+    return [int(v[k]) for k in DAC_ROW_FIELDS]
+
+
+class RowWindow(NamedTuple):
+    """outputs [t0, t0 + n) of one layer for the row in `slot`; buffer positions as DacStreamDecoder._conv takes them"""
+    slot: int
+    x_off: int
+    L_true: int
+    t0: int
+    n: int
+    r_off: int
+    y_off: int
+
+
+class _Row:
+    """the timeline of one slot: buffer i holds positions [base[i], have[i]) of layer i's input in columns [0, have - base) of its plane"""
+
+    def __init__(self, n_buf):
+        self.have = [0] * (n_buf + 1)
+        self.keep = [0] * n_buf
+        self.base = [0] * n_buf
+        self.L = None
+        self.samples = 0
+        self.closed = False
+
+
+class DacRowStreamDecoder:
+    """DacStreamDecoder with one timeline per row, for rows that come and go (UniMoEAudio.serve(stream=True)).
+    push(n_new): how many more latent frames each of the `slots` rows has -> {row: new samples}; flush(rows, min_duration): the true
+    right edge and Dac.decode's pad; reset(row): a flushed row starts over at frame 0 for the next request.  For any schedule a row's
+    samples between two resets are bit-identical to DacModel.decode of its frames.
+    `source(requests, slab)`: requests = [(row, f0, n, col)], writes latent frames [f0, f0 + n) of each row into slab[row, :, col:col + n]
+    (slab [slots, Dl, W]); a source with a `table_words` attribute is given its slice of the read's table instead (DelayedRowsSource).
+    `max_frames`: the most frames a push brings per row (the slabs are sized for it; a larger push still works, a slab then grows).
+    ragged=True: per layer ONE library call for all rows (the table kernels); the number of calls in a push is 1 + buffers + layers,
+    whatever the rows do.  ragged=False, the yardstick: the same bookkeeping, one umoe_dac_*_win call per (layer, row with news).
+    All work is queued on the current stream."""
+
+    def __init__(self, model: DacModel, slots: int, source, max_frames: int = 25, ragged: bool = True, dtype=torch.float32, device=None):
+        self.model, self.slots, self.source, self.ragged = model, int(slots), source, bool(ragged)
+        self.plan = stream_plan(model)
+        self.dtype = dtype
+        self.device = device if device is not None else next(model.parameters()).device
+        lys = self.plan.layers
+        self.rows = [_Row(len(lys)) for _ in range(self.slots)]
+        per_frame, self.chan = [1], [lys[0].cin]
+        for ly in lys[:-1]:
+            per_frame.append(per_frame[-1] * (ly.stride if ly.kind == "convt" else 1))
+            self.chan.append(ly.cout)
+        room = int(max_frames) + self.plan.lookahead_frames + 2
+        self.bufs = [self._empty(self.slots, c, p * room + 64) for c, p in zip(self.chan, per_frame)]
+        self.grown = 0
+        self.last_plan = None          # what the last push / flush asked of the executor (tests, measurements)
+
+    def _empty(self, *shape):
+        return torch.empty(shape, dtype=self.dtype, device=self.device)
+
+    # ---- bookkeeping: DacStreamDecoder._advance for one row, recording the work instead of doing it ---------------------------
+    def _room(self, work, r: int, i: int, n: int) -> int:
+        """room for n more positions behind have in buffer i of row r: the kept left context [keep, have) moves to column 0 (recorded, one
+        launch per buffer later); returns the column of position have"""
+        st = self.rows[r]
+        kept, shift = st.have[i] - st.keep[i], st.keep[i] - st.base[i]
+        if shift:
+            work["shift"][i].append((r, shift, kept))
+            st.base[i] = st.keep[i]
+        if kept + n > self.bufs[i].shape[2]:
+            old = self.bufs[i]
+            self.bufs[i] = self._empty(old.shape[0], old.shape[1], 2 * (kept + n))
+            self.bufs[i][:, :, :old.shape[2]] = old
+            self.grown += 1
+        return kept
+
+    def _advance(self, work, r: int, n_new: int, final: bool):
+        P, st = self.plan, self.rows[r]
+        lys = P.layers
+        if n_new:
+            col = self._room(work, r, 0, n_new)
+            work["src"].append((r, st.have[0], n_new, col))
+            st.have[0] += n_new
+        if final:
+            st.L = [st.have[0]]
+            for ly in lys:
+                st.L.append(ly.out_len(st.L[-1]))
+        for i, ly in enumerate(lys):
+            target = st.L[i + 1] if final else ly.ready(st.have[i])
+            if ly.res is not None:
+                target = min(target, st.have[ly.res])
+            n = target - st.have[i + 1]
+            if n <= 0:
+                continue
+            t0 = st.have[i + 1]
+            y_off = t0 if i + 1 == len(lys) else t0 - self._room(work, r, i + 1, n)
+            r_off = st.base[ly.res] if ly.res is not None else 0
+            work["conv"][i].append(RowWindow(r, st.base[i], st.L[i] if final else _OPEN, t0, n, r_off, y_off))
+            st.have[i + 1] = target
+        # left context: what the next window of each reader of buffer i starts at
+        for i, ly in enumerate(lys):
+            need = max(0, ly.reads(st.have[i + 1], st.have[i + 1] + 1)[0])
+            for j, lj in enumerate(lys):
+                if lj.res == i:
+                    need = min(need, st.have[j + 1])
+            st.keep[i] = max(st.keep[i], min(need, st.have[i]))
+
+    # ---- executors ------------------------------------------------------------------------------------------------------------
+    def _conv(self, ly: StreamLayer, x, x_off, L_true, t0, n, resid, r_off, y, y_off):
+        """one window of one row through the _win entry (the grouped executor; the test suite swaps in a float64 restatement)"""
+        DacStreamDecoder._conv(self, ly, x, x_off, L_true, t0, n, resid, r_off, y, y_off)
+
+    def _planes(self, i: int, w: RowWindow, wave):
+        """(x, resid, y) of a window of layer i, each the [1, C, W] plane of the row's slot"""
+        ly = self.plan.layers[i]
+        s = slice(w.slot, w.slot + 1)
+        y = wave[s] if i + 1 == len(self.plan.layers) else self.bufs[i + 1][s]
+        return self.bufs[i][s], (self.bufs[ly.res][s] if ly.res is not None else None), y
+
+    def _shift(self, i: int, moves, table=None):
+        """buffer i: per (row, shift, count) the columns [shift, shift + count) of the row's plane move to [0, count), one launch for all"""
+        buf = self.bufs[i]
+        if table is None:
+            host = torch.zeros((self.slots, len(SHIFT_ROW_FIELDS)), dtype=torch.int64)
+            for r, shift, count in moves:
+                host[r] = torch.tensor([buf[r].data_ptr(), buf.shape[2], shift, count])
+            table = (host, host.to(self.device))
+        host, dev = table
+        _lib_call("umoe_dac_shift_rows", C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, buf.shape[1], _stream())
+
+    def _conv_rows(self, i: int, wins: List[RowWindow], wave, table):
+        """layer i: the windows of all rows in one launch; table = (host [slots, 12], its device copy)"""
+        ly = self.plan.layers[i]
+        f = self.model._folded()
+        w, b = f[ly.mod]
+        a = f[ly.snake] if ly.snake is not None else None
+        host, dev = table
+        max_n = max((v.n for v in wins), default=0)
+        if ly.kind == "conv":
+            _lib_call("umoe_dac_conv1d_win_rows", C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n, _dev_f32(w),
+                      _dev_f32(b), _dev_f32(a), ly.cin, ly.cout, ly.K, ly.stride, ly.dil, ly.pad, int(ly.tanh), _stream())
+        else:
+            _lib_call("umoe_dac_conv_transpose1d_win_rows", C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n,
+                      _dev_f32(w), _dev_f32(b), _dev_f32(a), ly.cin, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, _stream())
+
+    def _tables(self, work, wave):
+        """Every table of a read in one int64 tensor [source rows | per buffer the moves | per layer the windows], `slots` rows each (a
+        row without news is all zeros: idle), and ONE copy to the device.  -> (host, device) views per section"""
+        lys, S = self.plan.layers, self.slots
+        nw = getattr(self.source, "table_words", 0)
+        ns, nc = len(SHIFT_ROW_FIELDS), len(DAC_ROW_FIELDS)
+        host = torch.zeros(S * (nw + ns * len(self.bufs) + nc * len(lys)), dtype=torch.int64)
+        o = S * nw
+        shift_at, conv_at = [], []
+        for i, buf in enumerate(self.bufs):
+            sec = host[o:o + S * ns].view(S, ns)
+            for r, shift, count in work["shift"][i]:
+                sec[r] = torch.tensor([buf[r].data_ptr(), buf.shape[2], shift, count])
+            shift_at.append(o)
+            o += S * ns
+        for i, ly in enumerate(lys):
+            sec = host[o:o + S * nc].view(S, nc)
+            for v in work["conv"][i]:
+                x, resid, y = self._planes(i, v, wave)
+                sec[v.slot] = torch.tensor(dac_row_words(x=x.data_ptr(), resid=0 if resid is None else resid.data_ptr(), y=y.data_ptr(),
+                                                         x_off=v.x_off, Lx=x.shape[2], r_off=v.r_off, Lr=0 if resid is None else resid.shape[2],
+                                                         y_off=v.y_off, Ly=y.shape[2], t_begin=v.t0, n=v.n, L=v.L_true))
+            conv_at.append(o)
+            o += S * nc
+        if nw:
+            self.source.fill_table(host[:S * nw].view(S, nw), work["src"], self.bufs[0])
+        dev = self._upload(host)
+        cut = lambda at, n: (host[at:at + S * n].view(S, n), dev[at:at + S * n].view(S, n))      # noqa: E731
+        return cut(0, nw) if nw else None, [cut(at, ns) for at in shift_at], [cut(at, nc) for at in conv_at]
+
+    def _upload(self, host: torch.Tensor) -> torch.Tensor:
+        return host.to(self.device)
+
+    def _execute(self, work, wave):
+        lys = self.plan.layers
+        if self.ragged:
+            src_t, shift_t, conv_t = self._tables(work, wave)
+            for i in range(len(self.bufs)):          # (the moves first: new frames and outputs land behind the moved context)
+                self._shift(i, work["shift"][i], shift_t[i])
+            if src_t is not None:
+                self.source.run_table(src_t, work["src"], self.bufs[0])
+            elif work["src"]:
+                self.source(work["src"], self.bufs[0])
+            for i in range(len(lys)):
+                self._conv_rows(i, work["conv"][i], wave, conv_t[i])
+            return
+        # the yardstick: moves first (as above, one launch per buffer that has any), then per layer one _win call per row with news
+        for i in range(len(self.bufs)):
+            if work["shift"][i]:
+                self._shift(i, work["shift"][i])
+        if work["src"]:
+            self.source(work["src"], self.bufs[0])
+        for i, ly in enumerate(lys):
+            for v in work["conv"][i]:
+                x, resid, y = self._planes(i, v, wave)
+                self._conv(ly, x, v.x_off, v.L_true, v.t0, v.n, resid, v.r_off, y, v.y_off)
+
+    def _run(self, todo, final: bool, pads=None) -> dict:
+        """todo: {row: n_new}; plans every row, executes once, -> {row: samples}"""
+        lys = self.plan.layers
+        work = {"src": [], "shift": [[] for _ in self.bufs], "conv": [[] for _ in lys]}
+        before = {r: self.rows[r].have[-1] for r in todo}
+        for r, n in todo.items():
+            self._advance(work, r, n, final)
+        got = {r: self.rows[r].have[-1] - before[r] for r in todo}
+        # the waveform of this call: plane r holds row r's new samples from column 0, then (flush) its zero pad
+        width = max((got[r] + (pads[r] if pads else 0) for r in todo), default=0)
+        wave = (torch.zeros if pads else torch.empty)((self.slots, 1, max(width, 1)), dtype=self.dtype, device=self.device)
+        self.last_plan = work
+        self._execute(work, wave)
+        return {r: wave[r, 0, :got[r] + (pads[r] if pads else 0)] for r in todo}
+
+    def push(self, n_new) -> dict:
+        """n_new: more latent frames per row (`slots` ints; 0: the row is idle in this push) -> {row: new samples (1-D tensor)} for
+        the rows with frames"""
+        n_new = [int(v) for v in n_new]
+        assert len(n_new) == self.slots and min(n_new) >= 0
+        for r, n in enumerate(n_new):
+            if n and self.rows[r].closed:
+                raise ValueError(f"row {r} was flushed already (reset it for the next request)")
+        out = self._run({r: n for r, n in enumerate(n_new) if n}, False)
+        for r, a in out.items():
+            self.rows[r].samples += a.shape[0]
+        return out
+
+    def flush(self, rows, min_duration=None) -> dict:
+        """The rest of each row's waveform: the true right edge (a decode of T frames has plan.out_len(T) samples), then the zero pad
+        Dac.decode appends when the audio is shorter than min_duration seconds -> {row: samples (1-D tensor)}"""
+        rows = [rows] if isinstance(rows, int) else list(rows)
+        sr = self.model.sample_rate
+        pads = {}
+        for r in rows:
+            st = self.rows[r]
+            if st.closed:
+                raise ValueError(f"row {r} was flushed already")
+            duration = self.plan.out_len(st.have[0]) / sr if st.have[0] else 0.0
+            pads[r] = int((min_duration - duration) * sr) if min_duration is not None and duration < min_duration else 0      # Dac.decode
+        out = self._run({r: 0 for r in rows}, True, pads)
+        for r, a in out.items():
+            self.rows[r].samples += a.shape[0]
+            self.rows[r].closed = True
+        return out
+
+    def reset(self, row: int):
+        """row `row` (flushed, or never used) starts over: the next push is frame 0 of a new sequence"""
+        self.rows[row] = _Row(len(self.plan.layers))
+
+
+class DelayedRowsSource:
+    """DelayedTokenSource for DacRowStreamDecoder: every row reads the token buffer on its own clock.  t_valid[row] (the row's local
+    step + 1 at the last state read, serve.final_frames): token positions at or past it read as the pad code.  Under the ragged
+    executor the requests of a read are one table section and one umoe_rvq_from_delayed_rows launch; called directly (the grouped
+    executor) it is one umoe_rvq_from_delayed per row."""
+    table_words = len(RVQ_ROW_FIELDS)
+
+    def __init__(self, engine, model: DacModel):
+        cfg = engine.cfg
+        self.engine, self.model = engine, model
+        if engine.tokens.shape[2] > model.n_codebooks:
+            raise L.UmoeError(f"{engine.tokens.shape[2]} codec channels, the DAC has {model.n_codebooks} codebooks")
+        self.pad = int(cfg.codec_pad_value)
+        dev = engine.tokens.device
+        self.delay = torch.tensor(list(cfg.codec_delay_pattern), dtype=torch.int32, device=dev)
+        self.t_valid = [0] * engine.tokens.shape[0]
+        self._row_ids = torch.arange(engine.tokens.shape[0], dtype=torch.int32, device=dev)
+
+    def _weights(self):
+        f, NQ = self.model._folded(), self.engine.tokens.shape[2]
+        return f["cb"][:NQ].contiguous(), f["out_w"][:NQ].contiguous(), f["out_b"][:NQ].contiguous()
+
+    def _prefill(self):
+        """the rows' prefill steps on the device: words [3B, 4B) of the engine's state, which admissions keep current"""
+        B = self.engine.tokens.shape[0]
+        return self.engine.state[3 * B:4 * B]
+
+    def fill_table(self, sec: torch.Tensor, requests, slab: torch.Tensor):
+        for row, f0, n, col in requests:
+            sec[row] = torch.tensor([row, f0, n, self.t_valid[row], slab[row].data_ptr(), col, slab.shape[2], 0])
+
+    def run_table(self, table, requests, slab: torch.Tensor):
+        host, dev = table
+        eng = self.engine
+        B, Tmax, NQ = eng.tokens.shape
+        cb, ow, ob = self._weights()
+        _lib_call("umoe_rvq_from_delayed_rows", C.c_void_p(eng.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(self._prefill().data_ptr()),
+                  C.c_void_p(self.delay.data_ptr()), self.pad, C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), host.shape[0],
+                  max((n for _, _, n, _ in requests), default=0), _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2],
+                  ow.shape[1], _stream())
+
+    def __call__(self, requests, slab: torch.Tensor):
+        eng = self.engine
+        B, Tmax, NQ = eng.tokens.shape
+        cb, ow, ob = self._weights()
+        for row, f0, n, col in requests:
+            _lib_call("umoe_rvq_from_delayed", C.c_void_p(eng.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(self._prefill().data_ptr()),
+                      C.c_void_p(self.delay.data_ptr()), int(self.t_valid[row]), self.pad, C.c_void_p(self._row_ids[row:].data_ptr()), 1, f0, n,
+                      _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2], ow.shape[1], _dev_f32(slab[row]), col, slab.shape[2],
+                      _stream())

@@ -1107,6 +1107,18 @@ class DecodeEngine:
             raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 selects the launch-per-kernel path")
         return st
 
+    def poll_clock(self):
+        """poll() with the clock table: (state words, clock [B, 2] = {step_off, t_prompt} per row), both from ONE synchronising read, so
+        a row's local step (state[4B] - step_off) is that of the same moment as its countdown (serve.final_frames)"""
+        if self.row_clock is None:
+            raise L.UmoeError("poll_clock: the batch has no per-row clocks (start_serving / use_row_clock first)")
+        n = self.state.numel()
+        both = torch.cat((self.state, self.row_clock.reshape(-1))).cpu()
+        code = self.handoff_error()
+        if code:
+            raise L.UmoeError(f"decode engine: an in-launch hand-off timed out (code {code}); UMOE_FLAT_MOE=0 UMOE_FUSE_CQ=0 selects the launch-per-kernel path")
+        return both[:n], both[n:].reshape(-1, 2)
+
     def row_done(self, state_cpu: torch.Tensor, b: int) -> bool:
         """row b has ended (or was never used): its countdown is 0, so it is parked"""
         return int(state_cpu[self.batch + b]) == 0

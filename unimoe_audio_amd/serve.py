@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import weakref
 from collections import OrderedDict, deque
-from typing import Any, Callable, Deque, Dict, Iterable, Iterator, List, Tuple
+from typing import Any, Callable, Deque, Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 MAX_SLOTS = 8          # the default ceiling: the rows of the 16-row decode step
 MAX_SLOTS_WIDE = 32    # the most a caller may raise it to: the rows of the wide decode step
@@ -52,9 +52,12 @@ class Scheduler:
             self.live[row] = index
             self.admitted.append((index, row, self.steps_run))
 
-    def run(self, requests: Iterable[Any]) -> Iterator[Tuple[int, Any]]:
+    def run(self, requests: Iterable[Any], hook: Optional[Callable[[Any], Optional[Iterable[Any]]]] = None) -> Iterator[Tuple[int, Any]]:
         """Serves every request of `requests` (any iterable, read lazily: one request ahead of the free rows) and yields
-        (index, result) as each ends, index = the request's position in `requests`."""
+        (index, result) as each ends, index = the request's position in `requests`.
+        hook(state), when given, runs at every poll: behind poll(), before any take() of that poll and before the next admission, so
+        whatever it reads of a row that has ended (its last frames in the token buffer) is still the ended request's.  What it returns
+        (an iterable, or None) is yielded as it is, ahead of the poll's ended requests."""
         source = iter(enumerate(requests))
         while True:
             self._admit_free_rows(source)
@@ -63,6 +66,8 @@ class Scheduler:
             self.engine.steps(self.poll_every)
             self.steps_run += self.poll_every
             state = self.engine.poll()
+            if hook is not None:
+                yield from hook(state) or ()
             for row in sorted(self.live):
                 if self.engine.row_done(state, row):
                     index = self.live.pop(row)
@@ -70,6 +75,39 @@ class Scheduler:
                     self.free.append(row)
                     self.free.sort()
                     yield index, result
+
+
+class RowFrames(NamedTuple):
+    """What one state read makes final in one live row: frames [f0, f1) are new, `complete`: the request has ended and f1 is its
+    length, `t_valid`: the token positions of the row written so far (umoe_rvq_from_delayed reads the rest as pad)."""
+    row: int
+    f0: int
+    f1: int
+    complete: bool
+    t_valid: int
+
+
+def final_frames(state: Sequence[int], clock: Sequence[Sequence[int]], prefill_steps: Sequence[int], max_delay: int,
+                 emitted: Dict[int, int]) -> List[RowFrames]:
+    """DecodeEngine.run_stream's rule on per-row clocks.  state: the engine's state words (eos_detected[B], countdown[B], finished[B],
+    prefill_step[B], step, ...), clock: {step_off, t_prompt} per row, both of ONE read; emitted: {row: frames handed out so far} of the
+    rows that hold a request.  Row b lives at the local step d = step - step_off[b] and has written token positions [0, d + 1):
+    frame t is final once its most delayed channel is written, d >= prefill_step + t + max_delay, and it lies before the row's
+    length.  A row whose countdown is 0 has ended: its length is finished - prefill_step (DecodeEngine.take), all of it final, and
+    it wrote positions up to finished + max_delay.  One record per row of `emitted`, in row order."""
+    B = len(prefill_steps)
+    step = int(state[4 * B])
+    out = []
+    for b in sorted(emitted):
+        d = step - int(clock[b][0])
+        fin, ps = int(state[2 * B + b]), int(prefill_steps[b])
+        length = None if fin == -1 else max(fin - ps, 0)
+        complete = int(state[B + b]) == 0 and length is not None
+        f1 = max(d + 1 - max_delay - ps, 0)
+        if length is not None:
+            f1 = length if complete else min(f1, length)
+        out.append(RowFrames(b, int(emitted[b]), max(f1, int(emitted[b])), complete, fin + max_delay if complete else d + 1))
+    return out
 
 
 class VoicePrompt:
