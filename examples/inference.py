@@ -13,12 +13,12 @@ _MODEL = None
 
 
 def inference(task, input_text, model_path, ref_audio=None, ref_text=None, video=None, output="./output", device=0, reuse=True,
-              expert_weights="bf16", stream=False):
+              expert_weights="bf16", stream=False, dac_conv="direct"):
     global _MODEL
     from unimoe_audio_amd.api import UniMoEAudio
     try:
         if _MODEL is None or not reuse:
-            _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights)
+            _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights, dac_conv=dac_conv)
         if stream:
             return _stream(_MODEL, task, input_text, ref_audio, ref_text, video, output)
         if task == "text_to_speech":
@@ -50,13 +50,13 @@ def load_requests(path):
 
 
 def batch_inference(requests_file, model_path, output="./output", device=0, reuse=True, expert_weights="bf16", stream=False, serve=False,
-                    slots=8, prefix_cache=False):
+                    slots=8, prefix_cache=False, dac_conv="direct"):
     global _MODEL
     from unimoe_audio_amd.api import UniMoEAudio
     try:
         reqs = load_requests(requests_file)
         if _MODEL is None or not reuse:
-            _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights)
+            _MODEL = UniMoEAudio(model_path, device, expert_weights=expert_weights, dac_conv=dac_conv)
         if serve:
             # continuous batching: `slots` rows decode together, a request takes a row as soon as one is free
             import time
@@ -126,6 +126,8 @@ def main():
                     help="fp8: weight-only e4m3 expert weights in the decode engine (half the expert bytes per step; with --serve at every --slots 1..32); "
                          "fp8-only: the same and the bf16 expert weights are released (5.5 GB of experts instead of 27 GB, prefill on the e4m3 copies); "
                          "w12-only: the bf16 expert weights are released in favour of their lossless 12-bit copies (no result changes by a bit; prefill on the copies)")
+    ap.add_argument("--dac-conv", choices=["direct", "mfma"], default="direct",
+                    help="mfma: the codec's convolutions on the f32 matrix cores (exact fp32, another summation order: the last bits of a waveform differ)")
     ap.add_argument("--stream", action="store_true", help="stream the audio in chunks while the decode loop runs (prints each chunk's arrival)")
     ap.add_argument("--serve", action="store_true", help="with --requests: serve the list as a queue (UniMoEAudio.serve): --slots rows decode "
                                                          "together and a request is admitted as soon as a row is free; any number of requests")
@@ -136,12 +138,13 @@ def main():
     if a.requests:
         if a.prefix_cache and not a.serve:
             ap.error("--prefix-cache goes with --serve")
-        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream, a.serve, a.slots, a.prefix_cache)
+        out = batch_inference(a.requests, a.model, a.output, a.device, not a.no_reuse, a.expert_weights, a.stream, a.serve, a.slots, a.prefix_cache,
+                              a.dac_conv)
         sys.exit(0 if out else 1)
     if not a.task or a.input is None:
         ap.error("--task and --input are required (or --requests FILE.json)")
     out = inference(a.task, a.input, a.model, a.ref_audio, a.ref_text, a.video, a.output, a.device, not a.no_reuse, a.expert_weights,
-                    a.stream)
+                    a.stream, a.dac_conv)
     sys.exit(0 if out else 1)
 
 

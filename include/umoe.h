@@ -779,6 +779,33 @@ int umoe_dac_conv_transpose1d_win_rows(const int64_t* host, const int64_t* table
                                        const float* snake_alpha, int Cin, int Cout, int K, int stride, int pad, int out_pad,
                                        umoe_stream_t stream);
 int umoe_dac_shift_rows(const int64_t* host, const int64_t* table, int rows, int C, umoe_stream_t stream);
+/* The six convolution entries above on the f32-input MFMA (v_mfma_f32_16x16x4_f32; csrc/umoe_dac_mfma.hip): the argument list of the
+ * direct sibling with w replaced by wt, the k-major copy [Cin][K][Cout] of the folded weight (conv1d: w.permute(1, 2, 0); transposed:
+ * w.permute(0, 2, 1)).  Same function, same windows, same per-row tables (UMOE_DAC_ROW_WORDS, same words), same int64 window checks,
+ * same refusals by name with nothing written (bad arguments, an empty output); max_n == 0 and idle rows enqueue nothing.  fp32 in,
+ * fp32 accumulate: each output is an fmaf chain over (ci, k) ascending in steps of 4, so results differ from the direct kernels in
+ * the last bits and stay inside the same float64 bounds; among themselves the six are bit-identical per output position (the order
+ * never depends on the tile, window, row or batch index).  Grid (ceil(n / 64), ceil(Cout / 64), B or rows) for conv1d; the transposed
+ * form tiles 64 positions per phase, grid x = ceil(nq / 64) * stride with nq the values (t + pad) / stride takes over the window.
+ * Staging limit: none that depends on the geometry -- LDS is a fixed 20 480 bytes (two [32][80] fp32 images), so the direct
+ * kernels' "tile needs ... bytes of LDS" refusal has no counterpart; refused instead: Cin * taps beyond an int, and a grid beyond
+ * the launch limits (Cout > 64 * 65535, B > 65535). */
+int umoe_dac_conv1d_mfma(const float* x, const float* wt, const float* bias, const float* snake_alpha, const float* resid, int B, int Cin,
+                         int L, int Cout, int K, int stride, int dilation, int pad, int act, float* y, int* Lout_out, umoe_stream_t stream);
+int umoe_dac_conv_transpose1d_mfma(const float* x, const float* wt, const float* bias, const float* snake_alpha, int B, int Cin, int L,
+                                   int Cout, int K, int stride, int pad, int out_pad, float* y, int* Lout_out, umoe_stream_t stream);
+int umoe_dac_conv1d_win_mfma(const float* x, int x_off, int Lx, const float* wt, const float* bias, const float* snake_alpha,
+                             const float* resid, int r_off, int Lr, int B, int Cin, int L, int Cout, int K, int stride, int dilation, int pad,
+                             int act, int t_begin, int n, float* y, int y_off, int Ly, umoe_stream_t stream);
+int umoe_dac_conv_transpose1d_win_mfma(const float* x, int x_off, int Lx, const float* wt, const float* bias, const float* snake_alpha, int B,
+                                       int Cin, int L, int Cout, int K, int stride, int pad, int out_pad, int t_begin, int n, float* y,
+                                       int y_off, int Ly, umoe_stream_t stream);
+int umoe_dac_conv1d_win_rows_mfma(const int64_t* host, const int64_t* table, int rows, int max_n, const float* wt, const float* bias,
+                                  const float* snake_alpha, int Cin, int Cout, int K, int stride, int dilation, int pad, int act,
+                                  umoe_stream_t stream);
+int umoe_dac_conv_transpose1d_win_rows_mfma(const int64_t* host, const int64_t* table, int rows, int max_n, const float* wt,
+                                            const float* bias, const float* snake_alpha, int Cin, int Cout, int K, int stride, int pad,
+                                            int out_pad, umoe_stream_t stream);
 int umoe_rvq_from_delayed_rows(const int32_t* tokens, int B, int Tmax, int NQ, const int32_t* prefill_step, const int32_t* delay, int pad,
                                const int64_t* host, const int64_t* table, int rows, int max_n, const float* codebooks, const float* out_w,
                                const float* out_b, int CB, int cd, int Dl, umoe_stream_t stream);

@@ -11,7 +11,11 @@ runs, with the spread max - min), admission -> first chunk per request (median a
 calls per state read, and the makespan over the non-streamed leg's.  The ragged executor is judged against the grouped leg of the same
 process.  Writes profiles/serve_stream.json and prints it as one JSON line.
 
-    python scripts/serve_stream_bench.py [--slots 8,32] [--polls 16,25] [--runs 3] [--per-slot 3]
+--dac-conv mfma: the codec in conv_form="mfma" (DESIGN 4q).  --dac-conv both: the nonstream and ragged legs in BOTH forms, alternating in
+one process (legs nonstream_direct, ragged_direct, nonstream_mfma, ragged_mfma; no grouped leg), and per setting whether the MFMA
+form's DAC milliseconds per read beat the direct form's by more than the two spreads added.  Either writes profiles/serve_stream_mfma.json.
+
+    python scripts/serve_stream_bench.py [--slots 8,32] [--polls 16,25] [--runs 3] [--per-slot 3] [--dac-conv direct|mfma|both]
 """
 import argparse
 import json
@@ -69,7 +73,12 @@ def queue(n, seed):
 
 
 def run_leg(app, D, reqs, leg, slots, poll_every):
-    """one serving of the queue -> makespan, first-chunk latencies, DAC ms and library calls per read"""
+    """one serving of the queue -> makespan, first-chunk latencies, DAC ms and library calls per read.  leg: nonstream / ragged / grouped,
+    or one of them with the codec's form behind it (ragged_mfma)"""
+    leg, _, form = leg.partition("_")
+    if form:
+        app.dac.model.set_conv_form(form)
+        app.dac.model._folded()              # (the weights of this form, outside the timed span)
     kw = dict(slots=slots, poll_every=poll_every, max_prompt_tokens=256, max_audio_seconds=6)
     spans, calls, per_read_calls = [], [0], []
     lib_call, push, flush = D._lib_call, D.DacRowStreamDecoder.push, D.DacRowStreamDecoder.flush
@@ -129,8 +138,13 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--per-slot", type=int, default=3, help="requests in the queue per slot")
     ap.add_argument("--layers", type=int, default=0, help="debug only: override num_hidden_layers (0 = 36)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "serve_stream.json"))
+    ap.add_argument("--dac-conv", choices=["direct", "mfma", "both"], default="direct")
+    ap.add_argument("--out", default=None, help="default: profiles/serve_stream.json, or profiles/serve_stream_mfma.json with --dac-conv mfma / both")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "serve_stream.json" if args.dac_conv == "direct" else "serve_stream_mfma.json")
+    both = args.dac_conv == "both"
+    legs = ["nonstream_direct", "ragged_direct", "nonstream_mfma", "ragged_mfma"] if both else ["nonstream", "ragged", "grouped"]
     import bench
     from unimoe_audio_amd import dac as D
     from unimoe_audio_amd import serve as S
@@ -141,7 +155,8 @@ def main():
     if args.layers:
         cfg.num_hidden_layers = args.layers
     res = {"metric": "serve_stream", "dac": "16kHz random, decoder_dim 1536", "layers": cfg.num_hidden_layers, "runs": args.runs,
-           "queue": "music and speech, 2..6 s each (min = max), per_slot x slots requests", "per_slot": args.per_slot, "legs": {}}
+           "queue": "music and speech, 2..6 s each (min = max), per_slot x slots requests", "per_slot": args.per_slot, "dac_conv": args.dac_conv,
+           "legs": {}}
     # admission times of the streamed legs: Scheduler._admit_free_rows stamps them
     stamps = {}
     admit = S.Scheduler._admit_free_rows
@@ -161,19 +176,19 @@ def main():
             model.quantize_experts_("fp8")
         app = UniMoEAudio(None, 0, model=model)
         app._tokenizer = Tokenizer(cfg.codec_placeholder_value)
-        app.dac = D.Dac(model=D.DacModel(**D.DAC_16KHZ).init_random(0).to(dev).float())
+        app.dac = D.Dac(model=D.DacModel(**D.DAC_16KHZ).init_random(0).to(dev).float(), conv_form="direct" if both else args.dac_conv)
         reqs = queue(args.per_slot * slots, slots)
         for poll_every in [int(v) for v in args.polls.split(",")]:
             key = f"slots{slots}_{fmt}_poll{poll_every}"
             # warm-up: the engine, the graph capture, DAC weight folding and every kernel once per leg, on a short queue
-            for leg in ("nonstream", "ragged", "grouped"):
+            for leg in legs:
                 run_leg(app, D, reqs[:slots + 1], leg, slots, poll_every)
-            runs = {"nonstream": [], "ragged": [], "grouped": []}
+            runs = {leg: [] for leg in legs}
             for _ in range(args.runs):
                 for leg in runs:
                     stamps.clear()
                     r = run_leg(app, D, reqs, leg, slots, poll_every)
-                    if leg != "nonstream":
+                    if not leg.startswith("nonstream"):
                         lat = [r["first_at"][i] - stamps[i] for i in sorted(r["first_at"])]
                         r.update(first_chunk_median_s=statistics.median(lat), first_chunk_worst_s=max(lat))
                         del r["first_at"], r["t0"]
@@ -185,13 +200,24 @@ def main():
                 for k in rs[0]:
                     if k != "makespan_s":
                         out[leg][k] = round(statistics.median(r[k] for r in rs), 4)
-            base = out["nonstream"]["makespan_s"]
-            for leg in ("ragged", "grouped"):
-                out[leg]["makespan_over_nonstream"] = round(out[leg]["makespan_s"] / base, 4)
-            d = out["grouped"]["makespan_s"] - out["ragged"]["makespan_s"]
-            spread = max(out["grouped"]["makespan_spread_s"], out["ragged"]["makespan_spread_s"])
-            out["ragged_beats_grouped_by_s"] = round(d, 4)
-            out["beyond_spread"] = bool(d > spread)
+                if "dac_ms_per_read" in rs[0]:
+                    out[leg]["dac_ms_per_read_spread"] = round(max(r["dac_ms_per_read"] for r in rs) - min(r["dac_ms_per_read"] for r in rs), 4)
+            for leg in legs:
+                if not leg.startswith("nonstream"):
+                    base = out["nonstream" + leg.partition("_")[1] + leg.partition("_")[2]]["makespan_s"]
+                    out[leg]["makespan_over_nonstream"] = round(out[leg]["makespan_s"] / base, 4)
+            if both:
+                a, b = out["ragged_direct"], out["ragged_mfma"]
+                d = a["dac_ms_per_read"] - b["dac_ms_per_read"]
+                out["dac_ms_per_read_direct_over_mfma"] = round(a["dac_ms_per_read"] / b["dac_ms_per_read"], 3)
+                out["mfma_beats_direct_by_ms_per_read"] = round(d, 4)
+                out["beyond_spreads"] = bool(d > a["dac_ms_per_read_spread"] + b["dac_ms_per_read_spread"])
+                out["streamed_makespan_direct_over_mfma"] = round(a["makespan_s"] / b["makespan_s"], 4)
+            else:
+                d = out["grouped"]["makespan_s"] - out["ragged"]["makespan_s"]
+                spread = max(out["grouped"]["makespan_spread_s"], out["ragged"]["makespan_spread_s"])
+                out["ragged_beats_grouped_by_s"] = round(d, 4)
+                out["beyond_spread"] = bool(d > spread)
             out["requests"] = len(reqs)
             res["legs"][key] = out
             print(key, json.dumps(out), flush=True)

@@ -175,6 +175,8 @@ EXPORTS = [
     "umoe_kv_prefix_copy", "umoe_engine_prefix_build", "umoe_engine_admit_prefix",
     "umoe_engine_set_admit_dump",
     "umoe_dac_conv1d_win_rows", "umoe_dac_conv_transpose1d_win_rows", "umoe_dac_shift_rows", "umoe_rvq_from_delayed_rows",
+    "umoe_dac_conv1d_mfma", "umoe_dac_conv_transpose1d_mfma", "umoe_dac_conv1d_win_mfma", "umoe_dac_conv_transpose1d_win_mfma",
+    "umoe_dac_conv1d_win_rows_mfma", "umoe_dac_conv_transpose1d_win_rows_mfma",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -235,6 +237,11 @@ def lib():
         L.umoe_dac_conv1d_win_rows.argtypes = [vp, vp, i32, i32, vp, vp, vp] + [i32] * 7 + [vp]
         L.umoe_dac_conv_transpose1d_win_rows.argtypes = [vp, vp, i32, i32, vp, vp, vp] + [i32] * 6 + [vp]
         L.umoe_dac_shift_rows.argtypes = [vp, vp, i32, i32, vp]
+        if not hasattr(L, "umoe_dac_conv1d_mfma"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_dac_conv1d_mfma): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        for sfx in ("", "_win", "_win_rows"):          # the MFMA forms take their direct siblings' arguments (wt in the place of w)
+            for stem in ("umoe_dac_conv1d", "umoe_dac_conv_transpose1d"):
+                getattr(L, f"{stem}{sfx}_mfma").argtypes = getattr(L, stem + sfx).argtypes
         L.umoe_rvq_from_delayed_rows.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_rope.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_attn.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]

@@ -94,14 +94,21 @@ AUDIO_START = "<|AUDIO_START|>"
 
 class UniMoEAudio:
     def __init__(self, model_path: Optional[str], device_id: int = 0, config: Optional[UniMoEAudioConfig] = None,
-                 model: Optional[UniAudioRVQQwen2_5VLMoEForConditionalGeneration] = None, expert_weights: str = "bf16"):
+                 model: Optional[UniAudioRVQQwen2_5VLMoEForConditionalGeneration] = None, expert_weights: str = "bf16",
+                 dac_conv: str = "direct"):
         """expert_weights "fp8": weight-only fp8 (e4m3, one power-of-two scale per row) of the routed and shared experts
         (model.quantize_experts_): decode streams half the expert bytes, at every batch size from 1 to 32 requests; the whole model then
         computes with the dequantized weights.  "fp8-only": the same, and the bf16 expert parameters are released -- each expert as soon
         as it is loaded and quantized -- so the device holds the fp8 copy of every expert and nothing else (inference only: prefill runs
         on the fp8 copies too, the module forward / training / saving raise).  "w12-only": the bf16 expert parameters are released
         in favour of the LOSSLESS 12-bit copies that bf16 engines decode from anyway; prefill runs on them too and no bit of any result
-        changes (inference only, like fp8-only)."""
+        changes (inference only, like fp8-only).
+        dac_conv "mfma": the codec this object builds runs its convolutions on the f32 MFMA kernels (dac.Dac(conv_form=...)):
+        exact fp32 arithmetic in another summation order, so waveforms differ from "direct" in the last bits.  Everything that encodes or
+        decodes audio (text_to_*, their _stream twins, serve, voice) follows the codec; one assigned through `dac` keeps its own form."""
+        if dac_conv not in ("direct", "mfma"):
+            raise ValueError(f"dac_conv must be 'direct' or 'mfma' (got {dac_conv!r})")
+        self.dac_conv = dac_conv
         if expert_weights not in ("bf16", "fp8", "fp8-only", "w12-only"):
             raise ValueError(f"expert_weights must be 'bf16', 'fp8', 'fp8-only' or 'w12-only' (got {expert_weights!r})")
         if not torch.cuda.is_available():
@@ -160,7 +167,7 @@ class UniMoEAudio:
                     if os.path.isfile(p):
                         cand = p
                         break
-            self._dac = Dac(cand, device=self.device)
+            self._dac = Dac(cand, device=self.device, conv_form=self.dac_conv)
         return self._dac
 
     @dac.setter

@@ -10,6 +10,9 @@ dimension comes from the checkpoint's metadata or tensor shapes.  The arithmetic
 umoe_dac_conv_transpose1d with the preceding Snake fused, umoe_rvq_nearest, umoe_rvq_from_codes).  PARITY UNPINNED: `dac`,
 `audiotools` and `torchaudio` are absent offline, so the layers, the resampler (torchaudio's windowed-sinc formula) and the PCM
 conversion are restated from their published definitions; tests compare the kernels with plain fp32 torch restatements.
+Two forms of the convolutions (DacModel.conv_form, Dac(conv_form=...)): "direct", the fp32 VALU kernels and the default, and "mfma", the
+same layers as implicit GEMMs on the f32-input MFMA (umoe_dac_*_mfma on a k-major weight copy; exact fp32 in another summation order,
+DESIGN 4q).  uses_mfma() decides per layer shape, for the full, windowed and per-row calls alike.
 """
 from __future__ import annotations
 
@@ -38,9 +41,33 @@ def _dev_f32(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr())
 
 
+CONV_FORMS = ("direct", "mfma")
+
+
+def _check_form(form) -> str:
+    if form not in CONV_FORMS:
+        raise ValueError(f"conv form {form!r}: expected one of {CONV_FORMS}")
+    return form
+
+
+def uses_mfma(cin: int, cout: int, K: int, stride: int) -> bool:
+    """THE routing rule of conv_form="mfma": whether a layer of this shape runs on the f32 MFMA kernels (umoe_dac_*_mfma) or stays on the
+    direct ones.  Static in the layer's shape, and consulted by every call site (full, windowed, per-row), so all forms of one layer
+    agree and a model in "mfma" mode stays bit-identical between DacModel.decode and the streaming decoders."""
+    return True
+
+
+def kmajor(w: torch.Tensor, transposed: bool) -> torch.Tensor:
+    """the MFMA kernels' weight operand wt [Cin][K][Cout] from w [Cout][Cin][K] (conv1d) or [Cin][Cout][K] (transposed)"""
+    return (w.permute(0, 2, 1) if transposed else w.permute(1, 2, 0)).contiguous()
+
+
 def conv1d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, stride=1, dilation=1, padding=0,
-           snake_alpha: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, tanh: bool = False) -> torch.Tensor:
-    """y = [tanh](conv1d(snake?(x)) + bias) [+ resid]; x [B, Cin, L], w [Cout, Cin, K] (weight norm already folded)."""
+           snake_alpha: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, tanh: bool = False, form: str = "direct",
+           wt: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = [tanh](conv1d(snake?(x)) + bias) [+ resid]; x [B, Cin, L], w [Cout, Cin, K] (weight norm already folded).
+    form="mfma": the f32 MFMA kernel on wt = kmajor(w) (made here when the caller has none)."""
+    mfma = _check_form(form) == "mfma"
     B, Cin, Lx = x.shape
     Cout, Cin2, K = w.shape
     assert Cin2 == Cin
@@ -49,23 +76,30 @@ def conv1d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, st
     if resid is not None:
         assert tuple(resid.shape) == tuple(y.shape)
     lo = C.c_int()
-    L.check(L.lib().umoe_dac_conv1d(_dev_f32(x), _dev_f32(w), _dev_f32(bias), _dev_f32(snake_alpha), _dev_f32(resid), B, Cin, Lx, Cout, K,
-                                    stride, dilation, padding, int(tanh), _dev_f32(y), C.byref(lo), _stream()), "umoe_dac_conv1d")
+    name = "umoe_dac_conv1d_mfma" if mfma else "umoe_dac_conv1d"
+    if mfma and wt is None:
+        wt = kmajor(w, False)
+    _lib_call(name, _dev_f32(x), _dev_f32(wt if mfma else w), _dev_f32(bias), _dev_f32(snake_alpha), _dev_f32(resid), B, Cin, Lx, Cout, K,
+              stride, dilation, padding, int(tanh), _dev_f32(y), C.byref(lo), _stream())
     assert lo.value == Lout
     return y
 
 
 def conv_transpose1d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, stride, padding, output_padding=0,
-                     snake_alpha: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = conv_transpose1d(snake?(x)) + bias; x [B, Cin, L], w [Cin, Cout, K]."""
+                     snake_alpha: Optional[torch.Tensor] = None, form: str = "direct", wt: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = conv_transpose1d(snake?(x)) + bias; x [B, Cin, L], w [Cin, Cout, K].  form="mfma": as conv1d, wt = kmajor(w, True)."""
+    mfma = _check_form(form) == "mfma"
     B, Cin, Lx = x.shape
     Cin2, Cout, K = w.shape
     assert Cin2 == Cin
     Lout = (Lx - 1) * stride - 2 * padding + K + output_padding
     y = torch.empty((B, Cout, Lout), dtype=torch.float32, device=x.device)
     lo = C.c_int()
-    L.check(L.lib().umoe_dac_conv_transpose1d(_dev_f32(x), _dev_f32(w), _dev_f32(bias), _dev_f32(snake_alpha), B, Cin, Lx, Cout, K, stride,
-                                              padding, output_padding, _dev_f32(y), C.byref(lo), _stream()), "umoe_dac_conv_transpose1d")
+    name = "umoe_dac_conv_transpose1d_mfma" if mfma else "umoe_dac_conv_transpose1d"
+    if mfma and wt is None:
+        wt = kmajor(w, True)
+    _lib_call(name, _dev_f32(x), _dev_f32(wt if mfma else w), _dev_f32(bias), _dev_f32(snake_alpha), B, Cin, Lx, Cout, K, stride,
+              padding, output_padding, _dev_f32(y), C.byref(lo), _stream())
     assert lo.value == Lout
     return y
 
@@ -86,6 +120,12 @@ class _WN(nn.Module):
         self.weight_v = nn.Parameter(torch.zeros(shape))
         self.bias = nn.Parameter(torch.zeros(bias_n))
         self.geom = geom
+
+    def shape4(self):
+        """(cin, cout, K, stride): what dac.uses_mfma decides on"""
+        a, b, K = (int(v) for v in self.weight_v.shape)
+        cin, cout = (a, b) if self.geom["transposed"] else (b, a)
+        return cin, cout, K, int(self.geom["stride"])
 
     def folded(self) -> torch.Tensor:
         v = self.weight_v.data.float()
@@ -173,6 +213,13 @@ class DacModel(nn.Module):
         dec += [Snake1d(cout), WNConv1d(cout, 1, 7, padding=3), nn.Tanh()]
         self.decoder = _Seq("model", dec)
         self._fold = None
+        self.conv_form = "direct"
+
+    def set_conv_form(self, form: str) -> "DacModel":
+        """"direct": the fp32 VALU kernels (the default); "mfma": every layer that dac.uses_mfma names runs on the f32 MFMA kernels, in
+        encode, decode and the streaming decoders alike (one more fp32 copy of those layers' weights, k-major, made at the next use)."""
+        self.conv_form = _check_form(form)
+        return self
 
     # ---- weights ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -229,15 +276,20 @@ class DacModel(nn.Module):
 
     def _folded(self) -> dict:
         """weight norm folded once (g * v / |v|), keyed by module; the RVQ projections stacked for the RVQ kernels."""
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        key = (self.conv_form,) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._fold is not None and self._fold["key"] == key:
             return self._fold
-        f = {"key": key}
+        f = {"key": key, "wt": {}}
         for m in self.modules():
             if isinstance(m, _WN):
                 f[m] = (m.folded(), m.bias.data.float().contiguous())
             elif isinstance(m, Snake1d):
                 f[m] = m.alpha.data.float().reshape(-1).contiguous()
+        if self.conv_form == "mfma":          # the MFMA kernels' weight operand, for the conv stacks' layers that dac.uses_mfma names
+            for part in (self.encoder, self.decoder):
+                for m in part.modules():
+                    if isinstance(m, _WN) and uses_mfma(*m.shape4()):
+                        f["wt"][m] = kmajor(f[m][0], m.geom["transposed"])
         q = self.quantizer.quantizers
         f["cb"] = torch.stack([v.codebook.weight.data.float() for v in q], 0).contiguous()                      # [NQ, CB, cd]
         f["in_w"] = torch.stack([f[v.in_proj][0][:, :, 0] for v in q], 0).contiguous()                           # [NQ, cd, Dl]
@@ -247,26 +299,32 @@ class DacModel(nn.Module):
         self._fold = f
         return f
 
+    def _route(self, m: "_WN", f: dict):
+        """(form, weight operand) of conv m under this model's conv_form: the one place every call site asks"""
+        wt = f["wt"].get(m)
+        return ("mfma", wt) if wt is not None else ("direct", f[m][0])
+
     # ---- graph walk: Snake is always followed by a conv, into whose input load it is fused -------------------------------
+    def _conv(self, m: "_WN", x, f, **kw):
+        form, wsel = self._route(m, f)
+        g = m.geom
+        if g["transposed"]:
+            return conv_transpose1d(x, f[m][0], f[m][1], stride=g["stride"], padding=g["padding"], output_padding=g["output_padding"], form=form,
+                                    wt=wsel, **kw)
+        return conv1d(x, f[m][0], f[m][1], stride=g["stride"], dilation=g["dilation"], padding=g["padding"], form=form, wt=wsel, **kw)
+
     def _run(self, mods, x, f):
         alpha = None
         for m in mods:
             if isinstance(m, Snake1d):
                 alpha = f[m]
             elif isinstance(m, _WN):
-                w, b = f[m]
-                g = m.geom
-                if g["transposed"]:
-                    x = conv_transpose1d(x, w, b, stride=g["stride"], padding=g["padding"], output_padding=g["output_padding"], snake_alpha=alpha)
-                else:
-                    x = conv1d(x, w, b, stride=g["stride"], dilation=g["dilation"], padding=g["padding"], snake_alpha=alpha)
+                x = self._conv(m, x, f, snake_alpha=alpha)
                 alpha = None
             elif isinstance(m, _Seq) and len(m.items()) == 4 and isinstance(m.items()[0], Snake1d):      # ResidualUnit: x + block(x)
                 a0, c0, a1, c1 = m.items()
-                w0, b0 = f[c0]
-                w1, b1 = f[c1]
-                t = conv1d(x, w0, b0, dilation=c0.geom["dilation"], padding=c0.geom["padding"], snake_alpha=f[a0])
-                x = conv1d(t, w1, b1, snake_alpha=f[a1], resid=x)
+                t = self._conv(c0, x, f, snake_alpha=f[a0])
+                x = self._conv(c1, t, f, snake_alpha=f[a1], resid=x)
             elif isinstance(m, _Seq):
                 x = self._run(m.items(), x, f)
             elif isinstance(m, nn.Tanh):
@@ -305,8 +363,7 @@ class DacModel(nn.Module):
         mods = self.decoder.items()
         x = self._run(mods[:-3], z.float().contiguous(), f)
         snake, last = mods[-3], mods[-2]
-        w, b = f[last]
-        return conv1d(x, w, b, padding=last.geom["padding"], snake_alpha=f[snake], tanh=True)
+        return self._conv(last, x, f, snake_alpha=f[snake], tanh=True)
 
 
 # ----------------------------------------------------------------------------------------------- resampler / wav io
@@ -370,10 +427,14 @@ def write_wav_pcm16(path: str, audio_CxL: torch.Tensor, sample_rate: int):
 class Dac:
     """reference utils/UniMoE_Audio_utils.py:56-134 (same methods and error behaviour; no download offline)."""
 
-    def __init__(self, weights_path: Optional[str] = None, device="cuda", model: Optional[DacModel] = None):
+    def __init__(self, weights_path: Optional[str] = None, device="cuda", model: Optional[DacModel] = None, conv_form: Optional[str] = None):
+        """conv_form "direct" / "mfma": the form of the codec's convolutions (DacModel.set_conv_form).  None, the default: "direct" for
+        a model loaded here; a `model` handed in keeps the form it has."""
         self.resampler = dict()
+        if conv_form is not None:
+            _check_form(conv_form)
         if model is not None:
-            self.model = model
+            self.model = model if conv_form is None else model.set_conv_form(conv_form)
             return
         base_dir = os.path.dirname(__file__)
         candidates = [p for p in (weights_path, os.environ.get("DAC_WEIGHTS")) if p]
@@ -384,7 +445,11 @@ class Dac:
         if not final:
             raise FileNotFoundError("DAC weights not found. Please place weights_16khz.pth in one of the following locations or set "
                                     "DAC_WEIGHTS to an absolute path:" + "\n - " + "\n - ".join(candidates))
-        self.model = DacModel.load(final, device)
+        self.model = DacModel.load(final, device).set_conv_form(conv_form or "direct")
+
+    @property
+    def conv_form(self) -> str:
+        return self.model.conv_form
 
     @property
     def device(self):
@@ -560,16 +625,18 @@ class DacStreamDecoder:
     def _conv(self, ly: StreamLayer, x, x_off, L_true, t0, n, resid, r_off, y, y_off):
         """outputs [t0, t0 + n) of layer ly into y (positions [y_off, ...)); x / resid hold positions from x_off / r_off"""
         f = self.model._folded()
-        w, b = f[ly.mod]
+        b = f[ly.mod][1]
+        form, w = self.model._route(ly.mod, f)
+        sfx = "_mfma" if form == "mfma" else ""
         a = f[ly.snake] if ly.snake is not None else None
         assert x.shape[1] == ly.cin and y.shape[1] == ly.cout and y.shape[0] == x.shape[0]
         assert resid is None or (resid.shape[:2] == y.shape[:2])
         if ly.kind == "conv":
-            _lib_call("umoe_dac_conv1d_win", _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), _dev_f32(resid), r_off,
+            _lib_call("umoe_dac_conv1d_win" + sfx, _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), _dev_f32(resid), r_off,
                       0 if resid is None else resid.shape[2], x.shape[0], ly.cin, L_true, ly.cout, ly.K, ly.stride, ly.dil, ly.pad,
                       int(ly.tanh), t0, n, _dev_f32(y), y_off, y.shape[2], _stream())
         else:
-            _lib_call("umoe_dac_conv_transpose1d_win", _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), x.shape[0],
+            _lib_call("umoe_dac_conv_transpose1d_win" + sfx, _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), x.shape[0],
                       ly.cin, L_true, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, t0, n, _dev_f32(y), y_off, y.shape[2], _stream())
 
     def _empty(self, *shape):
@@ -867,15 +934,17 @@ class DacRowStreamDecoder:
         """layer i: the windows of all rows in one launch; table = (host [slots, 12], its device copy)"""
         ly = self.plan.layers[i]
         f = self.model._folded()
-        w, b = f[ly.mod]
+        b = f[ly.mod][1]
+        form, w = self.model._route(ly.mod, f)
+        sfx = "_mfma" if form == "mfma" else ""
         a = f[ly.snake] if ly.snake is not None else None
         host, dev = table
         max_n = max((v.n for v in wins), default=0)
         if ly.kind == "conv":
-            _lib_call("umoe_dac_conv1d_win_rows", C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n, _dev_f32(w),
+            _lib_call("umoe_dac_conv1d_win_rows" + sfx, C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n, _dev_f32(w),
                       _dev_f32(b), _dev_f32(a), ly.cin, ly.cout, ly.K, ly.stride, ly.dil, ly.pad, int(ly.tanh), _stream())
         else:
-            _lib_call("umoe_dac_conv_transpose1d_win_rows", C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n,
+            _lib_call("umoe_dac_conv_transpose1d_win_rows" + sfx, C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n,
                       _dev_f32(w), _dev_f32(b), _dev_f32(a), ly.cin, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, _stream())
 
     def _tables(self, work, wave):
