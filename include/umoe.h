@@ -1059,6 +1059,94 @@ int umoe_engine_info(umoe_engine* e, const char* key);
 /* introspection for parity tests: device pointers into the workspace */
 const void* umoe_engine_buffer(umoe_engine* e, const char* name, size_t* bytes);
 
+/* ------------------------------------------------------------------ optimizer step (umoe_optim.hip; unimoe_audio_amd/optim.py)
+ * AdamW with decoupled decay (torch.optim.AdamW, no amsgrad) behind torch.nn.utils.clip_grad_norm_'s rule, on fp32 master weights
+ * of bf16 parameters (the reference trains under DeepSpeed's bf16 mode: UniMoEV2-Preview/deepspeed_zero2.conf, script/training.sh:61-72,
+ * moe_trainer.py:691-703).  All tensors of all parameter groups go through ONE chunked launch per stage; nothing syncs with the host.
+ *
+ * Tables (device arrays, packed on the host as plain records: unimoe_audio_amd/optim.py TENSOR_DTYPE / int64 pairs):
+ *   umoe_optim_tensor [n_tensors]  one record per parameter tensor, 56 bytes, 8-byte aligned:
+ *       p       the parameter: bf16 (p_fp32 = 0) or fp32 (p_fp32 = 1) [n]
+ *       g       its gradient, of the parameter's dtype [n]; NULL = the tensor is left out of this step (torch: .grad is None)
+ *       master  fp32 master weights [n] (p_fp32 = 0); ignored for an fp32 parameter, which is updated in place
+ *       m, v    fp32 first / second moments [n]
+ *       n       element count;  group  index into the per-group settings of umoe_optim_hyper (0 .. num_groups - 1)
+ *   umoe_optim_chunk [n_chunks]    (tensor index, first element): the chunk covers elements [first, min(first + chunk_elems, n)) of that
+ *       tensor, first a multiple of chunk_elems below n -- so a chunk never crosses its tensor.  chunk_elems: a positive multiple of 8.
+ *   The launch entries take the device tables and, optionally, the host arrays they were uploaded from (host_tensors / host_chunks,
+ *   both or neither): given, every record is checked before anything is enqueued -- a chunk that crosses its tensor (tensor index out
+ *   of range, first < 0, first >= n or not a multiple of chunk_elems), a group index outside the groups, n < 0 are refused.  The
+ *   kernels themselves skip a chunk whose record fails these bounds, so a table that was never checked cannot send a workgroup
+ *   outside [0, n) of a tensor either.
+ * Streams of a tensor that are 16-byte aligned together after the same number of leading elements take 16-byte vector loads and
+ * stores with a scalar head and tail (a view at an odd element offset); streams that are not co-aligned take the scalar path whole.
+ *
+ * Stage 1  umoe_optim_sqsum: partial[c] = sum of squares of chunk c's gradients, fp32, in a fixed order (per thread sequentially over
+ *   its 8-element vectors then its head / tail element, xor butterfly within the wave, waves added in order): no atomics, bitwise
+ *   reproducible, independent of grid_cap.  flags[c] = 1 when a gradient element (or the fp32 sum) is not finite.  A left-out tensor's
+ *   chunks write 0 / 0.
+ * Stage 2  umoe_optim_scalars: one workgroup adds the partials in fp64 (thread i its contiguous run of chunks in ascending order,
+ *   then the 256 runs in ascending order), reads the step counter t = counters[0] and writes the record:
+ *       norm = fp32(sqrt(sum)),  clip = min(1, fp32(max_norm) / (norm + 1e-6f)) in fp32 (1 when max_norm < 0: clipping off),
+ *       bc1[g] = fp32(1 - beta1[g]^(t+1)),  bc2[g] = fp32(1 - beta2[g]^(t+1))  (fp64 arithmetic),
+ *       skip = 1 when the sum or any flag is not finite.
+ *   skip 0: counters[0] = t + 1.  skip 1: counters[1] += 1 and t stays.   partial / flags may be NULL with n_chunks 0.
+ * Stage 3  umoe_optim_adamw: reads the record once per workgroup; skip set: returns having written nothing.  Otherwise per element,
+ *   fp32, no contraction, correctly rounded division and square root, with b1 = fp32(beta1), omb1 = fp32(1 - beta1) (the difference in
+ *   fp64), likewise b2 / omb2, decay = 1 - lr * wd, step = lr / bc1, sq = sqrt(bc2) computed once per workgroup in fp32:
+ *       g  = float(grad) * clip
+ *       m' = b1 * m + omb1 * g
+ *       v' = b2 * v + (omb2 * g) * g
+ *       w' = w * decay - (step * m') / (sqrt(v') / sq + eps)
+ *   stores w' (master, or the fp32 parameter itself), m', v' and p = bf16_rne(w').
+ *   rec NULL (no stage 1 / 2 ran: clipping off and no finite check): t_host >= 0 is the step counter kept by the caller; the bias
+ *   corrections are computed from it on the host the same way, clip = 1, nothing is skipped, and counters[0] = t_host + 1 is written
+ *   by the launch (counters may be NULL).
+ * Refusals (error return, nothing enqueued): NULL tables / outputs, num_groups outside 1..UMOE_OPTIM_MAX_GROUPS, chunk_elems <= 0 or
+ * not a multiple of 8, a host table record out of bounds (above).  n_chunks == 0 (an empty table) is a no-op returning 0.
+ * grid_cap: most workgroups launched, each striding over the chunk table; 0 = the default (2048). */
+#define UMOE_OPTIM_MAX_GROUPS 16
+typedef struct {
+    void* p;
+    const void* g;
+    float* master;
+    float* m;
+    float* v;
+    int64_t n;
+    int32_t group;
+    int32_t p_fp32;
+} umoe_optim_tensor;
+typedef struct {
+    int64_t tensor;
+    int64_t first;
+} umoe_optim_chunk;
+/* what stage 2 leaves for stage 3 (device, 144 bytes) */
+typedef struct {
+    float norm;
+    float clip;
+    int32_t skip;
+    int32_t reserved;
+    float bc1[UMOE_OPTIM_MAX_GROUPS];
+    float bc2[UMOE_OPTIM_MAX_GROUPS];
+} umoe_optim_record;
+/* per-group settings (host; read at every call, so a learning-rate schedule is just another value) */
+typedef struct {
+    int32_t num_groups;
+    int32_t reserved;
+    double max_norm;                      /* < 0: clipping off */
+    double lr[UMOE_OPTIM_MAX_GROUPS], beta1[UMOE_OPTIM_MAX_GROUPS], beta2[UMOE_OPTIM_MAX_GROUPS], eps[UMOE_OPTIM_MAX_GROUPS],
+        wd[UMOE_OPTIM_MAX_GROUPS];
+} umoe_optim_hyper;
+int umoe_optim_sqsum(const umoe_optim_tensor* tensors, int n_tensors, const umoe_optim_chunk* chunks, int64_t n_chunks, int chunk_elems,
+                     const umoe_optim_tensor* host_tensors, const umoe_optim_chunk* host_chunks, int num_groups, int grid_cap,
+                     float* partial, int32_t* flags, umoe_stream_t stream);
+int umoe_optim_scalars(const float* partial, const int32_t* flags, int64_t n_chunks, const umoe_optim_hyper* hyper, int64_t* counters,
+                       umoe_optim_record* rec, umoe_stream_t stream);
+int umoe_optim_adamw(const umoe_optim_tensor* tensors, int n_tensors, const umoe_optim_chunk* chunks, int64_t n_chunks, int chunk_elems,
+                     const umoe_optim_tensor* host_tensors, const umoe_optim_chunk* host_chunks, int grid_cap,
+                     const umoe_optim_hyper* hyper, const umoe_optim_record* rec, int64_t t_host, int64_t* counters,
+                     umoe_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,7 @@ EXPORTS = [
     "umoe_dac_conv1d_win_rows", "umoe_dac_conv_transpose1d_win_rows", "umoe_dac_shift_rows", "umoe_rvq_from_delayed_rows",
     "umoe_dac_conv1d_mfma", "umoe_dac_conv_transpose1d_mfma", "umoe_dac_conv1d_win_mfma", "umoe_dac_conv_transpose1d_win_mfma",
     "umoe_dac_conv1d_win_rows_mfma", "umoe_dac_conv_transpose1d_win_rows_mfma",
+    "umoe_optim_sqsum", "umoe_optim_scalars", "umoe_optim_adamw",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -242,6 +243,12 @@ def lib():
         for sfx in ("", "_win", "_win_rows"):          # the MFMA forms take their direct siblings' arguments (wt in the place of w)
             for stem in ("umoe_dac_conv1d", "umoe_dac_conv_transpose1d"):
                 getattr(L, f"{stem}{sfx}_mfma").argtypes = getattr(L, stem + sfx).argtypes
+        if not hasattr(L, "umoe_optim_adamw"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_optim_adamw): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        # tables and records of the optimizer step are plain arrays packed by unimoe_audio_amd/optim.py; `hyper` is its OptimHyper
+        L.umoe_optim_sqsum.argtypes = [vp, i32, vp, i64, i32, vp, vp, i32, i32, vp, vp, vp]
+        L.umoe_optim_scalars.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+        L.umoe_optim_adamw.argtypes = [vp, i32, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp]
         L.umoe_rvq_from_delayed_rows.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_rope.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_attn.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]

@@ -293,3 +293,21 @@ def moe_param_groups(model, weight_decay: float = 0.0, no_decay_suffixes=("bias"
         out.append({**g, "params": keep_p, "params_source": keep_n})
         moe_groups += [v for v in per.values() if v["params"]]
     return out + moe_groups
+
+
+def train_step(model, opt, input_ids, codec_input_ids, attention_mask, codec_labels, aux_balance_weight=None, position_ids=None,
+               set_to_none: bool = False):
+    """One training iteration: forward_train, backward, opt.step() (optim.AdamW: clip, fp32 master update, bf16 parameters rewritten
+    and their _version bumped, so every pack cache sees the edit) and opt.zero_grad().  Returns (loss, codec_loss, aux_mean, grad_norm),
+    all device tensors (detached); grad_norm is the optimizer's, the global norm before clipping.  Nothing here syncs with the host.
+    set_to_none=False keeps the gradient buffers, so the optimizer's device tables are packed once."""
+    from . import quant
+    if quant.is_released(model):
+        raise L.UmoeError("train_step: the expert parameters of this model were released (expert_weights 'fp8-only' / 'w12-only'): "
+                          "inference only: `quant.dequantize_experts_` first")
+    loss, codec_loss, aux_mean = forward_train(model, input_ids, codec_input_ids, attention_mask, codec_labels, aux_balance_weight, position_ids)
+    loss.backward()
+    opt.step()
+    grad_norm = opt.grad_norm.clone() if hasattr(opt, "grad_norm") else None
+    opt.zero_grad(set_to_none=set_to_none)
+    return loss.detach(), codec_loss.detach(), aux_mean.detach(), grad_norm
