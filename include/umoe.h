@@ -358,13 +358,21 @@ typedef struct {
     int num_groups;
     const uint16_t* p; int ldp;      /* [rows][ldp] bf16: its columns become output ROWS */
     const uint16_t* q; int ldq;      /* [rows][ldq] bf16: its columns become output COLUMNS */
-    void* out; int ldo;              /* bf16 [*, ldo] */
+    void* out; int ldo;              /* bf16 [*, ldo] (umoe_tiled_gemm_tn_acc: fp32 [*, ldo], 16-byte aligned) */
     int k_split;                     /* 0 / 1: none; > 1: that many parts; < 0: chosen by the library (1..8, from the tile count and K) */
     void* ws; long part_stride;      /* k_split > 1 or < 0: fp32 workspace (umoe_tiled_gemm_tn_workspace_bytes), part_stride = rows * ldo of the output */
 } umoe_tgemm_tn_args;
 size_t umoe_tiled_gemm_tn_workspace_bytes(const umoe_tgemm_tn_args* a);
 int umoe_tiled_gemm_tn_split(const umoe_tgemm_tn_args* a);      /* the K split the call would use (k_split < 0: the library's choice) */
 int umoe_tiled_gemm_tn(const umoe_tgemm_tn_args* a, umoe_stream_t stream);
+/* Accumulate form (fp32 main gradients): the same arguments and structs, but `out` and every group's `out` are FP32, 16-byte
+ * aligned, and every element umoe_tiled_gemm_tn would store becomes out = out + sum (one fp32 add on the unrounded fp32 sum).  Rows at or
+ * beyond m and columns at or beyond n are neither read nor written.  No K split: the tile's owner loads its float4, adds and stores -- no
+ * atomics, bitwise reproducible.  K split (same rule and workspace): s = part 0 + part 1 + ... in the bf16 entry's order, then
+ * out = out + s -- s has the bits the bf16 entry rounds.  A group whose window is empty (device k_count 0: an expert no token reached)
+ * leaves its output bit for bit as it was.  Refusals: those of umoe_tiled_gemm_tn, and an fp32 output that is not 16-byte aligned;
+ * a refused call enqueues nothing. */
+int umoe_tiled_gemm_tn_acc(const umoe_tgemm_tn_args* a, umoe_stream_t stream);
 
 /* Named wrappers required by the scope table; thin calls of umoe_grouped_gemm.
  * umoe_grouped_swiglu_fwd: routed experts, core.py:406-416 + :34-49 on ragged rows.
@@ -514,6 +522,11 @@ typedef struct {
 size_t umoe_swiglu_bwd_workspace_bytes(const umoe_swiglu_bwd_args* a);
 int umoe_grouped_swiglu_bwd(const umoe_swiglu_bwd_args* a, umoe_stream_t stream);
 int umoe_shared_swiglu_bwd(const umoe_swiglu_bwd_args* a, umoe_stream_t stream);
+/* The same composites with fp32 main gradients: dw_gate / dw_up / dw_down hold FP32 device pointers (16-byte aligned) that the three
+ * weight-gradient products add into (umoe_tiled_gemm_tn_acc); the K-split rule of the shared experts tests for a stacked slab in fp32
+ * elements.  dx_slots and everything on the input-gradient chain are bit-identical to the bf16 composites. */
+int umoe_grouped_swiglu_bwd_acc(const umoe_swiglu_bwd_args* a, umoe_stream_t stream);
+int umoe_shared_swiglu_bwd_acc(const umoe_swiglu_bwd_args* a, umoe_stream_t stream);
 
 /* backward of umoe_aux_loss_fwd (core.py:361-389): d_logits [S][E] fp32 = *d_aux * d aux / d logits (zero on the columns the
  * mask removed and on the shared columns); ws: 17 floats of scratch (per-expert token fractions, weight sum). */
@@ -1066,9 +1079,12 @@ const void* umoe_engine_buffer(umoe_engine* e, const char* name, size_t* bytes);
  *
  * Tables (device arrays, packed on the host as plain records: unimoe_audio_amd/optim.py TENSOR_DTYPE / int64 pairs):
  *   umoe_optim_tensor [n_tensors]  one record per parameter tensor, 56 bytes, 8-byte aligned:
- *       p       the parameter: bf16 (p_fp32 = 0) or fp32 (p_fp32 = 1) [n]
- *       g       its gradient, of the parameter's dtype [n]; NULL = the tensor is left out of this step (torch: .grad is None)
- *       master  fp32 master weights [n] (p_fp32 = 0); ignored for an fp32 parameter, which is updated in place
+ *       p_fp32  a flag word: bit 0 (UMOE_OPTIM_P_FP32) the parameter is fp32 and its own master; bit 1 (UMOE_OPTIM_G_FP32) the gradient
+ *               is fp32 whatever the parameter is (an fp32 main gradient of a bf16 parameter: DESIGN 4s).  0 and 1 mean what they did.
+ *       p       the parameter: bf16 (bit 0 clear) or fp32 (bit 0 set) [n]
+ *       g       its gradient [n], of the parameter's dtype unless bit 1 says fp32; NULL = the tensor is left out of this step (torch:
+ *               .grad is None)
+ *       master  fp32 master weights [n] (bit 0 clear); ignored for an fp32 parameter, which is updated in place
  *       m, v    fp32 first / second moments [n]
  *       n       element count;  group  index into the per-group settings of umoe_optim_hyper (0 .. num_groups - 1)
  *   umoe_optim_chunk [n_chunks]    (tensor index, first element): the chunk covers elements [first, min(first + chunk_elems, n)) of that
@@ -1106,6 +1122,8 @@ const void* umoe_engine_buffer(umoe_engine* e, const char* name, size_t* bytes);
  * not a multiple of 8, a host table record out of bounds (above).  n_chunks == 0 (an empty table) is a no-op returning 0.
  * grid_cap: most workgroups launched, each striding over the chunk table; 0 = the default (2048). */
 #define UMOE_OPTIM_MAX_GROUPS 16
+#define UMOE_OPTIM_P_FP32 1
+#define UMOE_OPTIM_G_FP32 2
 typedef struct {
     void* p;
     const void* g;
@@ -1146,6 +1164,22 @@ int umoe_optim_adamw(const umoe_optim_tensor* tensors, int n_tensors, const umoe
                      const umoe_optim_tensor* host_tensors, const umoe_optim_chunk* host_chunks, int grid_cap,
                      const umoe_optim_hyper* hyper, const umoe_optim_record* rec, int64_t t_host, int64_t* counters,
                      umoe_stream_t stream);
+
+/* Fold of the bf16 gradients autograd still produces (norm weights, biases, the router gate, the embedding tables) into fp32 main
+ * gradients, one chunked launch over a table of 24-byte records and a chunk table built as above:
+ *       main[i] = main[i] + float(g[i])     (one fp32 add; the bf16 -> fp32 conversion is exact)
+ *       g[i]    = +0                        (the same pass clears what it folded)
+ * g NULL: the tensor is left out (its main gradient is untouched).  16-byte loads and stores where g and main are 16-byte aligned together
+ * after the same number of leading elements, a scalar head and tail, the scalar path whole otherwise.  Each element belongs to one
+ * thread, so the result does not depend on grid_cap.  Refusals as for the stages above (host tables checked when given, a record with g
+ * but no main included); a refused call enqueues nothing. */
+typedef struct {
+    uint16_t* g;       /* bf16 [n], or NULL */
+    float* main;       /* fp32 [n] */
+    int64_t n;
+} umoe_optim_fold_tensor;
+int umoe_optim_fold(const umoe_optim_fold_tensor* tensors, int n_tensors, const umoe_optim_chunk* chunks, int64_t n_chunks, int chunk_elems,
+                    const umoe_optim_fold_tensor* host_tensors, const umoe_optim_chunk* host_chunks, int grid_cap, umoe_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,7 @@ EXPORTS = [
     "umoe_dac_conv1d_mfma", "umoe_dac_conv_transpose1d_mfma", "umoe_dac_conv1d_win_mfma", "umoe_dac_conv_transpose1d_win_mfma",
     "umoe_dac_conv1d_win_rows_mfma", "umoe_dac_conv_transpose1d_win_rows_mfma",
     "umoe_optim_sqsum", "umoe_optim_scalars", "umoe_optim_adamw",
+    "umoe_tiled_gemm_tn_acc", "umoe_grouped_swiglu_bwd_acc", "umoe_shared_swiglu_bwd_acc", "umoe_optim_fold",
 ]
 
 EP_PEER, EP_LOOPBACK, EP_RCCL = 0, 1, 2
@@ -249,6 +250,13 @@ def lib():
         L.umoe_optim_sqsum.argtypes = [vp, i32, vp, i64, i32, vp, vp, i32, i32, vp, vp, vp]
         L.umoe_optim_scalars.argtypes = [vp, vp, i64, vp, vp, vp, vp]
         L.umoe_optim_adamw.argtypes = [vp, i32, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp]
+        if not hasattr(L, "umoe_optim_fold"):
+            raise UmoeError(f"{_SO} predates this package (no umoe_optim_fold): rebuild it (`make -C unimoe_audio_amd/csrc`)")
+        # fp32 main gradients: the fold over (g, main, n) records (optim.FOLD_DTYPE) and the accumulate forms of the weight-gradient entries
+        L.umoe_optim_fold.argtypes = [vp, i32, vp, i64, i32, vp, vp, i32, vp]
+        L.umoe_tiled_gemm_tn_acc.argtypes = [C.POINTER(TGemmTnArgs), vp]
+        L.umoe_grouped_swiglu_bwd_acc.argtypes = [C.POINTER(SwigluBwdArgs), vp]
+        L.umoe_shared_swiglu_bwd_acc.argtypes = [C.POINTER(SwigluBwdArgs), vp]
         L.umoe_rvq_from_delayed_rows.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_rope.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.umoe_vision_attn.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp]

@@ -965,7 +965,9 @@ BwdSide& bwd_side() {
 //   dH = dY Wd ; (dG | dU) = swiglu'(G, U, dH) ; dX_slots = dG Wg + dU Wu ; dWd = dY^T H ; dWg = dG^T X ; dWu = dU^T X
 // ragged groups (routed experts): counts/offsets (8-aligned, umoe_dispatch_build_aligned) + optional gather list for x;
 // static groups (shared experts): counts == NULL, group g owns rows [row_base + g*max_rows, +max_rows).
-static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) {
+// acc (umoe_*_swiglu_bwd_acc): dw_gate / dw_up / dw_down hold fp32 main gradients that the weight-gradient products add into
+// (umoe_tiled_gemm_tn_acc); the input-gradient chain is the same launches on the same operands either way.
+static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream, const bool acc) {
     UMOE_REQUIRE(a && a->num_groups > 0 && a->num_groups <= 12 && a->w_gate && a->w_up && a->w_down && a->x && a->h && a->gu && a->dy &&
                      a->dx_slots && a->dw_gate && a->dw_up && a->dw_down && a->ws,
                  "umoe_*_swiglu_bwd: null argument or more than 12 groups");
@@ -1010,11 +1012,13 @@ static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) 
     // routed experts: ONE grouped launch per product kind with the experts' slot windows read on the device (gate and up together:
     // 2 G groups); shared experts: static windows, the K split chosen by the library when the outputs of a launch are one stacked slab
     // (ops.experts_swiglu_bwd allocates them so).
+    const size_t esz = acc ? sizeof(float) : sizeof(uint16_t);      // the slab tests count elements of the gradients' own type
     auto stacked = [&](uint16_t* const* ptrs, size_t elems) {
         for (int g = 1; g < G; ++g)
-            if (ptrs[g] != ptrs[0] + (size_t)g * elems) return false;
+            if (reinterpret_cast<const char*>(ptrs[g]) != reinterpret_cast<const char*>(ptrs[0]) + (size_t)g * elems * esz) return false;
         return true;
     };
+    auto tn_launch = [&](const umoe_tgemm_tn_args* b, umoe_stream_t st) { return acc ? umoe_tiled_gemm_tn_acc(b, st) : umoe_tiled_gemm_tn(b, st); };
     umoe_tn_group_t tn[24];
     auto wgrad_down = [&](umoe_stream_t st) -> int {
         umoe_tgemm_tn_args b{};
@@ -1034,7 +1038,7 @@ static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) 
             if (slab) { b.k_split = -1; b.ws = tn_ws; b.part_stride = (long)G * D * I; }
         }
         b.groups = tn; b.num_groups = G; b.p = a->dy; b.ldp = a->lddy; b.q = a->h; b.ldq = a->ldh; b.out = a->dw_down[0]; b.ldo = I;
-        return umoe_tiled_gemm_tn(&b, st);
+        return tn_launch(&b, st);
     };
     auto wgrad_gateup = [&](umoe_stream_t st) -> int {
         umoe_tgemm_tn_args b{};
@@ -1049,7 +1053,8 @@ static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) 
             }
             b.q = xe; b.ldq = D;
         } else {       // ... and of (dG | dU); x is read by identity (rows 0 .. S-1)
-            const bool slab = stacked(a->dw_gate, (size_t)I * D) && stacked(a->dw_up, (size_t)I * D) && a->dw_up[0] == a->dw_gate[0] + (size_t)G * I * D;
+            const bool slab = stacked(a->dw_gate, (size_t)I * D) && stacked(a->dw_up, (size_t)I * D) &&
+                              reinterpret_cast<const char*>(a->dw_up[0]) == reinterpret_cast<const char*>(a->dw_gate[0]) + (size_t)G * I * D * esz;
             for (int g = 0; g < G; ++g) {
                 const size_t r0 = (size_t)a->row_base + (size_t)g * S;
                 tn[g].m = I; tn[g].n = D; tn[g].k = S;
@@ -1063,7 +1068,7 @@ static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) 
             b.q = a->x; b.ldq = a->ldx;
         }
         b.groups = tn; b.num_groups = 2 * G; b.p = dgu; b.ldp = 2 * I; b.out = a->dw_gate[0]; b.ldo = D;
-        return umoe_tiled_gemm_tn(&b, st);
+        return tn_launch(&b, st);
     };
     // fork: dWd needs only the call's inputs
     BwdSide& bs = bwd_side();
@@ -1121,11 +1126,19 @@ static int swiglu_bwd_impl(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) 
 
 extern "C" int umoe_grouped_swiglu_bwd(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) {
     UMOE_REQUIRE(a && a->counts && a->offsets, "umoe_grouped_swiglu_bwd: routed experts need counts/offsets (umoe_dispatch_build_aligned)");
-    return swiglu_bwd_impl(a, stream);
+    return swiglu_bwd_impl(a, stream, false);
+}
+extern "C" int umoe_grouped_swiglu_bwd_acc(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) {
+    UMOE_REQUIRE(a && a->counts && a->offsets, "umoe_grouped_swiglu_bwd_acc: routed experts need counts/offsets (umoe_dispatch_build_aligned)");
+    return swiglu_bwd_impl(a, stream, true);
 }
 extern "C" int umoe_shared_swiglu_bwd(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) {
     UMOE_REQUIRE(a && !a->counts && !a->offsets, "umoe_shared_swiglu_bwd: shared experts take every row (counts/offsets must be NULL)");
-    return swiglu_bwd_impl(a, stream);
+    return swiglu_bwd_impl(a, stream, false);
+}
+extern "C" int umoe_shared_swiglu_bwd_acc(const umoe_swiglu_bwd_args* a, umoe_stream_t stream) {
+    UMOE_REQUIRE(a && !a->counts && !a->offsets, "umoe_shared_swiglu_bwd_acc: shared experts take every row (counts/offsets must be NULL)");
+    return swiglu_bwd_impl(a, stream, true);
 }
 
 // ------------------------------------------------------------------------------------ attention backward (composite)

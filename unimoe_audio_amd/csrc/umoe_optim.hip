@@ -13,6 +13,7 @@
 #define OPT_THREADS 256
 #define OPT_DEFAULT_GRID 2048      // cdna_hip_programming.md Guideline 11: cap a memory-bound grid at ~256 CU x 8 and stride the rest
 
+static_assert(sizeof(umoe_optim_fold_tensor) == 24, "umoe.h record layout");
 static_assert(sizeof(umoe_optim_tensor) == 56 && sizeof(umoe_optim_chunk) == 16 && sizeof(umoe_optim_record) == 144, "umoe.h record layout");
 
 struct optim_group_k { float lr, b1, omb1, b2, omb2, eps, wd, bc1, bc2; };
@@ -52,12 +53,16 @@ __device__ __forceinline__ chunk_view chunk_open(const umoe_optim_tensor* tensor
     cv.first = first;
     const long left = cv.t.n - first;
     cv.len = (int)(left < chunk_elems ? left : chunk_elems);
-    const int es = cv.t.p_fp32 ? 4 : 2;
-    int head = head_of(cv.t.g, first, es);
-    bool ok = (((uintptr_t)cv.t.g) & (es - 1)) == 0;
+    // p_fp32 is a flag word: bit 0 the parameter is fp32 (its own master), bit 1 the gradient is fp32 (a main gradient of a bf16 parameter)
+    const int es = (cv.t.p_fp32 & UMOE_OPTIM_P_FP32) ? 4 : 2;
+    const int eg = (cv.t.p_fp32 & (UMOE_OPTIM_P_FP32 | UMOE_OPTIM_G_FP32)) ? 4 : 2;
+    // the head is the parameter's where the parameter moves too (its elements are the widest apart in bytes per 16: a bf16 parameter
+    // needs up to 7, which its fp32 streams then share); the same number as the gradient's whenever the two have one type and co-align
+    int head = with_state ? head_of(cv.t.p, first, es) : head_of(cv.t.g, first, eg);
+    bool ok = (((uintptr_t)cv.t.g) & (eg - 1)) == 0;
     if (with_state) {
-        ok = ok && aligned_after(cv.t.p, first, head, es) && aligned_after(cv.t.m, first, head, 4) && aligned_after(cv.t.v, first, head, 4);
-        if (!cv.t.p_fp32) ok = ok && aligned_after(cv.t.master, first, head, 4);
+        ok = ok && aligned_after(cv.t.g, first, head, eg) && aligned_after(cv.t.m, first, head, 4) && aligned_after(cv.t.v, first, head, 4);
+        if (!(cv.t.p_fp32 & UMOE_OPTIM_P_FP32)) ok = ok && aligned_after(cv.t.master, first, head, 4);
     }
     cv.head = ok ? (head < cv.len ? head : cv.len) : cv.len;
     return cv;
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_sqsum_kernel(const umoe_opt
     const int tid = threadIdx.x;
     for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const chunk_view cv = chunk_open(tensors, n_tensors, chunks, c, chunk_elems, false);
-        const bool f32 = cv.t.p_fp32 != 0;
+        const bool f32 = (cv.t.p_fp32 & (UMOE_OPTIM_P_FP32 | UMOE_OPTIM_G_FP32)) != 0;      // the gradient's type
         float acc = 0.0f;
         const int nvec = (cv.len - cv.head) >> 3, tail0 = cv.head + (nvec << 3), nscal = cv.head + (cv.len - tail0);
         for (int i = tid; i < nvec; i += OPT_THREADS) {
@@ -211,13 +216,14 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_adamw_kernel(const umoe_opt
         s.decay = 1.0f - gk.lr * gk.wd;
         s.step = gk.lr / bc1;
         s.sq = sqrtf(bc2);
-        const bool f32 = cv.t.p_fp32 != 0;
+        const bool f32 = (cv.t.p_fp32 & UMOE_OPTIM_P_FP32) != 0;
+        const bool gf32 = (cv.t.p_fp32 & (UMOE_OPTIM_P_FP32 | UMOE_OPTIM_G_FP32)) != 0;
         float* wbase = f32 ? (float*)cv.t.p : cv.t.master;
         const int nvec = (cv.len - cv.head) >> 3, tail0 = cv.head + (nvec << 3), nscal = cv.head + (cv.len - tail0);
         for (int i = tid; i < nvec; i += OPT_THREADS) {
             const long e = cv.first + cv.head + ((long)i << 3);
             float g[8], w[8], m[8], v[8];
-            load8(cv.t.g, e, f32, g);
+            load8(cv.t.g, e, gf32, g);
             load8(wbase, e, true, w);
             load8(cv.t.m, e, true, m);
             load8(cv.t.v, e, true, v);
@@ -234,11 +240,45 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_adamw_kernel(const umoe_opt
         for (int i = tid; i < nscal; i += OPT_THREADS) {
             const long e = cv.first + (i < cv.head ? i : tail0 + (i - cv.head));
             float w = load1(wbase, e, true), m = load1(cv.t.m, e, true), v = load1(cv.t.v, e, true);
-            adamw_elem(w, m, v, load1(cv.t.g, e, f32), s);
+            adamw_elem(w, m, v, load1(cv.t.g, e, gf32), s);
             store1f(wbase, e, w);
             store1f(cv.t.m, e, m);
             store1f(cv.t.v, e, v);
             if (!f32) *(g_h1)((uint16_t*)cv.t.p + e) = f2bf(w);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- fold
+// main += float(g), g = +0 over the bf16 gradients autograd still produces (umoe.h "umoe_optim_fold"); the chunk walk of the stages above
+__global__ __launch_bounds__(OPT_THREADS) void optim_fold_kernel(const umoe_optim_fold_tensor* __restrict__ tensors, int n_tensors,
+                                                                 const umoe_optim_chunk* __restrict__ chunks, long n_chunks, int chunk_elems) {
+    const int tid = threadIdx.x;
+    for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const long ti = chunks[c].tensor, first = chunks[c].first;
+        if (ti < 0 || ti >= n_tensors) continue;
+        const umoe_optim_fold_tensor t = tensors[ti];
+        if (!t.g || !t.main || first < 0 || first >= t.n) continue;
+        const long left = t.n - first;
+        const int len = (int)(left < chunk_elems ? left : chunk_elems);
+        int head = head_of(t.g, first, 2);
+        const bool ok = (((uintptr_t)t.g) & 1) == 0 && aligned_after(t.main, first, head, 4);
+        head = ok ? (head < len ? head : len) : len;
+        const int nvec = (len - head) >> 3, tail0 = head + (nvec << 3), nscal = head + (len - tail0);
+        for (int i = tid; i < nvec; i += OPT_THREADS) {
+            const long e = first + head + ((long)i << 3);
+            float g[8], m[8];
+            load8(t.g, e, false, g);
+            load8(t.main, e, true, m);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) m[j] = m[j] + g[j];
+            store8f(t.main, e, m);
+            *(g_u4)(t.g + e) = u32x4_t{0u, 0u, 0u, 0u};
+        }
+        for (int i = tid; i < nscal; i += OPT_THREADS) {
+            const long e = first + (i < head ? i : tail0 + (i - head));
+            store1f(t.main, e, load1(t.main, e, true) + load1(t.g, e, false));
+            *(g_h1)(t.g + e) = (uint16_t)0;
         }
     }
 }
@@ -256,7 +296,7 @@ static int optim_check_tables(const char* who, const void* tensors, int n_tensor
     for (int i = 0; i < n_tensors; ++i) {
         UMOE_REQUIRE(ht[i].n >= 0 && ht[i].group >= 0 && ht[i].group < num_groups, "%s: tensor %d: n %lld, group %d of %d", who, i,
                      (long long)ht[i].n, ht[i].group, num_groups);
-        UMOE_REQUIRE(ht[i].n == 0 || !ht[i].g || (ht[i].p && ht[i].m && ht[i].v && (ht[i].p_fp32 || ht[i].master)),
+        UMOE_REQUIRE(ht[i].n == 0 || !ht[i].g || (ht[i].p && ht[i].m && ht[i].v && ((ht[i].p_fp32 & UMOE_OPTIM_P_FP32) || ht[i].master)),
                      "%s: tensor %d: NULL p / master / m / v", who, i);
     }
     for (int64_t c = 0; c < n_chunks; ++c) {
@@ -333,6 +373,36 @@ extern "C" int umoe_optim_adamw(const umoe_optim_tensor* tensors, int n_tensors,
     }
     optim_adamw_kernel<<<dim3(optim_grid(n_chunks, grid_cap)), OPT_THREADS, 0, (hipStream_t)stream>>>(tensors, n_tensors, chunks, (long)n_chunks,
                                                                                                      chunk_elems, ka, rec, counters);
+    UMOE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int umoe_optim_fold(const umoe_optim_fold_tensor* tensors, int n_tensors, const umoe_optim_chunk* chunks, int64_t n_chunks,
+                               int chunk_elems, const umoe_optim_fold_tensor* host_tensors, const umoe_optim_chunk* host_chunks, int grid_cap,
+                               umoe_stream_t stream) {
+    const char* who = "umoe_optim_fold";
+    UMOE_REQUIRE(n_tensors >= 0 && n_chunks >= 0 && grid_cap >= 0, "%s: negative count", who);
+    UMOE_REQUIRE(chunk_elems > 0 && chunk_elems % 8 == 0, "%s: chunk_elems must be a positive multiple of 8 (got %d)", who, chunk_elems);
+    if (n_chunks == 0) return 0;
+    UMOE_REQUIRE(tensors && chunks && n_tensors > 0, "%s: NULL table", who);
+    UMOE_REQUIRE((host_tensors == nullptr) == (host_chunks == nullptr), "%s: host_tensors and host_chunks go together", who);
+    if (host_tensors) {
+        for (int i = 0; i < n_tensors; ++i) {
+            UMOE_REQUIRE(host_tensors[i].n >= 0, "%s: tensor %d: n %lld", who, i, (long long)host_tensors[i].n);
+            UMOE_REQUIRE(host_tensors[i].n == 0 || !host_tensors[i].g || host_tensors[i].main, "%s: tensor %d: a gradient without a main gradient", who, i);
+            UMOE_REQUIRE((reinterpret_cast<size_t>(host_tensors[i].g) & 1) == 0 && (reinterpret_cast<size_t>(host_tensors[i].main) & 3) == 0,
+                         "%s: tensor %d: misaligned g / main", who, i);
+        }
+        for (int64_t c = 0; c < n_chunks; ++c) {
+            const int64_t ti = host_chunks[c].tensor, first = host_chunks[c].first;
+            UMOE_REQUIRE(ti >= 0 && ti < n_tensors, "%s: chunk %lld names tensor %lld of %d", who, (long long)c, (long long)ti, n_tensors);
+            UMOE_REQUIRE(first >= 0 && first < host_tensors[ti].n && first % chunk_elems == 0,
+                         "%s: chunk %lld crosses its tensor (first %lld, n %lld, chunk_elems %d)", who, (long long)c, (long long)first,
+                         (long long)host_tensors[ti].n, chunk_elems);
+        }
+    }
+    optim_fold_kernel<<<dim3(optim_grid(n_chunks, grid_cap)), OPT_THREADS, 0, (hipStream_t)stream>>>(tensors, n_tensors, chunks, (long)n_chunks,
+                                                                                                    chunk_elems);
     UMOE_LAUNCH_CHECK();
     return 0;
 }

@@ -50,7 +50,12 @@ __device__ __forceinline__ void tn_frags(bf16x8_t (&f)[N], const unsigned addr) 
     if constexpr (N >= 4) f[3] = tn_frag<OFF0 + 3 * STEP>(addr);
 }
 
-template <int NS, bool F32OUT>
+// OUT: how a lane stores its 4 consecutive fp32 sums -- TN_OUT_BF16 rounds them (umoe_tiled_gemm_tn without a K split), TN_OUT_F32 writes
+// them into the K-split partial slab `part`, TN_OUT_ACC adds them to the fp32 output in place (umoe_tiled_gemm_tn_acc without a K split:
+// one workgroup owns an output element, so a plain float4 load / add / store, no atomics).
+enum { TN_OUT_BF16 = 0, TN_OUT_F32 = 1, TN_OUT_ACC = 2 };
+
+template <int NS, int OUT>
 __global__ __launch_bounds__(512, 2) void tgemm_tn_kernel(const umoe_tgemm_tn_args p, const tn_pack gp, const int nx, const int ny, const int nz, const int ragged_order,
                                                            const unsigned total_wgs, const int ksplit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -89,6 +94,9 @@ __global__ __launch_bounds__(512, 2) void tgemm_tn_kernel(const umoe_tgemm_tn_ar
         const int hi = lo + per < K ? lo + per : K;
         koff += lo;
         K = hi > lo ? hi - lo : 0;
+    }
+    if constexpr (OUT == TN_OUT_ACC) {
+        if (K <= 0) return;      // an empty window (an expert no token reached) adds nothing: its output keeps its bits (workgroup-uniform, in front of every barrier)
     }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -208,7 +216,11 @@ __global__ __launch_bounds__(512, 2) void tgemm_tn_kernel(const umoe_tgemm_tn_ar
         for (int j = 0; j < 4; ++j) {
             const int col = n0 + 16 * (4 * j + wc) + 4 * h;
             if (col >= g.n) continue;
-            if constexpr (F32OUT) {
+            if constexpr (OUT == TN_OUT_ACC) {
+                float* o = reinterpret_cast<float*>(g.out ? g.out : p.out) + (orow_base + r) * (long)p.ldo + g.out_col_off + col;
+                const float4 prev = *reinterpret_cast<const float4*>(o);
+                *reinterpret_cast<float4*>(o) = make_float4(prev.x + acc[j][i][0], prev.y + acc[j][i][1], prev.z + acc[j][i][2], prev.w + acc[j][i][3]);
+            } else if constexpr (OUT == TN_OUT_F32) {
                 float* o = reinterpret_cast<float*>(g.out ? g.out : p.out) + (size_t)part * p.part_stride + (orow_base + r) * (long)p.ldo + g.out_col_off + col;
                 *reinterpret_cast<float4*>(o) = make_float4(acc[j][i][0], acc[j][i][1], acc[j][i][2], acc[j][i][3]);
             } else {
@@ -458,7 +470,20 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
     reinterpret_cast<uint2*>(out)[i] = make_uint2((uint32_t)f2bf(s.x) | ((uint32_t)f2bf(s.y) << 16), (uint32_t)f2bf(s.z) | ((uint32_t)f2bf(s.w) << 16));
 }
 
-template <bool F32OUT>
+// the accumulate form of the same sum: out = out + (part 0 + part 1 + ...), the parts added first in tn_reduce_kernel's order
+__global__ __launch_bounds__(256) void tn_reduce_acc_kernel(const float* __restrict__ parts, const long part_stride, const int nparts, const long n4, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    float4 s = reinterpret_cast<const float4*>(parts)[i];
+    for (int k = 1; k < nparts; ++k) {
+        const float4 t = reinterpret_cast<const float4*>(parts + (size_t)k * part_stride)[i];
+        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+    }
+    const float4 o = reinterpret_cast<const float4*>(out)[i];
+    reinterpret_cast<float4*>(out)[i] = make_float4(o.x + s.x, o.y + s.y, o.z + s.z, o.w + s.w);
+}
+
+template <int OUT>
 static int launch_tn(const umoe_tgemm_tn_args* a, int max_m, int max_n, int ragged, int ksplit, hipStream_t s) {
     constexpr int NS = 4;
     constexpr int lds = NS * 2 * 16 * 1088;
@@ -467,13 +492,13 @@ static int launch_tn(const umoe_tgemm_tn_args* a, int max_m, int max_n, int ragg
     memcpy(gp.g, a->groups, sizeof(umoe_tn_group_t) * a->num_groups);
     static bool configured = false;
     if (!configured) {
-        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tgemm_tn_kernel<NS, F32OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        UMOE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tgemm_tn_kernel<NS, OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         configured = true;
     }
     const int nx = ceil_div(max_n, 256), ny = ceil_div(max_m, 256), nz = a->num_groups * ksplit;
     const long nwg = ragged ? (long)nx * (((long)ny * nz + 7) & ~7L) : (long)nx * ny * nz;
     UMOE_REQUIRE(nwg < (1L << 31), "umoe_tiled_gemm_tn: too many tiles (%ld)", nwg);
-    tgemm_tn_kernel<NS, F32OUT><<<dim3((unsigned)nwg), 512, lds, s>>>(*a, gp, nx, ny, nz, ragged, (unsigned)nwg, ksplit);
+    tgemm_tn_kernel<NS, OUT><<<dim3((unsigned)nwg), 512, lds, s>>>(*a, gp, nx, ny, nz, ragged, (unsigned)nwg, ksplit);
     UMOE_LAUNCH_CHECK();
     return 0;
 }
@@ -525,7 +550,8 @@ extern "C" size_t umoe_tiled_gemm_tn_workspace_bytes(const umoe_tgemm_tn_args* a
     return (size_t)ks * (size_t)a->part_stride * sizeof(float);
 }
 
-extern "C" int umoe_tiled_gemm_tn(const umoe_tgemm_tn_args* a, umoe_stream_t stream) {
+// acc: umoe_tiled_gemm_tn_acc -- fp32 `out`, every stored element becomes out + sum
+static int tn_entry(const umoe_tgemm_tn_args* a, umoe_stream_t stream, const bool acc) {
     UMOE_REQUIRE(a && a->groups && a->out, "umoe_tiled_gemm_tn: null argument");
     UMOE_REQUIRE(a->num_groups > 0 && a->num_groups <= TN_MAXG, "umoe_tiled_gemm_tn: 1..%d groups per launch (got %d)", TN_MAXG, a->num_groups);
     UMOE_REQUIRE((a->ldo & 3) == 0, "umoe_tiled_gemm_tn: ldo must be a multiple of 4");
@@ -544,13 +570,14 @@ extern "C" int umoe_tiled_gemm_tn(const umoe_tgemm_tn_args* a, umoe_stream_t str
                      "umoe_tiled_gemm_tn: group %d: n %% 4, column offsets %% 8, and the 8-column chunks that hold m / n must lie inside a row (m=%d n=%d)", i, g.m, g.n);
         UMOE_REQUIRE((g.k_off_dev == nullptr) == (g.k_count_dev == nullptr), "umoe_tiled_gemm_tn: group %d: k_off_dev and k_count_dev come together", i);
         UMOE_REQUIRE(g.k_count_dev || (g.k >= 0 && g.k_off >= 0), "umoe_tiled_gemm_tn: group %d: bad static window", i);
+        UMOE_REQUIRE(!acc || (reinterpret_cast<size_t>(g.out ? g.out : a->out) & 15) == 0, "umoe_tiled_gemm_tn_acc: group %d: the fp32 output must be 16-byte aligned", i);
         if (g.m > max_m) max_m = g.m;
         if (g.n > max_n) max_n = g.n;
         ragged |= g.k_count_dev != nullptr && a->num_groups > 1;
     }
     hipStream_t s = (hipStream_t)stream;
     const int ks = tn_effective_split(a);
-    if (ks == 1) return launch_tn<false>(a, max_m, max_n, ragged, 1, s);
+    if (ks == 1) return acc ? launch_tn<TN_OUT_ACC>(a, max_m, max_n, ragged, 1, s) : launch_tn<TN_OUT_BF16>(a, max_m, max_n, ragged, 1, s);
     // K split: fp32 partial slabs [k_split][part_stride] in the caller's workspace, summed in fixed order
     UMOE_REQUIRE(a->ws && ks <= 16, "umoe_tiled_gemm_tn: k_split needs a workspace (umoe_tiled_gemm_tn_workspace_bytes), k_split <= 16");
     UMOE_REQUIRE(!ragged, "umoe_tiled_gemm_tn: k_split needs static windows");
@@ -568,9 +595,13 @@ extern "C" int umoe_tiled_gemm_tn(const umoe_tgemm_tn_args* a, umoe_stream_t str
     UMOE_REQUIRE(covered == a->part_stride, "umoe_tiled_gemm_tn: k_split: the groups must cover the whole output slab (part_stride = %ld, covered %ld)", a->part_stride, covered);
     b.groups = gs;
     b.out = a->ws;
-    if (int rc = launch_tn<true>(&b, max_m, max_n, 0, ks, s)) return rc;
+    if (int rc = launch_tn<TN_OUT_F32>(&b, max_m, max_n, 0, ks, s)) return rc;
     const long n4 = a->part_stride / 4;
-    tn_reduce_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, s>>>(reinterpret_cast<const float*>(a->ws), a->part_stride, ks, n4, reinterpret_cast<uint16_t*>(a->out));
+    if (acc) tn_reduce_acc_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, s>>>(reinterpret_cast<const float*>(a->ws), a->part_stride, ks, n4, reinterpret_cast<float*>(a->out));
+    else tn_reduce_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, s>>>(reinterpret_cast<const float*>(a->ws), a->part_stride, ks, n4, reinterpret_cast<uint16_t*>(a->out));
     UMOE_LAUNCH_CHECK();
     return 0;
 }
+
+extern "C" int umoe_tiled_gemm_tn(const umoe_tgemm_tn_args* a, umoe_stream_t stream) { return tn_entry(a, stream, false); }
+extern "C" int umoe_tiled_gemm_tn_acc(const umoe_tgemm_tn_args* a, umoe_stream_t stream) { return tn_entry(a, stream, true); }

@@ -375,6 +375,13 @@ def _jitter_rows(t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
 # Shipped configuration only (ignore_differentiable_router, no token drop, ep_size 1): gradients reach the gate through
 # the softmax multipliers of the mixer's eval branch, the renormalisation and the global routing weight
 # (core.py:115-119,284,178-193), exactly the graph the reference's autograd walks.
+def _main_grads_of(triples):
+    """the (gate, up, down) fp32 main gradients of a list of expert weight triples (train.attach_main_grads), or None when some weight
+    carries none: the composite then writes bf16 gradients for all of them, as ever"""
+    mgs = [tuple(getattr(w, "main_grad", None) for w in t) for t in triples]
+    return mgs if all(m is not None for t in mgs for m in t) else None
+
+
 class _DCMoETrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, blk, x, attention_mask, aux_balance_weight, *params):
@@ -528,15 +535,17 @@ class _DCMoETrainFn(torch.autograd.Function):
             for q in range(n_loc):
                 grads[1 + 3 * q], grads[2 + 3 * q], grads[3 + 3 * q] = dwg[q], dwu[q], dwd[q]
         elif n_real:
+            mgs = _main_grads_of(ex[:n_real])
             dwg, dwu, dwd = ops.experts_swiglu_bwd([tuple(ex[e]) for e in range(n_real)], x=x, h=hbuf[:cap], gu=gu[:cap], dy=dy[:cap],
                                                    dx_slots=dxe[:cap], D=D, I=I_d, max_rows=S, counts=cnts, offsets=offs,
-                                                   slot_token=disp["slot_token"])
-            for e in range(n_real):
+                                                   slot_token=disp["slot_token"], main_grads=mgs)
+            for e in range(n_real if mgs is None else 0):      # (main gradients: added into in place, the weights get no .grad)
                 grads[1 + 3 * e], grads[2 + 3 * e], grads[3 + 3 * e] = dwg[e], dwu[e], dwd[e]
         if n_fix:
+            mgs = _main_grads_of(sh[:n_fix])
             dwg, dwu, dwd = ops.experts_swiglu_bwd([tuple(sh[i]) for i in range(n_fix)], x=x, h=hbuf[cap:], gu=gu[cap:], dy=dy[cap:],
-                                                   dx_slots=dxe[cap:], D=D, I=I_s, max_rows=S, row_base=0)
-            for i in range(n_fix):
+                                                   dx_slots=dxe[cap:], D=D, I=I_s, max_rows=S, row_base=0, main_grads=mgs)
+            for i in range(n_fix if mgs is None else 0):
                 b0 = 1 + 3 * n_loc + 3 * i
                 grads[b0], grads[b0 + 1], grads[b0 + 2] = dwg[i], dwu[i], dwd[i]
         if side is not None:

@@ -664,10 +664,15 @@ def tiled_gemm_w12(groups: Sequence[dict], a: torch.Tensor, out: torch.Tensor, *
     return out
 
 
-def tiled_gemm_tn(groups: Sequence[dict], p: torch.Tensor, q: torch.Tensor, out: torch.Tensor, *, k_split: int = 1):
+def tiled_gemm_tn(groups: Sequence[dict], p: torch.Tensor, q: torch.Tensor, out: torch.Tensor, *, k_split: int = 1, accumulate: bool = False):
     """out_g[m][n] = sum_k p[k][p_col_off + m] * q[k][q_col_off + n] over the group's row window (umoe_tiled_gemm_tn): the weight-gradient
     product dW = dY^T X on row-major activations, no transposed copies.  Group dict: m, n, optional p / q / out tensors of its own,
-    p_col_off, q_col_off, k_off + k (static window) or k_off_dev + k_count_dev (int32 device scalars), out_row_base, out_col_off."""
+    p_col_off, q_col_off, k_off + k (static window) or k_off_dev + k_count_dev (int32 device scalars), out_row_base, out_col_off.
+    accumulate: `out` (and every group's `out`) is an fp32 main gradient that the sums are ADDED to (umoe_tiled_gemm_tn_acc)."""
+    want = torch.float32 if accumulate else torch.bfloat16
+    for t in [out] + [g["out"] for g in groups if g.get("out") is not None]:
+        if t.dtype != want:
+            raise L.UmoeError(f"tiled_gemm_tn(accumulate={accumulate}): the output is {t.dtype}, not {want}")
     arr = (L.TnGroup * len(groups))()
     keep = []
     for i, g in enumerate(groups):
@@ -691,7 +696,10 @@ def tiled_gemm_tn(groups: Sequence[dict], p: torch.Tensor, q: torch.Tensor, out:
         args.part_stride = out.numel()
         ws = torch.empty(L.lib().umoe_tiled_gemm_tn_workspace_bytes(C.byref(args)), dtype=torch.uint8, device=out.device)
         args.ws = ws.data_ptr()
-    L.check(L.lib().umoe_tiled_gemm_tn(C.byref(args), _stream()), "umoe_tiled_gemm_tn")
+    if accumulate:
+        L.check(L.lib().umoe_tiled_gemm_tn_acc(C.byref(args), _stream()), "umoe_tiled_gemm_tn_acc")
+    else:
+        L.check(L.lib().umoe_tiled_gemm_tn(C.byref(args), _stream()), "umoe_tiled_gemm_tn")
     return out
 
 
@@ -704,11 +712,28 @@ def linear_input_grad(dy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return tiled_gemm([dict(w=w, w_kmajor=1, static_count=S)], dy, out, max_rows=S)
 
 
-def linear_weight_grad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+def check_main_grad(mg: torch.Tensor, w: torch.Tensor, what: str = "main_grad") -> torch.Tensor:
+    """an fp32 main gradient of `w` as the accumulate kernels take it: fp32, the parameter's shape and device, contiguous, 16-byte aligned"""
+    if not isinstance(mg, torch.Tensor) or mg.dtype != torch.float32:
+        raise L.UmoeError(f"{what}: a main gradient is an fp32 tensor (got {getattr(mg, 'dtype', type(mg).__name__)})")
+    if mg.shape != w.shape:
+        raise L.UmoeError(f"{what}: shape {tuple(mg.shape)}, the parameter's is {tuple(w.shape)}")
+    if mg.device != w.device or not mg.is_cuda:
+        raise L.UmoeError(f"{what}: on {mg.device}, the parameter on {w.device}; there is no CPU fallback")
+    if not mg.is_contiguous():
+        raise L.UmoeError(f"{what}: not contiguous (strides {mg.stride()})")
+    return mg
+
+
+def linear_weight_grad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, main_grad: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """dW [N][K] = dy[:, :N]^T x for y = x W^T (torch.nn.functional.linear backward, core.py:21-49): no transposed copies; dy may carry
-    zero-padded columns behind N (row stride a multiple of 8)."""
+    zero-padded columns behind N (row stride a multiple of 8).  main_grad (fp32 [N][K]): the product is added into it instead
+    (umoe_tiled_gemm_tn_acc, no bf16 dW is allocated) and None is returned."""
     N, K = w.shape
     assert x.shape[0] == dy.shape[0] and x.shape[1] == K and dy.shape[1] >= N
+    if main_grad is not None:
+        tiled_gemm_tn([dict(m=N, n=K, k=x.shape[0])], dy, x, check_main_grad(main_grad, w), k_split=-1, accumulate=True)
+        return None
     dw = torch.empty((N, K), dtype=torch.bfloat16, device=w.device)
     return tiled_gemm_tn([dict(m=N, n=K, k=x.shape[0])], dy, x, dw, k_split=-1)
 
@@ -731,22 +756,27 @@ def side_stream(device, tag: str = "wgrad"):
     return st
 
 
-def linear_grads(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, need_dx: bool = True, need_dw: bool = True):
+def linear_grads(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, need_dx: bool = True, need_dw: bool = True,
+                 main_grad: Optional[torch.Tensor] = None):
     """(dX, dW) of y = x W^T.  Nothing in a backward pass reads dW, so when both are wanted the weight gradient runs on a SIDE stream beside
     the input gradient (fork / join inside this call, like the expert composite in umoe_bwd.hip): the round tails of the two GEMMs and the
-    K-split reduction overlap.  UMOE_BWD_OVERLAP=0: both on the current stream."""
+    K-split reduction overlap.  UMOE_BWD_OVERLAP=0: both on the current stream.  main_grad: dW is added into that fp32 buffer
+    (linear_weight_grad) and comes back as None."""
     if not (need_dx and need_dw) or not bwd_overlap():
-        return (linear_input_grad(dy, w) if need_dx else None), (linear_weight_grad(dy, x, w) if need_dw else None)
+        return (linear_input_grad(dy, w) if need_dx else None), (linear_weight_grad(dy, x, w, main_grad) if need_dw else None)
     main = torch.cuda.current_stream()
     side = side_stream(dy.device)
     side.wait_stream(main)
     with torch.cuda.stream(side):
-        dw = linear_weight_grad(dy, x, w)
+        dw = linear_weight_grad(dy, x, w, main_grad)
     dy.record_stream(side)          # (the caching allocator must not hand these blocks out again before the side stream is through)
     x.record_stream(side)
+    if main_grad is not None:
+        main_grad.record_stream(side)
     dx = linear_input_grad(dy, w)
     main.wait_stream(side)
-    dw.record_stream(main)
+    if dw is not None:
+        dw.record_stream(main)
     return dx, dw
 
 
@@ -843,12 +873,29 @@ def rmsnorm_bwd(h: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, eps: float, 
 
 
 def experts_swiglu_bwd(ws_list, *, x, h, gu, dy, dx_slots, D: int, I: int, max_rows: int, counts=None, offsets=None, slot_token=None,
-                       row_base: int = 0):
+                       row_base: int = 0, main_grads=None):
     """umoe_grouped_swiglu_bwd (counts/offsets given: routed experts) or umoe_shared_swiglu_bwd (static groups).
-    ws_list: list of (w_gate [I,D], w_up [I,D], w_down [D,I]) row-major bf16 tensors.  Returns lists (dWg, dWu, dWd)."""
+    ws_list: list of (w_gate [I,D], w_up [I,D], w_down [D,I]) row-major bf16 tensors.  Returns lists (dWg, dWu, dWd).
+    main_grads: list of (mg_gate, mg_up, mg_down) fp32 main gradients, one triple per group -- the weight gradients are added into them
+    (umoe_*_swiglu_bwd_acc), no bf16 gradients are allocated and (None, None, None) is returned."""
     G = len(ws_list)
     dev = x.device
     arr = lambda ts: (C.c_void_p * G)(*[t.data_ptr() for t in ts])
+    if main_grads is not None:
+        if len(main_grads) != G:
+            raise L.UmoeError(f"experts_swiglu_bwd: {len(main_grads)} main-gradient triples for {G} groups")
+        mgs = [[check_main_grad(main_grads[g][k], ws_list[g][k], f"experts_swiglu_bwd: main_grads[{g}][{k}]") for g in range(G)] for k in range(3)]
+        keep = (arr([w[0] for w in ws_list]), arr([w[1] for w in ws_list]), arr([w[2] for w in ws_list]), arr(mgs[0]), arr(mgs[1]), arr(mgs[2]))
+        a = L.SwigluBwdArgs(num_groups=G, w_gate=keep[0], w_up=keep[1], w_down=keep[2], D=D, I=I, counts=_p(counts), offsets=_p(offsets),
+                            slot_token=_p(slot_token), max_rows=max_rows, slot_rows=h.shape[0], row_base=row_base,
+                            x=_p(x), ldx=x.stride(0), h=_pv(h), ldh=h.stride(0), gu=_pv(gu), ldgu=gu.stride(0), dy=_pv(dy), lddy=dy.stride(0),
+                            dx_slots=_pv(dx_slots), lddx=dx_slots.stride(0), dw_gate=keep[3], dw_up=keep[4], dw_down=keep[5])
+        nbytes = L.lib().umoe_swiglu_bwd_workspace_bytes(C.byref(a))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+        fn = L.lib().umoe_grouped_swiglu_bwd_acc if counts is not None else L.lib().umoe_shared_swiglu_bwd_acc
+        L.check(fn(C.byref(a), _stream()), "umoe_swiglu_bwd_acc (composite)")
+        return None, None, None
     # one stacked allocation per kind: the composite then runs each kind's G weight-gradient products as ONE grouped launch
     # (gate and up in ONE allocation [2][G][I][D]: the shared experts' K-split weight-gradient launch writes them as one slab)
     dwgu = torch.empty((2, G) + tuple(ws_list[0][0].shape), dtype=torch.bfloat16, device=dev)

@@ -32,6 +32,9 @@ CHUNK_ELEMS = 16384        # elements a workgroup owns at a time: 8 iterations o
 # the records of include/umoe.h (tests/test_optim_cpu.py compares them with the header through a compiled probe)
 TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("master", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("group", "<i4"),
                          ("p_fp32", "<i4")], align=True)
+# p_fp32 is a flag word: bit 0 the parameter is fp32 (its own master), bit 1 the gradient is fp32 (an fp32 main gradient of a bf16 parameter)
+P_FP32, G_FP32 = 1, 2
+FOLD_DTYPE = np.dtype([("g", "<u8"), ("main", "<u8"), ("n", "<i8")], align=True)      # umoe_optim_fold_tensor
 CHUNK_DTYPE = np.dtype([("tensor", "<i8"), ("first", "<i8")], align=True)
 RECORD_DTYPE = np.dtype([("norm", "<f4"), ("clip", "<f4"), ("skip", "<i4"), ("reserved", "<i4"), ("bc1", "<f4", (MAX_GROUPS,)),
                          ("bc2", "<f4", (MAX_GROUPS,))], align=True)
@@ -77,6 +80,28 @@ def _head(ptr: int, esize: int) -> int:
     return ((-ptr) & 15) // esize
 
 
+def main_grad_offsets(ptrs_and_sizes) -> tuple:
+    """where each tensor's run starts in one flat fp32 buffer, by the rule of AdamW._allocate: 4-element (16-byte) slots, shifted so that the
+    run is 16-byte aligned after as many elements as its bf16 parameter (a view at an odd element offset keeps its vectors).
+    ptrs_and_sizes: (data_ptr, element_size, numel) per parameter -> (offsets, total elements)"""
+    offs, cur = [], 0
+    for ptr, esize, n in ptrs_and_sizes:
+        h = _head(ptr, esize) % 4
+        o = -(-cur // 4) * 4 + (-h) % 4
+        offs.append(o)
+        cur = o + n
+    return offs, cur
+
+
+def _check_main_grad(mg, p: torch.Tensor, i: int):
+    if not isinstance(mg, torch.Tensor) or mg.dtype != torch.float32:
+        raise L.UmoeError(f"AdamW: main_grad of parameter {i} is {getattr(mg, 'dtype', type(mg).__name__)}; a main gradient is fp32")
+    if mg.shape != p.shape or not mg.is_contiguous():
+        raise L.UmoeError(f"AdamW: main_grad of parameter {i} has shape {tuple(mg.shape)} (strides {mg.stride()}), the parameter {tuple(p.shape)}")
+    if not mg.is_cuda or mg.device != p.device:
+        raise L.UmoeError(f"AdamW: main_grad of parameter {i} is on {mg.device}, the parameter on {p.device}; there is no CPU fallback")
+
+
 def _check_param(p: torch.Tensor, name: str):
     if not isinstance(p, torch.Tensor):
         raise TypeError(f"AdamW: {name} is a {type(p).__name__}, not a tensor")
@@ -102,7 +127,11 @@ class AdamW(torch.optim.Optimizer):
 
     bf16 parameters get fp32 master weights, allocated with m and v on the first step() as three flat buffers (12 bytes per bf16
     parameter); an fp32 parameter is its own master.  `grad_norm` (fp32), `steps` and `skipped_steps` (int64) are device tensors:
-    reading them is the caller's sync.  A parameter whose .grad is None is left out of that step."""
+    reading them is the caller's sync.  A parameter whose .grad is None is left out of that step.
+
+    A parameter that carries an fp32 `main_grad` (train.attach_main_grads) is updated from it: the gradient arrives without a bf16
+    rounding, `.grad` is ignored for that parameter (it must be None or all zero after MainGrads.fold()), and zero_grad() zeroes the
+    main gradients as well."""
 
     def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_grad_norm: Optional[float] = None, check_finite: bool = True, chunk_elems: int = CHUNK_ELEMS):
@@ -207,9 +236,14 @@ class AdamW(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------------------------------------------------- step
     def _sync_table(self) -> bool:
-        """re-packs and uploads the tensor table when some p / grad pointer changed; True when it did"""
+        """re-packs and uploads the tensor table when some p / grad / main-grad pointer changed; True when it did"""
         key = []
         for i, (gi, p) in enumerate(self._params):
+            mg = getattr(p, "main_grad", None)
+            if mg is not None:
+                _check_main_grad(mg, p, i)
+                key.append((p.data_ptr(), mg.data_ptr(), mg.data_ptr()))
+                continue
             g = p.grad
             if g is not None:
                 if g.dtype != p.dtype:
@@ -218,17 +252,17 @@ class AdamW(torch.optim.Optimizer):
                     raise L.UmoeError(f"AdamW: the gradient of parameter {i} is on {g.device}; there is no CPU fallback")
                 if not g.is_contiguous() or g.shape != p.shape:
                     raise L.UmoeError(f"AdamW: the gradient of parameter {i} is not contiguous (shape {tuple(g.shape)}, strides {g.stride()})")
-            key.append((p.data_ptr(), 0 if g is None else g.data_ptr()))
+            key.append((p.data_ptr(), 0 if g is None else g.data_ptr(), 0))
         key = tuple(key)
         if key == self._key:
             return False
         t = self._tensors_host
-        for i, ((gi, p), (pp, gp)) in enumerate(zip(self._params, key)):
+        for i, ((gi, p), (pp, gp, mp)) in enumerate(zip(self._params, key)):
             st = self.state[p]
             if not p.is_contiguous():
                 raise L.UmoeError(f"AdamW: parameter {i} is no longer contiguous")
             t[i] = (pp, gp, st["master"].data_ptr() if "master" in st else 0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), gi,
-                    int(p.dtype == torch.float32))
+                    (P_FP32 if p.dtype == torch.float32 else 0) | (G_FP32 if mp else 0))
         self._uploaded.synchronize()              # the previous upload (if any) has read the staging buffer
         self._staging.numpy()[:] = t.view(np.uint8).reshape(-1)
         self._tensors.copy_(self._staging, non_blocking=True)
@@ -242,7 +276,8 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if not any(p.grad is not None for _, p in self._params):      # nothing to update: no step is counted, as in torch
+        has_grad = lambda p: p.grad is not None or getattr(p, "main_grad", None) is not None      # noqa: E731
+        if not any(has_grad(p) for _, p in self._params):      # nothing to update: no step is counted, as in torch
             return loss
         self._need_state()
         hyper = make_hyper(self.param_groups, self.max_grad_norm)
@@ -267,8 +302,21 @@ class AdamW(torch.optim.Optimizer):
                                          C.byref(hyper), None, self._host_t, self._counters.data_ptr(), stream), "umoe_optim_adamw")
         self._host_t += 1
         # every pack cache of the package is keyed on (data_ptr, _version): the kernels wrote behind autograd's back
-        torch.autograd.graph.increment_version([p for _, p in self._params if p.grad is not None])
+        torch.autograd.graph.increment_version([p for _, p in self._params if has_grad(p)])
         return loss
+
+    @torch.no_grad()
+    def zero_grad(self, set_to_none: bool = True):
+        """torch's zero_grad, and the fp32 main gradients zeroed as well: one zero_() per flat buffer they are views of"""
+        super().zero_grad(set_to_none=set_to_none)
+        seen = {}
+        for _, p in self._params:
+            mg = getattr(p, "main_grad", None)
+            if mg is not None:
+                base = mg._base if mg._base is not None else mg
+                seen[id(base)] = base
+        for base in seen.values():
+            base.zero_()
 
     # ------------------------------------------------------------------------------------------------------ checkpointing
     def state_dict(self):

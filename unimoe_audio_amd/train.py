@@ -8,7 +8,7 @@ training loss :817-854; attention / RMSNorm / mRoPE arithmetic = the transformer
 Backward of the contractions: dX = dY W reads the weight as stored (k-major operand of umoe_tiled_gemm, transposing LDS reads) and
 dW = dY^T X runs on the row-major activations themselves (umoe_tiled_gemm_tn, transposing LDS reads; K split chosen by the library).  Attention backward: the fused
 flash-style kernels of umoe_attn_bwd.hip (the unfused composite of umoe_bwd.hip for shapes they do not cover).  No CPU fallback: CPU
-tensors raise.
+tensors raise.  Several micro-batches per optimizer step accumulate in fp32 main gradients (attach_main_grads, train_step_accum below).
 """
 from __future__ import annotations
 
@@ -45,7 +45,9 @@ class LinearFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy = dy.to(torch.bfloat16).contiguous()
         S = x.shape[0]
-        dx, dw = ops.linear_grads(_pad8(dy), x, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])   # [S][N] x [N][K] (weight as stored) | dy^T x
+        # (a weight that carries an fp32 main gradient gets dy^T x added into it and no .grad: attach_main_grads below)
+        dx, dw = ops.linear_grads(_pad8(dy), x, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1],    # [S][N] x [N][K] (weight as stored) | dy^T x
+                                  main_grad=getattr(w, "main_grad", None))
         db = dy.float().sum(0).to(torch.bfloat16) if ctx.has_b and ctx.needs_input_grad[2] else None
         return dx, dw, db
 
@@ -251,7 +253,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dyb = dy.to(torch.bfloat16).contiguous()
-        return ops.linear_grads(_pad8(dyb), x, w)
+        return ops.linear_grads(_pad8(dyb), x, w, main_grad=getattr(w, "main_grad", None))
 
 
 def ops_f32_head(x, w):
@@ -311,3 +313,142 @@ def train_step(model, opt, input_ids, codec_input_ids, attention_mask, codec_lab
     grad_norm = opt.grad_norm.clone() if hasattr(opt, "grad_norm") else None
     opt.zero_grad(set_to_none=set_to_none)
     return loss.detach(), codec_loss.detach(), aux_mean.detach(), grad_norm
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Gradient accumulation over micro-batches in fp32 main gradients.  bf16 `grad += dW` rounds the running sum to 8 mantissa
+# bits at every micro-batch; here every trainable bf16 parameter carries an fp32 `main_grad` instead.  The weight-gradient GEMMs of
+# LinearFn / _HeadFn and of the routed and shared experts add into it from their fp32 accumulators (umoe_tiled_gemm_tn_acc), the bf16
+# gradients autograd still produces (norm weights, biases, the router gate, q/k/v projections, the embedding tables) are folded in by one
+# chunked launch per micro-batch (umoe_optim_fold), and optim.AdamW reads the fp32 buffer.
+class MainGrads:
+    """The fp32 main gradients of a set of bf16 parameters: one flat zeroed buffer, parameter i's run at `offsets[i]` (optim.AdamW's
+    alignment rule), `p.main_grad` a view of it.  zero_(), fold(), detach(), nbytes."""
+
+    def __init__(self, params, chunk_elems: int = 16384):
+        from . import optim as O
+        import numpy as np
+        self.params = list(params)
+        if not self.params:
+            raise L.UmoeError("attach_main_grads: no trainable bf16 parameter")
+        devs = {p.device for p in self.params}
+        if len(devs) > 1 or not self.params[0].is_cuda:
+            raise L.UmoeError(f"attach_main_grads: parameters on {sorted(map(str, devs))}; one device, and there is no CPU fallback")
+        for i, p in enumerate(self.params):
+            if not p.is_contiguous():
+                raise L.UmoeError(f"attach_main_grads: parameter {i} is not contiguous (shape {tuple(p.shape)}, strides {p.stride()})")
+        dev = self.params[0].device
+        self.offsets, total = O.main_grad_offsets([(p.data_ptr(), p.element_size(), p.numel()) for p in self.params])
+        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.attach()
+        self.chunk_elems = int(chunk_elems)
+        self._chunks_host = O.build_chunk_table([p.numel() for p in self.params], self.chunk_elems)
+        self._chunks = torch.from_numpy(self._chunks_host.view(np.int64).reshape(-1, 2).copy()).to(dev)
+        self._tensors_host = np.zeros(len(self.params), dtype=O.FOLD_DTYPE)
+        self._staging = torch.empty(self._tensors_host.nbytes, dtype=torch.uint8).pin_memory()
+        self._tensors = torch.zeros(self._tensors_host.nbytes, dtype=torch.uint8, device=dev)
+        self._uploaded = torch.cuda.Event()
+        self._key = None
+
+    @property
+    def nbytes(self) -> int:
+        return self.flat.numel() * 4
+
+    def zero_(self):
+        self.flat.zero_()
+        return self
+
+    @torch.no_grad()
+    def fold(self):
+        """main_grad += float(grad), grad = +0 for every parameter whose .grad is not None: one launch on the current stream, no host sync
+        (the table is re-uploaded only when a .grad pointer changed)"""
+        import numpy as np
+        key = []
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is not None and (g.dtype != torch.bfloat16 or g.shape != p.shape or not g.is_contiguous() or g.device != p.device):
+                raise L.UmoeError(f"MainGrads.fold: the gradient of parameter {i} is {g.dtype} {tuple(g.shape)} on {g.device} (strides "
+                                  f"{g.stride()}); contiguous bf16 of the parameter's shape on its device")
+            key.append(0 if g is None else g.data_ptr())
+        key = tuple(key)
+        if not any(key) or len(self._chunks_host) == 0:
+            return self
+        fresh = key != self._key
+        if fresh:
+            t = self._tensors_host
+            for i, (p, gp) in enumerate(zip(self.params, key)):
+                t[i] = (gp, p.main_grad.data_ptr(), p.numel())
+            self._uploaded.synchronize()
+            self._staging.numpy()[:] = t.view(np.uint8).reshape(-1)
+            self._tensors.copy_(self._staging, non_blocking=True)
+            self._uploaded.record()
+            self._key = key
+        L.check(L.lib().umoe_optim_fold(self._tensors.data_ptr(), len(self.params), self._chunks.data_ptr(), len(self._chunks_host), self.chunk_elems,
+                                        self._tensors_host.ctypes.data if fresh else None, self._chunks_host.ctypes.data if fresh else None, 0,
+                                        ops._stream()), "umoe_optim_fold")
+        return self
+
+    def attach(self):
+        """(re)sets `p.main_grad` to the parameter's view of the flat buffer (what detach() removed)"""
+        for p, o in zip(self.params, self.offsets):
+            p.main_grad = self.flat[o:o + p.numel()].view(p.shape)
+        return self
+
+    def detach(self):
+        """removes the `main_grad` attributes: the model is back on the plain bf16 .grad path"""
+        for p in self.params:
+            if hasattr(p, "main_grad"):
+                del p.main_grad
+        self._key = None
+        return self
+
+
+def attach_main_grads(model_or_groups, chunk_elems: int = 16384) -> MainGrads:
+    """Gives every trainable bf16 parameter of a module (or of parameter groups / an iterable of parameters) an fp32 `main_grad`, views of
+    one flat zeroed buffer (4 bytes per parameter).  A module remembers the result (`model._main_grads`, what train_step_accum looks for)."""
+    if isinstance(model_or_groups, torch.nn.Module):
+        ps = list(model_or_groups.parameters())
+    else:
+        ps = []
+        for g in model_or_groups:
+            ps += list(g["params"]) if isinstance(g, dict) else [g]
+    seen, keep = set(), []
+    for p in ps:
+        if id(p) in seen or not p.requires_grad or p.dtype != torch.bfloat16 or p.numel() == 0:
+            continue
+        seen.add(id(p))
+        keep.append(p)
+    mg = MainGrads(keep, chunk_elems)
+    if isinstance(model_or_groups, torch.nn.Module):
+        model_or_groups._main_grads = mg
+    return mg
+
+
+def train_step_accum(model, opt, micro_batches, set_to_none: bool = False):
+    """One optimizer step over several micro-batches: for each, forward_train, (loss / A).backward() -- the weight-gradient GEMMs add into the
+    fp32 main gradients -- and MainGrads.fold() for the bf16 gradients autograd produced; then opt.step() and opt.zero_grad().
+    micro_batches: a sequence of dicts (forward_train's keyword arguments) or tuples (its positional arguments).  Main gradients are
+    attached on first use.  Returns (mean loss, mean codec loss, mean aux, grad_norm) as device tensors; nothing syncs with the host."""
+    from . import quant
+    if quant.is_released(model):
+        raise L.UmoeError("train_step_accum: the expert parameters of this model were released (expert_weights 'fp8-only' / 'w12-only'): "
+                          "inference only: `quant.dequantize_experts_` first")
+    micro_batches = list(micro_batches)
+    if not micro_batches:
+        raise ValueError("train_step_accum: no micro-batch")
+    main = getattr(model, "_main_grads", None)
+    if main is None or not all(hasattr(p, "main_grad") for p in main.params):
+        main = attach_main_grads(model)
+    A = len(micro_batches)
+    tot = None
+    for mb in micro_batches:
+        loss, codec_loss, aux_mean = forward_train(model, **mb) if isinstance(mb, dict) else forward_train(model, *mb)
+        (loss / A).backward()
+        main.fold()
+        cur = torch.stack([loss.detach().float(), codec_loss.detach().float(), aux_mean.detach().float()])
+        tot = cur if tot is None else tot + cur
+    opt.step()
+    grad_norm = opt.grad_norm.clone() if hasattr(opt, "grad_norm") else None
+    opt.zero_grad(set_to_none=set_to_none)
+    mean = tot / A
+    return mean[0], mean[1], mean[2], grad_norm
