@@ -330,6 +330,48 @@ def test_row_decoder_matches_full_decode_float64(rates):
     assert calls[True] == n_events * 2 * len(plan.layers) and calls[False] != calls[True]
 
 
+# one row; three rows that part (tests/test_dac_stream_cpu.py's schedule): (pushes per row, the flushes that end it)
+SHARED = {"one_row": ([[1], [7], [25], [1], [25], [2]], [[0]]),
+          "rows_part": ([[1, 1, 1], [7, 7, 7], [25, 25, 25], [1, 7, 7], [25, 1, 0], [2, 20, 0]], [[2], [0, 1]])}
+
+
+@pytest.mark.parametrize("name", sorted(SHARED))
+@pytest.mark.parametrize("rates", [(8, 5, 4, 2), (3, 2)])
+def test_grouped_and_row_decoder_run_one_schedule(rates, name):
+    """DacStreamDecoder and DacRowStreamDecoder on the same pushes and flushes (min_duration=1): every row is handed the same windows
+    (layer, t0, n, L_true, x_off, r_off, y_off) in the same order, and its samples are equal bit for bit"""
+    from unimoe_audio_amd.dac import DacRowStreamDecoder
+    pushes, flushes = SHARED[name]
+    model = _tiny(rates)
+    B = len(pushes[0])
+    z = torch.randn(B, model.latent_dim, max(sum(ev[r] for ev in pushes) for r in range(B)), dtype=torch.float64,
+                    generator=torch.Generator().manual_seed(3))
+
+    class Grouped(Stream64):
+        def _conv(self, ly, x, x_off, L_true, t0, n, resid, r_off, y, y_off):
+            i = self.plan.layers.index(ly)
+            g = next(g for g in self._groups if g.bufs[i] is x)
+            self.wlog.extend((i, r, t0, n, L_true, x_off, r_off, y_off) for r in g.rows)
+            super()._conv(ly, x, x_off, L_true, t0, n, resid, r_off, y, y_off)
+
+    grouped, rows = Grouped(model, B, z), _with_window_log(_rows64(DacRowStreamDecoder))(model, B, True)
+    grouped.wlog, rows.z = [], {r: z[r] for r in range(B)}
+    got = {id(dec): [[] for _ in range(B)] for dec in (grouped, rows)}
+    for dec in (grouped, rows):
+        for ev in pushes:
+            for r, a in dec.push(ev).items():
+                got[id(dec)][r].append(a.clone())
+        for ends in flushes:
+            for r, a in dec.flush(ends, min_duration=1).items():
+                got[id(dec)][r].append(a.clone())
+    for r in range(B):
+        mine = [w for w in grouped.wlog if w[1] == r]
+        assert mine and mine == [w for w in rows.wlog if w[1] == r], r
+        a, b = torch.cat(got[id(grouped)][r]), torch.cat(got[id(rows)][r])
+        n, sr = grouped.plan.out_len(sum(ev[r] for ev in pushes)), model.sample_rate
+        assert a.shape[0] == n + (int((1 - n / sr) * sr) if n < sr else 0) and torch.equal(a, b), r
+
+
 def test_flush_pads_like_dac_decode_and_reset_reopens_the_row():
     from unimoe_audio_amd.dac import DacRowStreamDecoder, stream_plan
     model = _tiny()
@@ -348,7 +390,7 @@ def test_flush_pads_like_dac_decode_and_reset_reopens_the_row():
 
 
 def test_a_reset_that_keeps_the_old_have_is_caught():
-    from unimoe_audio_amd.dac import DacRowStreamDecoder, _Row
+    from unimoe_audio_amd.dac import DacRowStreamDecoder, _Timeline
     model = _tiny((3, 2))
     Rows64 = _with_window_log(_rows64(DacRowStreamDecoder))
 
@@ -357,7 +399,7 @@ def test_a_reset_that_keeps_the_old_have_is_caught():
 
         def bad_reset(r):
             old = dec.rows[r]
-            dec.rows[r] = _Row(len(dec.plan.layers))
+            dec.rows[r] = _Timeline(len(dec.plan.layers))
             dec.rows[r].have = list(old.have)
 
         res = _drive(dec, model, reset=bad_reset if planted else None)
@@ -370,22 +412,52 @@ def test_a_reset_that_keeps_the_old_have_is_caught():
         run(True)
 
 
-def test_left_context_trimmed_one_position_too_far_is_caught():
+def _plant_trimmed_context(monkeypatch):
+    """the plant, in the one schedule both decoders run: every timeline made from here on trims buffer 0 one position too far"""
+    from unimoe_audio_amd import dac as D
+
+    class Trimmed(D._Timeline):
+        def windows(self, plan, final, room):
+            yield from super().windows(plan, final, room)
+            if self.keep[0] < self.have[0]:
+                self.keep[0] += 1                          # buffer 0 feeds a K = 7 conv: it needs its 3 positions of left context
+
+    monkeypatch.setattr(D, "_Timeline", Trimmed)
+
+
+def test_left_context_trimmed_one_position_too_far_is_caught(monkeypatch):
     from unimoe_audio_amd.dac import DacRowStreamDecoder
     model = _tiny((3, 2))
-    base = _rows64(DacRowStreamDecoder)
-
-    class Trimmed(base):
-        def _advance(self, work, r, n_new, final):
-            super()._advance(work, r, n_new, final)
-            st = self.rows[r]
-            if st.keep[0] < st.have[0]:
-                st.keep[0] += 1                            # buffer 0 feeds a K = 7 conv: it needs its 3 positions of left context
-
-    good, bad = _with_window_log(base)(model, 3, True), _with_window_log(Trimmed)(model, 3, True)
-    _drive(good, model)
+    Rows64 = _with_window_log(_rows64(DacRowStreamDecoder))
+    _drive(Rows64(model, 3, True), model)
+    _plant_trimmed_context(monkeypatch)
     with pytest.raises(AssertionError):
-        _drive(bad, model)
+        _drive(Rows64(model, 3, True), model)
+
+
+def test_left_context_trimmed_one_position_too_far_is_caught_in_the_grouped_decoder(monkeypatch):
+    model = _tiny((3, 2))
+    z = torch.randn(3, model.latent_dim, 61, dtype=torch.float64)
+    pushes, flushes = SHARED["rows_part"]
+
+    class Driven(Stream64):
+        def drive(self):
+            for ev in pushes:
+                self.push(ev)
+            for ends in flushes:
+                self.flush(ends)
+            return self.samples
+
+    assert Driven(model, 3, z).drive() == [Driven(model, 3, z).plan.out_len(n) for n in (61, 61, 40)]
+    _plant_trimmed_context(monkeypatch)
+    with pytest.raises(AssertionError) as err:
+        Driven(model, 3, z).drive()
+    # the planted reason: Stream64._conv's (kind, t0, n, first read, last read, x_off, width) says that a window of the K = 7 conv behind
+    # buffer 0 reads the one position left of what the decoder kept
+    said = re.match(r"\('conv', (\d+), (\d+), (\d+), (\d+), (\d+),", str(err.value))
+    assert said, str(err.value)
+    t0, n, first, last, x_off = map(int, said.groups())
+    assert first == max(t0 - 3, 0) == x_off - 1
 
 
 # ---------------------------------------------------------------------------------------------------- the scheduler's hook

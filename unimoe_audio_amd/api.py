@@ -35,6 +35,40 @@ class AudioChunk(NamedTuple):
     final: bool
 
 
+class _ChunkAssembler:
+    """The host side of a streamed read, for _stream_audio and serve(stream=True) alike: what a decoder's push and flush returned becomes
+    AudioChunks with one copy to the host; per request (keyed by the chunks' `row`) it tracks the next start sample and, with an
+    output_dir, keeps the PCM for the wav that write() saves."""
+
+    def __init__(self, sample_rate: int, output_dir: Optional[str]):
+        self.sample_rate, self.output_dir = sample_rate, output_dir
+        self.start, self.kept = {}, {}
+
+    def read(self, out: dict, tail: dict, rows):
+        """out / tail: {decoder row: samples} of this read's push / flush; rows: [(decoder row, request key, complete)] -> yields
+        (decoder row, AudioChunk) for every row with samples or at its end"""
+        parts = [(row, key, complete, [t for t in (out.get(row), tail.get(row)) if t is not None]) for row, key, complete in rows]
+        flat = [t for *_, ts in parts for t in ts]
+        host = torch.cat(flat).float().cpu() if flat else torch.zeros(0)      # one copy to the host per read
+        o = 0
+        for row, key, complete, ts in parts:
+            n = sum(t.numel() for t in ts)
+            pcm, o = host[o:o + n], o + n
+            if n == 0 and not complete:
+                continue
+            chunk = AudioChunk(key, self.start.get(key, 0), pcm, complete)
+            self.start[key] = chunk.start_sample + n
+            if self.output_dir is not None:
+                self.kept.setdefault(key, []).append(pcm)
+            yield row, chunk
+
+    def write(self, key, name: str):
+        """generated_<name>_<key>.wav from the PCM kept for request `key`"""
+        from .dac import write_wav_pcm16
+        os.makedirs(self.output_dir, exist_ok=True)
+        write_wav_pcm16(os.path.join(self.output_dir, f"generated_{name}_{key}.wav"), torch.cat(self.kept.pop(key))[None], self.sample_rate)
+
+
 # serve(stream=True): do the rows' DAC windows go through the per-row table kernels, one launch per layer (True), or through one
 # umoe_dac_*_win launch per layer and row (False)?  Decided by scripts/serve_stream_bench.py (profiles/serve_stream.json, DESIGN 4p).
 SERVE_STREAM_RAGGED = True
@@ -228,11 +262,11 @@ class UniMoEAudio:
         umoe_rvq_from_delayed and the streaming DAC decoder, queued on the decode stream between two replays (never on a side
         stream: see DecodeEngine.run_stream).  A row's last chunk carries _finish's min_duration=1 zero pad.
         stem: one save_name, or one per row (generate_batch)."""
-        from .dac import DacStreamDecoder, DelayedTokenSource, write_wav_pcm16
+        from .dac import DacStreamDecoder, DelayedTokenSource
         B = input_ids.shape[0] // 2
         dm = self.dac.model
         decoder = source = None
-        start, kept = [0] * B, [[] for _ in range(B)]
+        chunks = _ChunkAssembler(dm.sample_rate, output_dir)
         for upd in self._stream_updates(input_ids, attention_mask, codec_input_ids, max_audio_seconds, min_audio_seconds, chunk_frames, **gen):
             if decoder is None:
                 source = DelayedTokenSource(self.model._engine, dm)
@@ -244,25 +278,11 @@ class UniMoEAudio:
             out = decoder.push(n_new)
             ends = [row for row, _, _, complete in upd.rows if complete]
             tail = decoder.flush(ends, min_duration=1) if ends else {}
-            # one copy to the host per state read
-            parts = [(row, complete, [t for t in (out.get(row), tail.get(row)) if t is not None]) for row, _, _, complete in upd.rows]
-            flat = [t for _, _, ts in parts for t in ts]
-            host = torch.cat(flat).float().cpu() if flat else torch.zeros(0)
-            o = 0
-            for row, complete, ts in parts:
-                n = sum(t.numel() for t in ts)
-                pcm, o = host[o:o + n], o + n
-                if n == 0 and not complete:
-                    continue
-                yield AudioChunk(row, start[row], pcm, complete)
-                start[row] += pcm.numel()
-                if output_dir is not None:
-                    kept[row].append(pcm)
-        if output_dir is not None:
-            os.makedirs(output_dir, exist_ok=True)
+            for _, chunk in chunks.read(out, tail, [(row, row, complete) for row, _, _, complete in upd.rows]):
+                yield chunk
+        if output_dir is not None:                         # (the wavs at the end of the stream, as the non-streaming methods write them)
             for i in range(B):
-                name = stem if isinstance(stem, str) else stem[i]
-                write_wav_pcm16(os.path.join(output_dir, f"generated_{name}_{i}.wav"), torch.cat(kept[i])[None], dm.sample_rate)
+                chunks.write(i, stem if isinstance(stem, str) else stem[i])
 
     # ---- reference task methods (both spellings) -----------------------------------------------------------------------
     def _texts(self, obj: Union[str, List[str]]) -> List[str]:
@@ -535,14 +555,14 @@ class UniMoEAudio:
         """serve(stream=True): at every poll, before an ended row is taken and the next request admitted into it (Scheduler.run's
         hook), the frames that became final on each row's own clock (serve.final_frames) go through umoe_rvq_from_delayed_rows and the
         per-row DAC decoder; rows that ended are flushed (min_duration=1, as _finish pads) and reset for their next request."""
-        from .dac import DacRowStreamDecoder, DelayedRowsSource, write_wav_pcm16
+        from .dac import DacRowStreamDecoder, DelayedRowsSource
         from .serve import final_frames
         dm = self.dac.model
         md = max(self.model.config.codec_delay_pattern)
         source = DelayedRowsSource(eng, dm)                # (refuses a DAC with fewer codebooks than codec channels)
         decoder = DacRowStreamDecoder(dm, sched.slots, source, max_frames=sched.poll_every, ragged=ragged)
         self.serve_decoder = decoder
-        start, kept = {}, {}
+        assembler = _ChunkAssembler(dm.sample_rate, output_dir)
 
         def hook(state):
             frames = final_frames(state.tolist(), sched.engine.clock.tolist(), eng.prefill_steps, md, {row: emitted[row] for row in sched.live})
@@ -552,26 +572,13 @@ class UniMoEAudio:
             out = decoder.push(n_new)
             ends = [fr.row for fr in frames if fr.complete]
             tail = decoder.flush(ends, min_duration=1) if ends else {}
-            parts = [(fr, [t for t in (out.get(fr.row), tail.get(fr.row)) if t is not None]) for fr in frames]
-            flat = [t for _, ts in parts for t in ts]
-            host = torch.cat(flat).float().cpu() if flat else torch.zeros(0)      # one copy to the host per read
-            o, chunks = 0, []
-            for fr, ts in parts:
-                n = sum(t.numel() for t in ts)
-                pcm, o = host[o:o + n], o + n
-                if n == 0 and not fr.complete:
-                    continue
-                index = sched.live[fr.row]
-                chunks.append(AudioChunk(index, start.get(index, 0), pcm, fr.complete))
-                start[index] = start.get(index, 0) + n
-                if output_dir is not None:
-                    kept.setdefault(index, []).append(pcm)
-                if fr.complete:
-                    decoder.reset(fr.row)
+            chunks = []
+            for row, chunk in assembler.read(out, tail, [(fr.row, sched.live[fr.row], fr.complete) for fr in frames]):
+                chunks.append(chunk)
+                if chunk.final:                            # the row's request has ended: its wav now, the row ready for the next one
+                    decoder.reset(row)
                     if output_dir is not None:
-                        os.makedirs(output_dir, exist_ok=True)
-                        name = sched.engine.held[fr.row].save_name
-                        write_wav_pcm16(os.path.join(output_dir, f"generated_{name}_{index}.wav"), torch.cat(kept.pop(index))[None], dm.sample_rate)
+                        assembler.write(chunk.row, sched.engine.held[row].save_name)
             return chunks
 
         for item in sched.run(requests, hook):

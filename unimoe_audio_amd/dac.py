@@ -17,6 +17,7 @@ DESIGN 4q).  uses_mfma() decides per layer shape, for the full, windowed and per
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 import wave
@@ -473,20 +474,29 @@ class Dac:
         z = self.model.from_codes(codes.to(self.device))
         audio_out = self.model.decode(z)[0].detach().cpu()
         sr = self.model.sample_rate
-        duration = audio_out.size(1) / sr
-        if min_duration is not None and duration < min_duration:                  # utils.py:127-132
-            pad = torch.zeros((audio_out.size(0), int((min_duration - duration) * sr)), dtype=audio_out.dtype)
-            audio_out = torch.cat((audio_out, pad), dim=1)
+        pad = min_duration_pad(audio_out.size(1), sr, min_duration)
+        if pad:
+            audio_out = torch.cat((audio_out, torch.zeros((audio_out.size(0), pad), dtype=audio_out.dtype)), dim=1)
         write_wav_pcm16(save_path, audio_out, sr)
+
+
+def min_duration_pad(n_samples: int, sample_rate: int, min_duration) -> int:
+    """zero samples the reference appends so that n_samples last min_duration seconds (utils.py:127-132): Dac.decode's and both flushes'"""
+    duration = n_samples / sample_rate
+    if min_duration is None or duration >= min_duration:
+        return 0
+    return int((min_duration - duration) * sample_rate)
 
 
 # ----------------------------------------------------------------------------------------------- streaming decode
 # The decoder is a chain of convolutions with bounded receptive fields, so a prefix of the waveform is fixed by a prefix of the
-# latent frames.  stream_plan() walks the graph DacModel._run walks and derives, per conv, which input positions an output reads;
-# DacStreamDecoder keeps one buffer per layer input, trimmed to the left context the next window needs, and computes every output
-# that the frames pushed so far fully determine.  Each output runs through the windowed kernels (umoe_dac_conv1d_win /
-# umoe_dac_conv_transpose1d_win), whose arithmetic per output is that of the full-sequence kernels, so the streamed waveform is
-# bit-identical to DacModel.decode for any schedule of pushes.
+# latent frames.  stream_plan() walks the graph DacModel._run walks and derives, per conv, which input positions an output reads.
+# ONE schedule, _Timeline, turns a sequence's pushes into windows: per layer input one buffer, trimmed to the left context the next
+# window needs, and per layer every output that the frames pushed so far fully determine.  TWO executors run its windows, each over
+# storage of its own: DacStreamDecoder (rows that share a timeline, a tensor per buffer, every window run as it is produced) and
+# DacRowStreamDecoder (a timeline per row over slabs, all windows of a read recorded and run at once; further down).  Each output runs
+# through the windowed kernels (umoe_dac_conv1d_win / umoe_dac_conv_transpose1d_win, or their _rows twins), whose arithmetic per
+# output is that of the full-sequence kernels, so the streamed waveform is bit-identical to DacModel.decode for any schedule of pushes.
 
 _OPEN = 1 << 26          # true length of a sequence that is still growing: no window reads past what was pushed, so any bound works
 
@@ -585,23 +595,96 @@ def stream_plan(model: DacModel) -> StreamPlan:
     return StreamPlan(layers, hop, model.latent_dim)
 
 
-class _Group:
-    """Rows that share one timeline: buffer i holds positions [base[i], have[i]) of layer i's input ([rows, C, have - base])."""
+class _Timeline:
+    """One sequence's progress through a StreamPlan, and THE window schedule of both streaming decoders.  Buffer i (layer i's input)
+    holds positions [base[i], have[i]) from column 0 of its storage; the windows to come read none before keep[i]; have[-1] counts the
+    waveform samples computed; L: the true length per buffer, once the sequence has ended.
+    The storage belongs to the decoder: `room(i, kept, shift, n)` makes room for n more positions in buffer i behind the `kept`
+    positions [keep, have), which move `shift` columns down to column 0, and returns the column of position have.
+    samples / closed: DacRowStreamDecoder's count per row (DacStreamDecoder, whose rows leave their group at a flush, keeps lists)."""
 
-    def __init__(self, rows, n_buf):
-        self.rows = list(rows)
+    def __init__(self, n_buf):
         self.have = [0] * (n_buf + 1)
         self.keep = [0] * n_buf
         self.base = [0] * n_buf
+        self.L = None
+        self.samples = 0                               # handed out so far, a flush's pad included
+        self.closed = False
+
+    def fork(self):
+        """a second timeline at the same point of an open sequence (DacStreamDecoder: rows that part)"""
+        t = type(self)(len(self.keep))
+        t.have, t.keep, t.base = list(self.have), list(self.keep), list(self.base)
+        return t
+
+    def _room(self, room, i: int, n: int) -> int:
+        kept, shift = self.have[i] - self.keep[i], self.keep[i] - self.base[i]
+        self.base[i] = self.keep[i]
+        return room(i, kept, shift, n)
+
+    def feed(self, n_new: int, room):
+        """n_new more latent frames -> (the first one's index, its column in buffer 0)"""
+        f0, col = self.have[0], self._room(room, 0, n_new)
+        self.have[0] += n_new
+        return f0, col
+
+    def windows(self, plan: StreamPlan, final: bool, room):
+        """Per layer, in order, the outputs its input now determines (final: up to the true right edge), as
+        (layer, x_off, L_true, t0, n, r_off, y_off): RowWindow's fields without the slot.  The output buffer has its room when a window
+        is yielded, so it may be run at once or recorded; the left context is trimmed once the generator is exhausted."""
+        lys, have = plan.layers, self.have
+        if final:
+            self.L = [have[0]]
+            for ly in lys:
+                self.L.append(ly.out_len(self.L[-1]))
+        for i, ly in enumerate(lys):
+            target = self.L[i + 1] if final else ly.ready(have[i])
+            if ly.res is not None:
+                target = min(target, have[ly.res])
+            t0 = have[i + 1]
+            n = target - t0
+            if n <= 0:
+                continue
+            y_off = t0 if i + 1 == len(lys) else t0 - self._room(room, i + 1, n)
+            r_off = self.base[ly.res] if ly.res is not None else 0
+            have[i + 1] = target
+            yield i, self.base[i], self.L[i] if final else _OPEN, t0, n, r_off, y_off
+        # left context: what the next window of each reader of buffer i starts at
+        for i, ly in enumerate(lys):
+            need = max(0, ly.reads(have[i + 1], have[i + 1] + 1)[0])
+            for j, lj in enumerate(lys):
+                if lj.res == i:
+                    need = min(need, have[j + 1])
+            self.keep[i] = max(self.keep[i], min(need, have[i]))
+
+
+class _Group:
+    """Rows that share one timeline `t`: bufs[i] is buffer i of all of them, [rows, C, have - base]."""
+
+    def __init__(self, rows, n_buf):
+        self.rows = list(rows)
+        self.t = _Timeline(n_buf)
         self.bufs = [None] * n_buf
-        self.L = None                                  # true lengths per buffer, once flushed
 
     def split(self, rows):
         g = _Group(rows, len(self.bufs))
         idx = torch.tensor([self.rows.index(r) for r in rows], dtype=torch.long)
-        g.have, g.keep, g.base = list(self.have), list(self.keep), list(self.base)
+        g.t = self.t.fork()
         g.bufs = [None if b is None else b.index_select(0, idx.to(b.device)) for b in self.bufs]
         return g
+
+
+def _call_operands(dec, ly: StreamLayer):
+    """What a _win or _win_rows call of layer ly takes from dec's model: (entry suffix, weight, bias, Snake alpha), the last three as
+    device pointers; form and weight are DacModel._route's (uses_mfma stays the only rule).  Resolved once per layer and read: every push
+    and flush empties dec._ops (DacModel._folded walks all parameters, more host time than the rest of a windowed call)."""
+    ops = dec._ops.get(ly)
+    if ops is None:
+        f = dec.model._folded()
+        form, w = dec.model._route(ly.mod, f)
+        alpha = f[ly.snake] if ly.snake is not None else None
+        ops = dec._ops[ly] = ("_mfma" if form == "mfma" else "", _dev_f32(w), _dev_f32(f[ly.mod][1]), _dev_f32(alpha))
+    return ops
 
 
 class DacStreamDecoder:
@@ -620,80 +703,50 @@ class DacStreamDecoder:
         self._groups = [_Group(range(self.batch), len(self.plan.layers))]
         self.samples = [0] * self.batch
         self.closed = [False] * self.batch
+        self._ops = {}                                 # _call_operands' results of the running push / flush
 
     # ---- executor of one window (the test suite swaps in a float64 restatement) ---------------------------------------------
     def _conv(self, ly: StreamLayer, x, x_off, L_true, t0, n, resid, r_off, y, y_off):
         """outputs [t0, t0 + n) of layer ly into y (positions [y_off, ...)); x / resid hold positions from x_off / r_off"""
-        f = self.model._folded()
-        b = f[ly.mod][1]
-        form, w = self.model._route(ly.mod, f)
-        sfx = "_mfma" if form == "mfma" else ""
-        a = f[ly.snake] if ly.snake is not None else None
+        sfx, w, b, a = _call_operands(self, ly)
         assert x.shape[1] == ly.cin and y.shape[1] == ly.cout and y.shape[0] == x.shape[0]
         assert resid is None or (resid.shape[:2] == y.shape[:2])
         if ly.kind == "conv":
-            _lib_call("umoe_dac_conv1d_win" + sfx, _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), _dev_f32(resid), r_off,
+            _lib_call("umoe_dac_conv1d_win" + sfx, _dev_f32(x), x_off, x.shape[2], w, b, a, _dev_f32(resid), r_off,
                       0 if resid is None else resid.shape[2], x.shape[0], ly.cin, L_true, ly.cout, ly.K, ly.stride, ly.dil, ly.pad,
                       int(ly.tanh), t0, n, _dev_f32(y), y_off, y.shape[2], _stream())
         else:
-            _lib_call("umoe_dac_conv_transpose1d_win" + sfx, _dev_f32(x), x_off, x.shape[2], _dev_f32(w), _dev_f32(b), _dev_f32(a), x.shape[0],
+            _lib_call("umoe_dac_conv_transpose1d_win" + sfx, _dev_f32(x), x_off, x.shape[2], w, b, a, x.shape[0],
                       ly.cin, L_true, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, t0, n, _dev_f32(y), y_off, y.shape[2], _stream())
 
     def _empty(self, *shape):
         return torch.empty(shape, dtype=self.dtype, device=self.device)
 
-    def _append(self, g: _Group, i: int, C: int, n: int):
-        """room for n more positions in buffer i (keeping [keep, have)); returns (tensor, column of position have)"""
-        old, keep = g.bufs[i], g.keep[i]
-        kept = g.have[i] - keep
-        buf = self._empty(len(g.rows), C, kept + n)
+    def _append(self, g: _Group, i: int, kept: int, shift: int, n: int) -> int:
+        """_Timeline's room(): a fresh tensor for buffer i, the kept part copied to its front"""
+        old = g.bufs[i]
+        g.bufs[i] = self._empty(len(g.rows), self.plan.layers[i].cin, kept + n)
         if kept:
-            buf[:, :, :kept] = old[:, :, keep - g.base[i]: keep - g.base[i] + kept]
-        g.bufs[i], g.base[i] = buf, keep
-        return buf, kept
+            g.bufs[i][:, :, :kept] = old[:, :, shift:shift + kept]
+        return kept
 
     def _advance(self, g: _Group, n_new: int, final: bool) -> torch.Tensor:
-        P = self.plan
-        lys = P.layers
+        lys = self.plan.layers
+        room = functools.partial(self._append, g)
         if n_new:
-            buf, col = self._append(g, 0, P.latent_dim, n_new)
-            self.source(g.rows, g.have[0], n_new, buf, col)
-            g.have[0] += n_new
-        if final:
-            g.L = [g.have[0]]
-            for ly in lys:
-                g.L.append(ly.out_len(g.L[-1]))
+            f0, col = g.t.feed(n_new, room)
+            self.source(g.rows, f0, n_new, g.bufs[0], col)
         wave = None
-        t_wave = g.have[-1]
-        for i, ly in enumerate(lys):
-            target = g.L[i + 1] if final else ly.ready(g.have[i])
-            if ly.res is not None:
-                target = min(target, g.have[ly.res])
-            n = target - g.have[i + 1]
-            if n <= 0:
-                continue
-            t0 = g.have[i + 1]
-            if i + 1 == len(lys):
-                y, y_off = self._empty(len(g.rows), ly.cout, n), t0
-            else:
-                y, col = self._append(g, i + 1, ly.cout, n)
-                y_off = t0 - col
-            resid = g.bufs[ly.res] if ly.res is not None else None
-            r_off = g.base[ly.res] if ly.res is not None else 0
-            self._conv(ly, g.bufs[i], g.base[i], g.L[i] if final else _OPEN, t0, n, resid, r_off, y, y_off)
-            g.have[i + 1] = target
+        t_wave = g.t.have[-1]
+        for i, x_off, L_true, t0, n, r_off, y_off in g.t.windows(self.plan, final, room):          # every window runs as it is produced
+            ly = lys[i]
+            y = self._empty(len(g.rows), ly.cout, n) if i + 1 == len(lys) else g.bufs[i + 1]
+            self._conv(ly, g.bufs[i], x_off, L_true, t0, n, g.bufs[ly.res] if ly.res is not None else None, r_off, y, y_off)
             if i + 1 == len(lys):
                 wave = y[:, 0]
-        # left context: what the next window of each reader of buffer i starts at
-        for i, ly in enumerate(lys):
-            need = max(0, ly.reads(g.have[i + 1], g.have[i + 1] + 1)[0])
-            for j, lj in enumerate(lys):
-                if lj.res == i:
-                    need = min(need, g.have[j + 1])
-            g.keep[i] = max(g.keep[i], min(need, g.have[i]))
         if wave is None:
             wave = self._empty(len(g.rows), 0)
-        assert wave.shape[1] == g.have[-1] - t_wave
+        assert wave.shape[1] == g.t.have[-1] - t_wave
         return wave
 
     def _regroup(self, key):
@@ -713,6 +766,7 @@ class DacStreamDecoder:
         for r in range(self.batch):
             if n_new[r] and self.closed[r]:
                 raise ValueError(f"row {r} was flushed already")
+        self._ops = {}
         self._regroup(lambda r: n_new[r])
         out = {}
         for g in self._groups:
@@ -732,6 +786,7 @@ class DacStreamDecoder:
         for r in rows:
             if self.closed[r]:
                 raise ValueError(f"row {r} was flushed already")
+        self._ops = {}
         self._regroup(lambda r: r in todo)
         out = {}
         keep = []
@@ -742,11 +797,9 @@ class DacStreamDecoder:
             w = self._advance(g, 0, True)
             for k, r in enumerate(g.rows):
                 a = w[k]
-                total = self.samples[r] + a.shape[0]
-                sr = self.model.sample_rate
-                duration = total / sr
-                if min_duration is not None and duration < min_duration:                  # Dac.decode
-                    a = torch.cat((a, torch.zeros(int((min_duration - duration) * sr), dtype=a.dtype, device=a.device)))
+                pad = min_duration_pad(self.samples[r] + a.shape[0], self.model.sample_rate, min_duration)
+                if pad:
+                    a = torch.cat((a, torch.zeros(pad, dtype=a.dtype, device=a.device)))
                 out[r] = a
                 self.samples[r] += a.shape[0]
                 self.closed[r] = True
@@ -758,41 +811,60 @@ def _lib_call(name, *args):
     L.check(getattr(L.lib(), name)(*args), name)
 
 
-class DelayedTokenSource:
-    """Latent frames straight from a decode engine's delayed token buffer (umoe_rvq_from_delayed): frame t of row b reverts the delay
-    pattern, tokens[b][prefill_step_b + t + delay_c][c], and sums the codebook rows like DacModel.from_codes, bit for bit.
-    `t_valid` (dec_step + 1 of the last state read): token positions at or past it read as the pad code, as DecodeEngine.finish() has it."""
+class _DelayedSource:
+    """What both sources of latent frames share: the engine's delayed token buffer, the delay pattern, the codebooks and output
+    projections of the engine's codec channels, and THE umoe_rvq_from_delayed call.  Frame t of row b reverts the delay pattern,
+    tokens[b][prefill_step_b + t + delay_c][c], and sums the codebook rows like DacModel.from_codes, bit for bit; token positions at
+    or past t_valid read as the pad code, as DecodeEngine.finish() has it."""
 
     def __init__(self, engine, model: DacModel):
-        cfg = engine.cfg
         self.engine, self.model = engine, model
-        self.pad = int(cfg.codec_pad_value)
-        dev = engine.tokens.device
-        self.prefill = torch.tensor(engine.prefill_steps, dtype=torch.int32, device=dev)
-        self.delay = torch.tensor(list(cfg.codec_delay_pattern), dtype=torch.int32, device=dev)
+        self.pad = int(engine.cfg.codec_pad_value)
+        self.delay = torch.tensor(list(engine.cfg.codec_delay_pattern), dtype=torch.int32, device=engine.tokens.device)
+
+    def _refuse_missing_codebooks(self):
+        NQ = self.engine.tokens.shape[2]
+        if NQ > self.model.n_codebooks:
+            raise L.UmoeError(f"{NQ} codec channels, the DAC has {self.model.n_codebooks} codebooks")
+
+    def _weights(self):
+        f, NQ = self.model._folded(), self.engine.tokens.shape[2]
+        return f["cb"][:NQ].contiguous(), f["out_w"][:NQ].contiguous(), f["out_b"][:NQ].contiguous()
+
+    def _from_delayed(self, weights, *, prefill, t_valid, rows, n_rows, f0, n, out, col):
+        """frames [f0, f0 + n) of the n_rows rows whose ids the int32 tensor `rows` starts with -> out[k, :, col:col + n]; out is
+        [n_rows, Dl, W], or for one row its plane [Dl, W].  weights: _weights(), taken once per read (it goes through DacModel._folded)"""
+        B, Tmax, NQ = self.engine.tokens.shape
+        cb, ow, ob = weights
+        _lib_call("umoe_rvq_from_delayed", C.c_void_p(self.engine.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(prefill.data_ptr()),
+                  C.c_void_p(self.delay.data_ptr()), int(t_valid), self.pad, C.c_void_p(rows.data_ptr()), n_rows, f0, n,
+                  _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2], ow.shape[1], _dev_f32(out), col, out.shape[-1], _stream())
+
+
+class DelayedTokenSource(_DelayedSource):
+    """Latent frames straight from a decode engine's delayed token buffer, for DacStreamDecoder: all rows on the engine's one clock.
+    `t_valid`: dec_step + 1 of the last state read."""
+
+    def __init__(self, engine, model: DacModel):
+        super().__init__(engine, model)
+        self.prefill = torch.tensor(engine.prefill_steps, dtype=torch.int32, device=engine.tokens.device)
         self.t_valid = 0
         self._rows = {}
 
     def __call__(self, rows, f0, n, out, col):
-        eng, f = self.engine, self.model._folded()
-        B, Tmax, NQ = eng.tokens.shape
-        if NQ > self.model.n_codebooks:
-            raise L.UmoeError(f"{NQ} codec channels, the DAC has {self.model.n_codebooks} codebooks")
+        self._refuse_missing_codebooks()
         key = tuple(rows)
         if key not in self._rows:
-            self._rows[key] = torch.tensor(rows, dtype=torch.int32, device=eng.tokens.device)
-        cb = f["cb"][:NQ].contiguous()
-        ow, ob = f["out_w"][:NQ].contiguous(), f["out_b"][:NQ].contiguous()
-        _lib_call("umoe_rvq_from_delayed", C.c_void_p(eng.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(self.prefill.data_ptr()),
-                  C.c_void_p(self.delay.data_ptr()), int(self.t_valid), self.pad, C.c_void_p(self._rows[key].data_ptr()), len(rows), f0, n,
-                  _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2], ow.shape[1], _dev_f32(out), col, out.shape[2], _stream())
+            self._rows[key] = torch.tensor(rows, dtype=torch.int32, device=self.engine.tokens.device)
+        self._from_delayed(self._weights(), prefill=self.prefill, t_valid=self.t_valid, rows=self._rows[key], n_rows=len(rows), f0=f0, n=n,
+                           out=out, col=col)
 
 
 # ----------------------------------------------------------------------------------------------- one timeline per row
 # A served batch (UniMoEAudio.serve) admits every request at a poll of its own, so R live rows are on up to R timelines and
 # DacStreamDecoder would part them into R groups: R launches per layer and read, each filling a small part of the GPU.
-# DacRowStreamDecoder keeps the same schedule PER ROW (have / keep / base / L per layer, from the same StreamPlan) over slabs
-# [slots][C][W] and hands every layer the windows of all rows at once: umoe_dac_conv1d_win_rows / umoe_dac_conv_transpose1d_win_rows
+# DacRowStreamDecoder keeps one _Timeline PER ROW (the schedule above, unchanged) over slabs [slots][C][W], records the windows the
+# timelines produce and hands every layer the windows of all rows at once: umoe_dac_conv1d_win_rows / umoe_dac_conv_transpose1d_win_rows
 # read each row's window from a table (umoe.h "Per-row window tables"), one launch per layer whatever the rows are doing.
 
 DAC_ROW_FIELDS = ("x", "resid", "y", "x_off", "Lx", "r_off", "Lr", "y_off", "Ly", "t_begin", "n", "L")      # umoe.h UMOE_DAC_ROW_WORDS
@@ -817,18 +889,6 @@ class RowWindow(NamedTuple):
     y_off: int
 
 
-class _Row:
-    """the timeline of one slot: buffer i holds positions [base[i], have[i]) of layer i's input in columns [0, have - base) of its plane"""
-
-    def __init__(self, n_buf):
-        self.have = [0] * (n_buf + 1)
-        self.keep = [0] * n_buf
-        self.base = [0] * n_buf
-        self.L = None
-        self.samples = 0
-        self.closed = False
-
-
 class DacRowStreamDecoder:
     """DacStreamDecoder with one timeline per row, for rows that come and go (UniMoEAudio.serve(stream=True)).
     push(n_new): how many more latent frames each of the `slots` rows has -> {row: new samples}; flush(rows, min_duration): the true
@@ -847,7 +907,7 @@ class DacRowStreamDecoder:
         self.dtype = dtype
         self.device = device if device is not None else next(model.parameters()).device
         lys = self.plan.layers
-        self.rows = [_Row(len(lys)) for _ in range(self.slots)]
+        self.rows = [_Timeline(len(lys)) for _ in range(self.slots)]      # buffer i of row r: columns [0, have - base) of plane bufs[i][r]
         per_frame, self.chan = [1], [lys[0].cin]
         for ly in lys[:-1]:
             per_frame.append(per_frame[-1] * (ly.stride if ly.kind == "convt" else 1))
@@ -856,19 +916,16 @@ class DacRowStreamDecoder:
         self.bufs = [self._empty(self.slots, c, p * room + 64) for c, p in zip(self.chan, per_frame)]
         self.grown = 0
         self.last_plan = None          # what the last push / flush asked of the executor (tests, measurements)
+        self._ops = {}                 # _call_operands' results of the running push / flush
 
     def _empty(self, *shape):
         return torch.empty(shape, dtype=self.dtype, device=self.device)
 
-    # ---- bookkeeping: DacStreamDecoder._advance for one row, recording the work instead of doing it ---------------------------
-    def _room(self, work, r: int, i: int, n: int) -> int:
-        """room for n more positions behind have in buffer i of row r: the kept left context [keep, have) moves to column 0 (recorded, one
-        launch per buffer later); returns the column of position have"""
-        st = self.rows[r]
-        kept, shift = st.have[i] - st.keep[i], st.keep[i] - st.base[i]
+    # ---- bookkeeping: row r's timeline advances, the work is recorded instead of done -------------------------------------------
+    def _room(self, work, r: int, i: int, kept: int, shift: int, n: int) -> int:
+        """_Timeline's room() for buffer i of row r: the kept context's move to column 0 is recorded; a slab too narrow for kept + n grows"""
         if shift:
             work["shift"][i].append((r, shift, kept))
-            st.base[i] = st.keep[i]
         if kept + n > self.bufs[i].shape[2]:
             old = self.bufs[i]
             self.bufs[i] = self._empty(old.shape[0], old.shape[1], 2 * (kept + n))
@@ -877,40 +934,15 @@ class DacRowStreamDecoder:
         return kept
 
     def _advance(self, work, r: int, n_new: int, final: bool):
-        P, st = self.plan, self.rows[r]
-        lys = P.layers
+        st, room = self.rows[r], functools.partial(self._room, work, r)
         if n_new:
-            col = self._room(work, r, 0, n_new)
-            work["src"].append((r, st.have[0], n_new, col))
-            st.have[0] += n_new
-        if final:
-            st.L = [st.have[0]]
-            for ly in lys:
-                st.L.append(ly.out_len(st.L[-1]))
-        for i, ly in enumerate(lys):
-            target = st.L[i + 1] if final else ly.ready(st.have[i])
-            if ly.res is not None:
-                target = min(target, st.have[ly.res])
-            n = target - st.have[i + 1]
-            if n <= 0:
-                continue
-            t0 = st.have[i + 1]
-            y_off = t0 if i + 1 == len(lys) else t0 - self._room(work, r, i + 1, n)
-            r_off = st.base[ly.res] if ly.res is not None else 0
-            work["conv"][i].append(RowWindow(r, st.base[i], st.L[i] if final else _OPEN, t0, n, r_off, y_off))
-            st.have[i + 1] = target
-        # left context: what the next window of each reader of buffer i starts at
-        for i, ly in enumerate(lys):
-            need = max(0, ly.reads(st.have[i + 1], st.have[i + 1] + 1)[0])
-            for j, lj in enumerate(lys):
-                if lj.res == i:
-                    need = min(need, st.have[j + 1])
-            st.keep[i] = max(st.keep[i], min(need, st.have[i]))
+            f0, col = st.feed(n_new, room)
+            work["src"].append((r, f0, n_new, col))
+        for i, *window in st.windows(self.plan, final, room):
+            work["conv"][i].append(RowWindow(r, *window))
 
     # ---- executors ------------------------------------------------------------------------------------------------------------
-    def _conv(self, ly: StreamLayer, x, x_off, L_true, t0, n, resid, r_off, y, y_off):
-        """one window of one row through the _win entry (the grouped executor; the test suite swaps in a float64 restatement)"""
-        DacStreamDecoder._conv(self, ly, x, x_off, L_true, t0, n, resid, r_off, y, y_off)
+    _conv = DacStreamDecoder._conv     # one window of one row through the _win entry (the grouped executor; tests swap in float64)
 
     def _planes(self, i: int, w: RowWindow, wave):
         """(x, resid, y) of a window of layer i, each the [1, C, W] plane of the row's slot"""
@@ -933,19 +965,15 @@ class DacRowStreamDecoder:
     def _conv_rows(self, i: int, wins: List[RowWindow], wave, table):
         """layer i: the windows of all rows in one launch; table = (host [slots, 12], its device copy)"""
         ly = self.plan.layers[i]
-        f = self.model._folded()
-        b = f[ly.mod][1]
-        form, w = self.model._route(ly.mod, f)
-        sfx = "_mfma" if form == "mfma" else ""
-        a = f[ly.snake] if ly.snake is not None else None
+        sfx, w, b, a = _call_operands(self, ly)
         host, dev = table
         max_n = max((v.n for v in wins), default=0)
         if ly.kind == "conv":
-            _lib_call("umoe_dac_conv1d_win_rows" + sfx, C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n, _dev_f32(w),
-                      _dev_f32(b), _dev_f32(a), ly.cin, ly.cout, ly.K, ly.stride, ly.dil, ly.pad, int(ly.tanh), _stream())
+            _lib_call("umoe_dac_conv1d_win_rows" + sfx, C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n, w, b, a,
+                      ly.cin, ly.cout, ly.K, ly.stride, ly.dil, ly.pad, int(ly.tanh), _stream())
         else:
             _lib_call("umoe_dac_conv_transpose1d_win_rows" + sfx, C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), self.slots, max_n,
-                      _dev_f32(w), _dev_f32(b), _dev_f32(a), ly.cin, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, _stream())
+                      w, b, a, ly.cin, ly.cout, ly.K, ly.stride, ly.pad, ly.out_pad, _stream())
 
     def _tables(self, work, wave):
         """Every table of a read in one int64 tensor [source rows | per buffer the moves | per layer the windows], `slots` rows each (a
@@ -1005,7 +1033,7 @@ class DacRowStreamDecoder:
                 self._conv(ly, x, v.x_off, v.L_true, v.t0, v.n, resid, v.r_off, y, v.y_off)
 
     def _run(self, todo, final: bool, pads=None) -> dict:
-        """todo: {row: n_new}; plans every row, executes once, -> {row: samples}"""
+        """todo: {row: n_new}; plans every row, executes once, counts what it hands out -> {row: samples}"""
         lys = self.plan.layers
         work = {"src": [], "shift": [[] for _ in self.bufs], "conv": [[] for _ in lys]}
         before = {r: self.rows[r].have[-1] for r in todo}
@@ -1015,9 +1043,13 @@ class DacRowStreamDecoder:
         # the waveform of this call: plane r holds row r's new samples from column 0, then (flush) its zero pad
         width = max((got[r] + (pads[r] if pads else 0) for r in todo), default=0)
         wave = (torch.zeros if pads else torch.empty)((self.slots, 1, max(width, 1)), dtype=self.dtype, device=self.device)
-        self.last_plan = work
+        self.last_plan, self._ops = work, {}
         self._execute(work, wave)
-        return {r: wave[r, 0, :got[r] + (pads[r] if pads else 0)] for r in todo}
+        out = {r: wave[r, 0, :got[r] + (pads[r] if pads else 0)] for r in todo}
+        for r, a in out.items():
+            self.rows[r].samples += a.shape[0]
+            self.rows[r].closed = final                # (push lets only open rows through)
+        return out
 
     def push(self, n_new) -> dict:
         """n_new: more latent frames per row (`slots` ints; 0: the row is idle in this push) -> {row: new samples (1-D tensor)} for
@@ -1027,55 +1059,37 @@ class DacRowStreamDecoder:
         for r, n in enumerate(n_new):
             if n and self.rows[r].closed:
                 raise ValueError(f"row {r} was flushed already (reset it for the next request)")
-        out = self._run({r: n for r, n in enumerate(n_new) if n}, False)
-        for r, a in out.items():
-            self.rows[r].samples += a.shape[0]
-        return out
+        return self._run({r: n for r, n in enumerate(n_new) if n}, False)
 
     def flush(self, rows, min_duration=None) -> dict:
         """The rest of each row's waveform: the true right edge (a decode of T frames has plan.out_len(T) samples), then the zero pad
         Dac.decode appends when the audio is shorter than min_duration seconds -> {row: samples (1-D tensor)}"""
         rows = [rows] if isinstance(rows, int) else list(rows)
-        sr = self.model.sample_rate
         pads = {}
         for r in rows:
             st = self.rows[r]
             if st.closed:
                 raise ValueError(f"row {r} was flushed already")
-            duration = self.plan.out_len(st.have[0]) / sr if st.have[0] else 0.0
-            pads[r] = int((min_duration - duration) * sr) if min_duration is not None and duration < min_duration else 0      # Dac.decode
-        out = self._run({r: 0 for r in rows}, True, pads)
-        for r, a in out.items():
-            self.rows[r].samples += a.shape[0]
-            self.rows[r].closed = True
-        return out
+            # (known before the windows run: the pad is part of the wave tensor they write into)
+            pads[r] = min_duration_pad(self.plan.out_len(st.have[0]) if st.have[0] else 0, self.model.sample_rate, min_duration)
+        return self._run({r: 0 for r in rows}, True, pads)
 
     def reset(self, row: int):
         """row `row` (flushed, or never used) starts over: the next push is frame 0 of a new sequence"""
-        self.rows[row] = _Row(len(self.plan.layers))
+        self.rows[row] = _Timeline(len(self.plan.layers))
 
 
-class DelayedRowsSource:
-    """DelayedTokenSource for DacRowStreamDecoder: every row reads the token buffer on its own clock.  t_valid[row] (the row's local
-    step + 1 at the last state read, serve.final_frames): token positions at or past it read as the pad code.  Under the ragged
-    executor the requests of a read are one table section and one umoe_rvq_from_delayed_rows launch; called directly (the grouped
-    executor) it is one umoe_rvq_from_delayed per row."""
+class DelayedRowsSource(_DelayedSource):
+    """The source of DacRowStreamDecoder: every row reads the token buffer on its own clock.  t_valid[row]: the row's local step + 1
+    at the last state read (serve.final_frames).  Under the ragged executor the requests of a read are one table section and one
+    umoe_rvq_from_delayed_rows launch; called directly (the grouped executor) it is one umoe_rvq_from_delayed per row."""
     table_words = len(RVQ_ROW_FIELDS)
 
     def __init__(self, engine, model: DacModel):
-        cfg = engine.cfg
-        self.engine, self.model = engine, model
-        if engine.tokens.shape[2] > model.n_codebooks:
-            raise L.UmoeError(f"{engine.tokens.shape[2]} codec channels, the DAC has {model.n_codebooks} codebooks")
-        self.pad = int(cfg.codec_pad_value)
-        dev = engine.tokens.device
-        self.delay = torch.tensor(list(cfg.codec_delay_pattern), dtype=torch.int32, device=dev)
+        super().__init__(engine, model)
+        self._refuse_missing_codebooks()
         self.t_valid = [0] * engine.tokens.shape[0]
-        self._row_ids = torch.arange(engine.tokens.shape[0], dtype=torch.int32, device=dev)
-
-    def _weights(self):
-        f, NQ = self.model._folded(), self.engine.tokens.shape[2]
-        return f["cb"][:NQ].contiguous(), f["out_w"][:NQ].contiguous(), f["out_b"][:NQ].contiguous()
+        self._row_ids = torch.arange(engine.tokens.shape[0], dtype=torch.int32, device=engine.tokens.device)
 
     def _prefill(self):
         """the rows' prefill steps on the device: words [3B, 4B) of the engine's state, which admissions keep current"""
@@ -1097,11 +1111,7 @@ class DelayedRowsSource:
                   ow.shape[1], _stream())
 
     def __call__(self, requests, slab: torch.Tensor):
-        eng = self.engine
-        B, Tmax, NQ = eng.tokens.shape
-        cb, ow, ob = self._weights()
+        weights = self._weights()
         for row, f0, n, col in requests:
-            _lib_call("umoe_rvq_from_delayed", C.c_void_p(eng.tokens.data_ptr()), B, Tmax, NQ, C.c_void_p(self._prefill().data_ptr()),
-                      C.c_void_p(self.delay.data_ptr()), int(self.t_valid[row]), self.pad, C.c_void_p(self._row_ids[row:].data_ptr()), 1, f0, n,
-                      _dev_f32(cb), _dev_f32(ow), _dev_f32(ob), cb.shape[1], cb.shape[2], ow.shape[1], _dev_f32(slab[row]), col, slab.shape[2],
-                      _stream())
+            self._from_delayed(weights, prefill=self._prefill(), t_valid=self.t_valid[row], rows=self._row_ids[row:], n_rows=1, f0=f0, n=n,
+                               out=slab[row], col=col)
